@@ -2,7 +2,18 @@
 """bench.py - RIR spectrograms/sec for one full U-Net train step (forward + loss + backward + gradient
 all-reduce + Adam) on N MI355X GPUs of one node.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line (contract fields, `config`, `loss`).  Everything
+else the benchmark measures or checks - per-launch kernel brackets and the roofline, the data-parallel probe and the replica
+check, the same-invocation 1-GPU reference, and the side figures listed below - runs only with --full (--full --lean: the
+headline run with its brackets, probe and replica check, without the side figures).
+
+--dump-outputs DIR: after the timed steps, what the timed path's last step left for its caller, as DIR/<name>.npy (float32,
+float64 for the loss; at most 64 MB in all, larger arrays as a fixed seeded sample of their elements): `pred` (the
+prediction), `loss` (the step's loss), `params` (every trainable variable after the update, Keras layouts, concatenated in
+the engine's parameter order), `bn_moving` (the BatchNorm moving statistics).  Inputs, initial variables and Dropout
+seeds are fixed, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one process per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE come from the
@@ -14,7 +25,7 @@ Workload at every N: BASELINE.json configs[1] per GPU - dl_models/u_net.py UNet,
 kernels=3, batch 32 of [2,256,256] synthetic amp/phase spectrograms + [2,16] information vectors (weak scaling: the
 global batch is 32*N, configs[2] at N=8).  Prints ONE JSON line on rank 0.
 
-What the line holds besides the contract fields (N = 1):
+What the line holds besides the contract fields with --full (N = 1):
   roofline      the MFMA convolution kernels, HIP-event brackets on the launch stream inside the timed region: `frac` /
                 `frac_fwd` over the forward launches of the timed (side-stream) run, `frac_all` + `by_family` over forward,
                 data-gradient and weight-gradient launches of a short single-stream sub-run of the same process (with the
@@ -57,6 +68,40 @@ def synthetic_batch(B, H, W, device, seed):
         a[:, :, :, c0:] = 0.0
     emb = torch.randint(26, 1282, (B, 2, 16), device=device, generator=g, dtype=torch.int64)
     return spec_in.contiguous(), emb, spec_out.contiguous()
+
+
+# --dump-outputs: element caps per array (4 bytes each: 32 + 24 + 4 MB, under 64 MB in all)
+DUMP_MAX_ELEMS = {"pred": 8 << 20, "params": 6 << 20, "bn_moving": 1 << 20}
+
+
+def _sample(a, max_elems, seed):
+    """a as it is when it has at most max_elems elements, else a fixed seeded sample of max_elems of its elements (flat order,
+    the same indices for the same size on every run)."""
+    import numpy as np
+    if a.size <= max_elems:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, max_elems, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(out_dir, eng, pred, loss):
+    """What the timed path's last step left for its caller (module docstring, --dump-outputs).  eng: the engine it drove; pred: the
+    prediction as that path returns it; loss: the step's loss."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    eng.rt.synchronize()
+    params = eng.export_keras_params()
+    arrays = {
+        "pred": pred.detach().float().cpu().numpy(),
+        "loss": np.array([loss], dtype=np.float64),
+        "params": torch.cat([params[n].reshape(-1).float() for n in eng.specs]).numpy(),
+        "bn_moving": torch.cat([eng.moving[n].reshape(-1).float().cpu() for n in sorted(eng.moving)]).numpy()
+                     if eng.moving else np.zeros(0, np.float32),
+    }
+    for i, (name, a) in enumerate(arrays.items()):
+        if name in DUMP_MAX_ELEMS:
+            a = _sample(a, DUMP_MAX_ELEMS[name], 1000 + i)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _cpu_steps(F0, H, W, B, steps=5, warmups=2, budget_s=150.0):
@@ -255,9 +300,11 @@ class Runner:
             dt = float(t[0])
         return dt, fam
 
-    def engine_run(self, dtype, steps, warmup, overlap, prof=True, f0=None, size=None, depth=None, batch=None, hw=None):
-        """Trainer.step over a UNetEngine.  Returns a result dict.  hw: (H, W) of a non-square input."""
+    def engine_run(self, dtype, steps, warmup, overlap, prof=True, f0=None, size=None, depth=None, batch=None, hw=None, dump=None):
+        """Trainer.step over a UNetEngine.  Returns a result dict.  hw: (H, W) of a non-square input.  prof: kernel brackets and
+        the data-parallel probe (--full only).  dump: directory for dump_outputs of the last timed step."""
         U, a = self.U, self.args
+        prof = prof and a.full
         f0, size, depth, batch = f0 or a.f0, size or a.size, depth or a.depth, batch or a.batch
         H_, W_ = hw if hw is not None else (size, size)
         eng = U.UNetEngine(H_, W_, batch, F0=f0, k=3, depth=depth, device=self.device, n_replicas=self.world, dtype=dtype,
@@ -276,19 +323,21 @@ class Runner:
         dt, fam = self.timed(lambda: tr.step(spec_in, emb, spec_out), steps, warmup, level)
         res = {"value": batch * self.world * steps / dt, "ms_per_step": dt * 1e3 / steps, "steps": steps, "warmup": warmup,
                "dtype": dtype, "loss": tr.last_loss(), "params": eng.n_params(), "fam": fam, "overlap": overlap}
+        if dump is not None and self.rank == 0:
+            dump_outputs(dump, eng, eng.pred, res["loss"])
         if (self.world > 1 or a.force_dp) and prof:
             with DpProbe(tr) as probe:           # after the timed region
                 for _ in range(5):
                     probe.step(lambda: tr.step(spec_in, emb, spec_out))
                 self.sync()
                 res["dp_probe"] = probe.summary()
-        if self.world > 1:
+        if self.world > 1 and a.full:
             res["replicas_in_sync"] = self.replicas_in_sync(eng.theta)
         del tr, eng
         torch.cuda.empty_cache()
         return res
 
-    def module_run(self, dtype, steps, warmup, overlap):
+    def module_run(self, dtype, steps, warmup, overlap, dump=None):
         """The same workload through the drop-in boundary (the reference's loop shape, main_training.py:253-290)."""
         U, a = self.U, self.args
         gen_state = torch.random.get_rng_state()
@@ -303,15 +352,21 @@ class Runner:
         # DataGenerator.__getitem__ yields NHWC (datageneratorv2.py:101-102)
         spec_in, spec_out = spec_in.permute(0, 2, 3, 1).contiguous(), spec_out.permute(0, 2, 3, 1).contiguous()
 
+        last = {}
+
         def step():
             pred = model.model([spec_in, emb], training=True)
             loss = tr.compute_loss(spec_out, pred)
             loss.backward()
             tr.apply_gradients()
+            last["pred"] = pred
 
         dt, _ = self.timed(step, steps, warmup, 0)
         res = {"value": a.batch * self.world * steps / dt, "ms_per_step": dt * 1e3 / steps, "steps": steps, "warmup": warmup,
                "loss": tr.last_loss()}
+        if dump is not None and self.rank == 0:
+            dump_outputs(dump, model.engine, last["pred"], res["loss"])
+        last.clear()
         del tr, model
         torch.cuda.empty_cache()
         return res
@@ -435,12 +490,21 @@ def main():
                          "the value it prints is not a scaling measurement and says so")
     ap.add_argument("--through-module", action="store_true",
                     help="headline value from the drop-in boundary (UNet module + Trainer.compute_loss) instead of Trainer.step")
-    ap.add_argument("--lean", action="store_true", help="headline run only (no sub-runs, other configs or CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything besides the headline figure: kernel brackets and roofline, data-parallel probe and replica "
+                         "check, 1-GPU reference, module path, fp32 mode, other configs, CPU baseline (off: headline run only)")
+    ap.add_argument("--lean", action="store_true",
+                    help="with --full: the headline run with its brackets, probe and replica check only (no sub-runs, 1-GPU "
+                         "reference, other configs or CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (module docstring)")
     ap.add_argument("--dtype", choices=["bf16", "f32", "both"], default="both",
                     help="storage type of activations/gradients (accumulation, statistics, master weights are always fp32). "
-                         "'both' (default): bf16 is the headline line (BASELINE.json configs[1] names bf16) and the fp32 "
-                         "parity mode is measured as well and reported under 'fp32_mode'")
+                         "'both' (default): bf16 is the headline line (BASELINE.json configs[1] names bf16) and, with --full, "
+                         "the fp32 parity mode is measured as well and reported under 'fp32_mode'")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -478,11 +542,13 @@ def main():
     H = W = args.size
     overlap = not args.no_overlap
     head_dtype = "bf16" if args.dtype in ("bf16", "both") else "f32"
-    full = world == 1 and not args.lean              # side figures are single-GPU material
+    side = args.full and not args.lean
+    full = world == 1 and side                       # side figures are single-GPU material
 
-    eng_res = run.engine_run(head_dtype, args.steps, args.warmup, overlap)
+    eng_res = run.engine_run(head_dtype, args.steps, args.warmup, overlap,
+                             dump=None if args.through_module else args.dump_outputs)
     single_ref = None
-    if world > 1 and not args.lean and not args.rehearse_shared_gpu:
+    if world > 1 and side and not args.rehearse_shared_gpu:
         # thr(N) / (N thr(1)) against a 1-GPU figure of the SAME invocation: rank 0 runs the same per-GPU workload alone (no
         # collective, the other GPUs idle at the barrier behind it) - same box, same process, same kernels
         if rank == 0:
@@ -491,7 +557,8 @@ def main():
         run.sync()
     mod_res = None
     if args.through_module or full:
-        mod_res = run.module_run(head_dtype, args.steps if args.through_module else min(args.steps, 10), min(args.warmup, 3), overlap)
+        mod_res = run.module_run(head_dtype, args.steps if args.through_module else min(args.steps, 10), min(args.warmup, 3), overlap,
+                                 dump=args.dump_outputs if args.through_module else None)
     sub = f32_res = f32_sub = None
     configs = {}
     if full:

@@ -108,3 +108,45 @@ def test_data_parallel_probe_of_the_bench_line_on_two_gloo_ranks(tmp_path):
         assert all(b["issue_to_complete_ms"] is not None and b["issue_to_complete_ms"] >= 0.0 for b in s["buckets"])
         assert 0.0 < s["backward_end_at_ms"] <= s["step_ms"] and abs(s["exposed_tail_ms"] - (s["step_ms"] - s["backward_end_at_ms"])) < 1e-9
         assert at[-1] <= s["step_ms"]
+
+
+def test_dump_outputs_writes_what_the_step_left(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: after a product Trainer.step (simulated runtime) bench.dump_outputs writes the prediction, the loss,
+    the updated variables in Keras layouts and the BatchNorm moving statistics as float32 / float64 .npy files; an array over its
+    cap becomes a fixed sample of its elements, the same on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
+    import bench
+    import cpu_ops
+    import unet_rir_amd as U
+    from oracle import torch_ref as R
+    from sim_runtime import SimRuntime
+    rt = SimRuntime()
+    cpu_ops.install(monkeypatch, rt)
+    H, W, F0, B = 32, 32, 4, 2
+    eng = U.UNetEngine(H, W, B, F0=F0, k=3, device="cpu", runtime=rt, overlap_wgrad=True)
+    g = torch.Generator(); g.manual_seed(0)
+    eng.reset_parameters(g)
+    tr = U.Trainer(eng, lr=1e-3, dropout=False)
+    spec_in, emb, spec_out = (torch.tensor(a) for a in R.synthetic_batch(R.Config(H, W, F0, 3), B))
+    tr.step(spec_in, emb, spec_out)
+    loss = tr.last_loss()
+    bench.dump_outputs(str(tmp_path / "a"), eng, eng.pred, loss)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("pred", "loss", "params", "bn_moving")}
+    assert got["loss"].dtype == np.float64 and got["loss"].tolist() == [loss]
+    assert all(got[n].dtype == np.float32 for n in ("pred", "params", "bn_moving"))
+    assert np.array_equal(got["pred"], eng.pred.numpy())
+    kp = eng.export_keras_params()
+    assert np.array_equal(got["params"], np.concatenate([kp[n].reshape(-1).numpy() for n in eng.specs]))
+    assert got["bn_moving"].size == sum(v.numel() for v in eng.moving.values()) > 0
+    assert sum(bench.DUMP_MAX_ELEMS.values()) * 4 + 8 <= 64_000_000
+
+    cap = got["params"].size // 3
+    monkeypatch.setitem(bench.DUMP_MAX_ELEMS, "params", cap)
+    bench.dump_outputs(str(tmp_path / "b"), eng, eng.pred, loss)
+    bench.dump_outputs(str(tmp_path / "c"), eng, eng.pred, loss)
+    s_b, s_c = np.load(tmp_path / "b" / "params.npy"), np.load(tmp_path / "c" / "params.npy")
+    assert s_b.shape == (cap,) and np.array_equal(s_b, s_c)
+    assert np.isin(s_b, got["params"]).all()
