@@ -1,0 +1,467 @@
+"""What the two engine families share: engine.UNetEngine (the hand-scheduled U-Net) and graph.GraphEngine (the closure-list
+executor under UNetGraphEngine, ResAEEngine and AutoencoderEngine) differ in their forward and backward passes only.  The
+parameter store, its work copies and Keras layouts, the initialisers, the l2 term, the dropout mask buffers, the per-step
+device counters and the side-stream hand-overs of the backward pass live here, once.
+
+Parameters, gradients and Adam moments are four flat fp32 buffers with identical layout, ordered by backward completion so
+gradient buckets for the all-reduce are contiguous slices that become final in order; every offset is a multiple of ALIGN.
+Kernel layouts: Conv2D [Cout][k][k][Cin], Conv2DTranspose [Cin][k][k][Cout], Dense [out][in] (graph engines: [out][1][1][in]).
+"""
+import math
+import struct
+from collections import OrderedDict
+
+import torch
+
+from . import ops
+from .device import HipRuntime
+
+BN_EPS = 1e-3          # keras BatchNormalization default (dl_models/u_net.py:368)
+BN_MOMENTUM = 0.99
+L2_COEF = 1e-3         # l2(0.001) on strided Conv2D / Conv2DTranspose kernels (dl_models/u_net.py:274, :302)
+DROPOUT_P = 0.3        # dl_models/u_net.py:260
+ALIGN = 64             # parameter offsets are multiples of 64 floats (256 B)
+# parameter kinds that hold a kernel; *_padin / *_padout: the 2 real input / output channels zero-padded to PAD
+KERNEL_KINDS = ("conv", "convT", "conv_padin", "convT_padout", "conv_padout", "dense")
+
+
+def _aligned(n):
+    return -(-n // ALIGN) * ALIGN
+
+
+def _as_f32(v):
+    """v rounded to fp32, as a Python float."""
+    return struct.unpack("f", struct.pack("f", float(v)))[0]
+
+
+class ParamSpec:
+    __slots__ = ("name", "shape", "offset", "numel", "kind", "keras_shape")
+
+    def __init__(self, name, shape, kind, keras_shape):
+        self.name, self.shape, self.kind, self.keras_shape = name, tuple(shape), kind, tuple(keras_shape)
+        self.numel = int(math.prod(shape))
+        self.offset = -1
+
+    @property
+    def end(self):
+        """End of this parameter's aligned range in the flat buffers."""
+        return self.offset + _aligned(self.numel)
+
+
+class _SideStream:
+    """`with engine._wg() as ws:` - enqueue on the weight-gradient stream after everything the main stream has queued."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.ctx = None
+
+    def __enter__(self):
+        eng = self.eng
+        if eng.wg_stream is None:
+            return eng.ws
+        eng.rt.wait(eng.wg_stream, eng.rt.record())
+        self.ctx = eng.rt.on(eng.wg_stream)
+        self.ctx.__enter__()
+        eng._flush_ready()         # buckets whose hand-over was deferred to this event (see EngineBase._ready)
+        return eng.ws_w
+
+    def __exit__(self, *exc):
+        if self.ctx is not None:
+            self.ctx.__exit__(*exc)
+        return False
+
+
+class DeviceCounters:
+    """Mixin of the engines: the per-step scalars (Adam's bias-corrected rate, the dropout draw number) either travel as launch
+    arguments computed on the host (default) or live in DEVICE memory, advanced by one tiny kernel at the start of every step
+    (`use_device_counters()`): a step then consists of the same launches with the same arguments every time and can be captured
+    once into a HIP graph and replayed (trainer.Trainer(graph=True)).  The host mirrors (`adam_t`, `dropout_step`) are kept in
+    step either way; checkpoints hold the host values."""
+    n_dropout_draws = 1          # dropout masks drawn per step
+    # compute_loss switches (main_training.py:38-39, :214-222); set through trainer.Trainer(sigmoid_loss=, diff_loss=, beta=)
+    loss_diff = False            # diff_loss: the phase target is phase_true - phase of the network input
+    loss_phase_weight = None     # sigmoid_loss: fp32 [W] column weights of the phase term (device tensor)
+    _last_spec = None            # the input of the last forward pass (diff_loss through loss_from_logits)
+
+    def _loss_extras(self, spec=None):
+        if spec is not None:
+            self._last_spec = spec
+        ref = self._last_spec if self.loss_diff else None
+        if self.loss_diff and ref is None:
+            raise RuntimeError("diff_loss needs the network input of the last forward pass")
+        return {"phase_ref": ref, "phase_weight": self.loss_phase_weight}
+
+    def use_device_counters(self, on=True):
+        dev = self._shared.get("dev")
+        if not on:
+            if dev is not None:
+                dev["on"] = False          # the tensors stay alive: a captured graph may still reference them
+            return
+        if dev is None:
+            dev = self._shared["dev"] = {"state": torch.zeros(3, dtype=torch.int64, device=self.device),
+                                         "cfg": torch.zeros(8, dtype=torch.float32, device=self.device),
+                                         "hyper": torch.zeros(8, dtype=torch.float32, device=self.device), "cfg_host": None, "offset": 0,
+                                         "on": False}
+        if not dev["on"]:
+            dev["on"] = True
+            self.sync_device_counters()
+
+    def _dev(self):
+        dev = self._shared.get("dev")
+        return dev if (dev is not None and dev["on"]) else None
+
+    def sync_device_counters(self):
+        """Host counters -> device (when the mode is switched on, after reset_parameters, after a restored checkpoint)."""
+        dev = self._dev()
+        if dev is not None:
+            dev["state"].copy_(torch.tensor([self.adam_t, self._shared["dropout_step"], self._shared["dropout_step"]], dtype=torch.int64))
+
+    @property
+    def device_counters(self):
+        return self._dev()
+
+    def begin_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, n_draws=None, forward_only=False):
+        """Device counters only: the launch that opens a step (before the dropout masks are drawn; n_draws of them, default
+        n_dropout_draws).  forward_only: a pass without an optimizer step (validation) - the Adam step count stays."""
+        dev = self._dev()
+        if dev is None:
+            return
+        self.set_step_cfg(lr, beta1, beta2, eps, grad_scale)
+        ops.step_advance(dev["state"], dev["cfg"], dev["hyper"], self.n_dropout_draws if n_draws is None else n_draws, not forward_only)
+        dev["offset"] = 0
+
+    def set_step_cfg(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
+        """Device counters only: the optimizer's scalars as the next step_advance launch reads them.  Copies only when a value
+        changed (the rate changes once per epoch, main_training.py:342-344): a blocking 20-byte transfer, outside any graph."""
+        dev = self._dev()
+        cfg = (float(lr), beta1, beta2, eps, float(grad_scale))
+        if dev is not None and dev["cfg_host"] != cfg:
+            dev["cfg"][:5].copy_(torch.tensor(cfg, dtype=torch.float32))
+            dev["cfg_host"] = cfg
+
+    def _draw_mask(self, buf):
+        """Fill `buf` with the next keep mask of this engine's dropout stream."""
+        dev = self._dev()
+        if dev is None:
+            ops.dropout_mask(buf, DROPOUT_P, self.dropout_seed, self._shared["dropout_step"])
+        else:
+            ops.dropout_mask_dev(buf, DROPOUT_P, self.dropout_seed, dev["state"], dev["offset"])
+            dev["offset"] += 1
+        self._shared["dropout_step"] += 1
+        return buf
+
+    optimizer = "adam"           # "adam" | "nadam" | "sgd" (main_training.py:164-169); set through trainer.Trainer(optimizer=)
+
+    def _adam(self, lo, hi, *args):
+        dev = self._dev()
+        th, g, m, v = (self.theta, self.grad, self.adam_m, self.adam_v) if lo is None else \
+            (self.theta[lo:hi], self.grad[lo:hi], self.adam_m[lo:hi], self.adam_v[lo:hi])
+        if args[0] == "sgd":
+            ops.sgd(th, g, args[1], args[2])
+        elif args[0] == "nadam":
+            ops.nadam(th, g, m, v, *args[1:])
+        elif dev is None:
+            ops.adam(th, g, m, v, *args)
+        else:
+            ops.adam_dev(th, g, m, v, dev["hyper"])
+        self.t_dirty = True
+
+    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
+        """One optimizer step over the whole flat parameter buffer in one launch (optimizer.apply_gradients, main_training.py:268)."""
+        self._adam(None, None, *self.adam_begin(lr, beta1, beta2, eps, grad_scale))
+
+    def adam_begin(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
+        """Advance the step count once and return the arguments of adam_range for this step (bucket-wise optimizer).  Adam: the
+        bias-corrected rate; Nadam: the momentum-schedule coefficients of this step (the running product of the schedule lives
+        beside the step count); SGD: the rate."""
+        self.adam_t += 1
+        t = self.adam_t
+        if self.optimizer == "sgd":
+            return ("sgd", lr, grad_scale)
+        if self.optimizer == "nadam":
+            mu_t = beta1 * (1.0 - 0.5 * 0.96 ** (0.004 * t))
+            mu_t1 = beta1 * (1.0 - 0.5 * 0.96 ** (0.004 * (t + 1)))
+            ms_new = self._shared.get("m_schedule", 1.0) * mu_t
+            self._shared["m_schedule"] = ms_new
+            return ("nadam", lr, beta1, beta2, eps, (1.0 - mu_t) / (1.0 - ms_new), mu_t1 / (1.0 - ms_new * mu_t1), 1.0 / (1.0 - beta2 ** t), grad_scale)
+        # the betas as the kernels see them (fp32), so that the launched step and the device-counter step (step_advance_kernel computes
+        # the same expression from its fp32 cfg in fp64) produce the same bias-corrected rate bit for bit
+        b1, b2 = _as_f32(beta1), _as_f32(beta2)
+        return (lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t), beta1, beta2, eps, grad_scale)
+
+    def adam_range(self, lo, hi, *args):
+        """The optimizer on the flat parameter range [lo, hi) (element offsets, multiples of the 64-float alignment)."""
+        self._adam(lo, hi, *args)
+
+
+class EngineBase(DeviceCounters):
+    """Construction, parameter store and side-stream plumbing common to every engine (one replica, fixed batch size)."""
+
+    def __init__(self, device, n_replicas, dtype, runtime, share):
+        """runtime: stream / event provider (device.HipRuntime by default; the CPU tests pass a simulated one).
+        share: another engine of the same class and configuration whose parameters, gradients, Adam moments, work copies and
+        BatchNorm moving statistics this one aliases (only the activation buffers depend on the batch size)."""
+        self.rt = runtime if runtime is not None else HipRuntime(device)
+        if dtype not in ("f32", "bf16"):
+            raise ValueError("dtype must be 'f32' or 'bf16'")
+        # storage type of activations and their gradients; parameters, statistics and weight gradients are always fp32
+        self.dtype = dtype
+        self.adt = torch.float32 if dtype == "f32" else torch.bfloat16
+        self.PAD = 4 if dtype == "f32" else 8          # channel granule = 16 bytes (zero-padded 2-channel ends)
+        self.device = torch.device(device)
+        self.n_replicas = n_replicas
+        self.training = True
+        # state shared by every engine built over one parameter set (the model classes keep one engine per batch size)
+        self._shared = share._shared if share is not None else {"adam_t": 0, "t_dirty": True, "dropout_step": 0}
+        self.dropout_seed = share.dropout_seed if share is not None else (torch.initial_seed() & 0xFFFFFFFF)
+        self._mask_bufs = {}
+        self._pending_ready = []
+
+    def _init_side_stream(self, share, overlap_wgrad, arena_bytes, park_max_bytes=None):
+        """The weight-gradient and optimizer streams (share's when it has them), the side stream's own scratch buffer (as large as
+        self.ws is now) and the batch of parked split-K reductions (bf16 storage; ops.ReduceBatch)."""
+        self._rb = ops.ReduceBatch(self.device, arena_bytes, park_max_bytes=park_max_bytes) if ops.wgrad_defer_supported(self.dtype) else None
+        self.park_reduces = self._rb is not None          # False: every weight gradient reduces its slabs at once (A/B, scripts/ab_switch.py)
+        # two probed streams: weight gradients, and the trainer's bucket-wise optimizer (trainer.py)
+        if share is not None and overlap_wgrad and share.wg_stream is not None:
+            self.wg_stream, self.opt_stream = share.wg_stream, share.opt_stream
+        else:
+            self.wg_stream, self.opt_stream = self.rt.concurrent_streams(2) if overlap_wgrad else (None, None)
+        self.ws_w = ops.Workspace(self.device, self.ws.nbytes) if self.wg_stream is not None else self.ws
+
+    @property
+    def adam_t(self):
+        return self._shared["adam_t"]
+
+    @adam_t.setter
+    def adam_t(self, v):
+        self._shared["adam_t"] = v
+
+    @property
+    def t_dirty(self):
+        """The work copies (transposed / bf16 kernels) are older than the master parameters."""
+        return self._shared["t_dirty"]
+
+    @t_dirty.setter
+    def t_dirty(self, v):
+        self._shared["t_dirty"] = v
+
+    # ------------------------------------------------------------------ parameters
+    def _layout_params(self, specs, t_names, h_names, s2_names, share=None):
+        """Lay `specs` (backward-completion order) out in the flat buffers theta / grad / adam_m / adam_v (views p, g) and the
+        kernels' work copies: fp32 with the channel roles swapped of t_names (theta_t, views pt), bf16 in both orientations of
+        h_names (theta_h / theta_th, views ph / pth), and of the 3x3 stride-2 kernels s2_names a third bf16 copy in the order the
+        stride-2 forward kernel's LDS-DMA reads it (ppk, csrc/conv3x3d.hip).  share: alias that engine's buffers."""
+        for i, s_ in enumerate(specs):
+            s_.offset = specs[i - 1].end if i else 0
+        self.specs = OrderedDict((s_.name, s_) for s_ in specs)
+        if share is not None and [(n, s_.shape) for n, s_ in share.specs.items()] != [(n, s_.shape) for n, s_ in self.specs.items()]:
+            raise ValueError("share= needs an engine of the same configuration (only the batch size may differ)")
+
+        def buf(attr, names, dtype, min_elems):
+            if share is not None:
+                return getattr(share, attr)
+            return torch.zeros(max(sum(_aligned(self.specs[n].numel) for n in names), min_elems), dtype=dtype, device=self.device)
+
+        def views(flat, names):
+            out, o = {}, 0
+            for n in names:
+                out[n] = flat[o:o + self.specs[n].numel]
+                o += _aligned(self.specs[n].numel)
+            return out
+        self.theta, self.grad, self.adam_m, self.adam_v = (buf(a, self.specs, torch.float32, 0) for a in ("theta", "grad", "adam_m", "adam_v"))
+        self.p = {n: self.theta[s_.offset:s_.offset + s_.numel].view(s_.shape) for n, s_ in self.specs.items()}
+        self.g = {n: self.grad[s_.offset:s_.offset + s_.numel].view(s_.shape) for n, s_ in self.specs.items()}
+        self.theta_t = buf("theta_t", t_names, torch.float32, 4)
+        self.pt = views(self.theta_t, t_names)
+        self.ph, self.pth, self.ppk, self._cast_table = {}, {}, {}, None
+        if h_names:
+            self.theta_h, self.theta_th = buf("theta_h", h_names, torch.bfloat16, 8), buf("theta_th", h_names, torch.bfloat16, 8)
+            self.ph, self.pth = views(self.theta_h, h_names), views(self.theta_th, h_names)
+            if share is not None:
+                self.ppk = share.ppk
+            for n in s2_names if share is None else ():
+                ne = ops.conv3x3s2_packed_elems(self.specs[n].shape[0], self.specs[n].shape[3])
+                if ne:
+                    self.ppk[n] = torch.zeros(ne, dtype=torch.bfloat16, device=self.device)
+
+    def refresh_transposed(self):
+        """Work copies from the fp32 masters: Conv2D / Dense kernels -> [Cin][T][Cout] for dgrad, Conv2DTranspose kernels ->
+        [Cout][T][Cin] for forward; the bf16 kernels' copies (both orientations, packed) in one batched launch."""
+        for n, t in self.pt.items():
+            if n in self.ph:
+                continue                                    # bf16 kernels: both work copies come from the cast below
+            s_ = self.specs[n]
+            N, C_ = s_.shape[0], s_.shape[-1]
+            ops.transpose_weight(self.p[n], t, N, s_.numel // (N * C_), C_)
+        if self.ph:
+            if self._cast_table is None:
+                ent = []
+                for n in self.ph:
+                    s_ = self.specs[n]
+                    N, T, C_ = s_.shape[0], s_.shape[1] * s_.shape[2], s_.shape[3]
+                    ent.append((self.p[n], self.ph[n], self.pth[n], N, T, C_, C_, N, self.ppk.get(n)))
+                self._cast_table = ops.make_cast_table(ent, self.device)
+            ops.cast_weights_batched(self._cast_table)
+        self.t_dirty = False
+
+    def reset_parameters(self, generator=None):
+        """Keras default initialisers (no initialiser argument in the reference models): glorot_uniform kernels, zero biases,
+        gamma 1, beta 0, Embedding U(-0.05, 0.05)."""
+        with torch.no_grad():
+            for n, s_ in self.specs.items():
+                t, ks = self.p[n], s_.keras_shape
+                if s_.kind == "embedding":
+                    t.copy_((torch.rand(s_.shape, generator=generator) * 0.1 - 0.05).to(self.device))
+                elif s_.kind in KERNEL_KINDS:
+                    if len(ks) == 4:
+                        rf = ks[0] * ks[1]
+                        fan_in, fan_out = ks[2] * rf, ks[3] * rf
+                    else:
+                        fan_in, fan_out = ks
+                    lim = math.sqrt(6.0 / (fan_in + fan_out))
+                    w = ((torch.rand(s_.shape, generator=generator) * 2 - 1) * lim).to(self.device)
+                    if s_.kind in ("conv_padin", "convT_padout"):
+                        w[..., 2:] = 0
+                    if s_.kind == "conv_padout":
+                        w[2:] = 0
+                    t.copy_(w)
+                elif s_.kind == "gamma":
+                    t.fill_(1.0)
+                else:
+                    t.zero_()
+            for n, b in self.moving.items():
+                b.fill_(1.0 if n.endswith("variance") else 0.0)
+            self.adam_m.zero_(); self.adam_v.zero_(); self.adam_t = 0
+            self._shared["m_schedule"] = 1.0
+        self.t_dirty = True
+
+    # ---- conversion to / from the reference's own (Keras) layouts -----------------------------
+    def load_keras_params(self, params):
+        """params: name -> array in Keras layout (HWIO Conv2D, HWOI Conv2DTranspose, [in,out] Dense)."""
+        with torch.no_grad():
+            for n, s_ in self.specs.items():
+                a = torch.as_tensor(params[n]).to(torch.float32)
+                if tuple(a.shape) != s_.keras_shape:
+                    raise ValueError(f"{n}: expected Keras shape {s_.keras_shape}, got {tuple(a.shape)}")
+                t = self.p[n]
+                if s_.kind in ("conv", "convT"):
+                    t.copy_(a.permute(3, 0, 1, 2).to(self.device))
+                elif s_.kind in ("conv_padin", "convT_padout"):
+                    t.zero_(); t[..., :2].copy_(a.permute(3, 0, 1, 2).to(self.device))
+                elif s_.kind == "conv_padout":
+                    t.zero_(); t[:2].copy_(a.permute(3, 0, 1, 2).to(self.device))
+                elif s_.kind == "dense":
+                    t.copy_(a.t().reshape(t.shape).to(self.device))
+                elif s_.kind == "bias_pad":
+                    t.zero_(); t[:2].copy_(a.to(self.device))
+                else:
+                    t.copy_(a.to(self.device))
+        self.t_dirty = True
+
+    def _to_keras(self, views):
+        out = {}
+        for n, s_ in self.specs.items():
+            t = views[n].detach()
+            if s_.kind in ("conv", "convT"):
+                a = t.permute(1, 2, 3, 0)
+            elif s_.kind in ("conv_padin", "convT_padout"):
+                a = t[..., :2].permute(1, 2, 3, 0)
+            elif s_.kind == "conv_padout":
+                a = t[:2].permute(1, 2, 3, 0)
+            elif s_.kind == "dense":
+                a = t.reshape(t.shape[0], -1).t()
+            elif s_.kind == "bias_pad":
+                a = t[:2]
+            else:
+                a = t
+            out[n] = a.contiguous().cpu()
+        return out
+
+    def export_keras_params(self):
+        return self._to_keras(self.p)
+
+    def export_keras_grads(self):
+        return self._to_keras(self.g)
+
+    def n_params(self):
+        """Trainable parameter count in the reference's sense (padding excluded)."""
+        return sum(int(math.prod(s_.keras_shape)) for s_ in self.specs.values())
+
+    # ------------------------------------------------------------------ loss
+    def reg_loss(self, into=None, accumulate=False):
+        """sum(model.losses) / replicas (main_training.py:232-233), evaluated on device into reg_out[0] (or added to `into`[0])."""
+        out = self.reg_out if into is None else into
+        first = not accumulate
+        for n in self.l2_names:
+            s_ = self.specs[n]
+            ops.sumsq(self.theta[s_.offset:s_.offset + s_.numel], L2_COEF / self.n_replicas, out, not first, self.ws)
+            first = False
+        if first:
+            out.zero_()
+        return out
+
+    def loss_total(self):
+        """Data loss + l2 terms as one device scalar (a 4-byte copy and the l2 reductions accumulating onto it)."""
+        self.loss_tot.copy_(self.loss_out[0:1])
+        self.reg_loss(into=self.loss_tot, accumulate=True)
+        return self.loss_tot
+
+    def dropout_mask(self, n, generator=None, slot=0):
+        """Keep mask [B, n] of Dropout(.3) scaled by 1/(1-p).  Default: the HIP generator kernel, draw number `dropout_step` of
+        stream `dropout_seed` (reproducible; the trainer offsets the seed by the replica rank), written into one reused buffer
+        per `slot`.  With a torch generator: torch's own stream of random numbers (tests)."""
+        if generator is not None:
+            return (torch.rand((self.B, n), device=self.device, generator=generator) >= DROPOUT_P).to(torch.float32) / (1.0 - DROPOUT_P)
+        buf = self._mask_bufs.get(slot)
+        if buf is None or buf.shape[1] != n:
+            buf = self._mask_bufs[slot] = torch.empty((self.B, n), dtype=torch.float32, device=self.device)
+        return self._draw_mask(buf)
+
+    # ------------------------------------------------------------------ side stream
+    def _wg(self):
+        return _SideStream(self)
+
+    def _ready(self, on_ready, off):
+        """The gradient range [0, off) of the flat buffer is final once the launches queued so far have run: hand it over.
+        A bucket's gradients come from both streams (weight gradients: side stream; BatchNorm / fused bias / data gradients:
+        main stream).  With a side stream, the SIDE stream hands the bucket over once it has waited for the main stream's
+        progress: the all-reduce orders after both and the main stream never blocks on the side stream.  That wait is the one the
+        next `with self._wg()` performs anyway, so the hand-over is parked until then instead of putting an event record of its
+        own into the main stream (each costs ~8 us of dispatch gap; later is always safe)."""
+        if self.wg_stream is None:
+            self._hand_over(on_ready, off)
+        else:
+            self._pending_ready.append((on_ready, off))
+
+    def _hand_over(self, fn, off):
+        """on_ready(off): the gradient range [0, off) is final.  A consumer that does not run the parked split-K reductions itself
+        (the trainer's bucketer does, lazily, at its bucket boundaries: GradBucketer.before_bucket) gets them run first."""
+        if getattr(getattr(fn, "__self__", None), "before_bucket", None) is None:
+            self.flush_reduces()
+        fn(off)
+
+    def flush_reduces(self):
+        """Run the parked split-K reductions (on the current stream: the one the weight gradients ran on).  Called by the trainer's
+        bucketer before a bucket's gradients are first read, and at the end of backward()."""
+        if self._rb is not None:
+            self._rb.flush()
+
+    def _flush_ready(self):
+        """Called on the side stream right after it has waited for the main stream: hand over the parked buckets."""
+        pend, self._pending_ready = self._pending_ready, []
+        for fn, off in pend:
+            self._hand_over(fn, off)
+
+    def _join_wg(self):
+        if self.wg_stream is not None:
+            self.rt.wait(self.rt.current_stream(), self.rt.record(self.wg_stream))
+
+    def _end_backward(self):
+        """Hand over what is still parked (the bucketer runs the parked reductions first), run the reductions nobody asked for
+        yet, and join the side stream: the optimizer and the next forward (which overwrites activations) must see every
+        weight gradient."""
+        if self._pending_ready or (self._rb is not None and len(self._rb)):
+            with self._wg():
+                self.flush_reduces()
+        self._join_wg()

@@ -580,7 +580,7 @@ def sgd(theta, g, lr, grad_scale=1.0):
 
 
 def nadam(theta, g, m, v, lr, beta1, beta2, eps, c_g, c_m, c_v, grad_scale=1.0):
-    """tf.keras.optimizers.Nadam step (main_training.py:164-165) with the step's schedule coefficients (engine.DeviceCounters)."""
+    """tf.keras.optimizers.Nadam step (main_training.py:164-165) with the step's schedule coefficients (engine_base.DeviceCounters)."""
     check(_lib.lib().unetrir_nadam_f32(_p(theta), _p(g), _p(m), _p(v), theta.numel(), float(lr), beta1, beta2, eps, float(c_g), float(c_m),
                                        float(c_v), float(grad_scale), _stream()), "nadam")
 

@@ -13,8 +13,6 @@ import os
 import torch
 import torch.distributed as dist
 
-from .engine import ALIGN
-
 
 class GradBucketer:
     """Cuts a flat gradient buffer, laid out in backward-completion order, into contiguous buckets and all-reduces
@@ -184,7 +182,7 @@ class Trainer:
         self._total_on_device = False
         self._anchor = torch.zeros((), device=engine.device, requires_grad=True)     # makes compute_loss() a graph leaf's consumer
         if dp or self.adam_stream is not None:
-            bounds = [s_.offset + (-(-s_.numel // ALIGN) * ALIGN) for s_ in engine.specs.values()]
+            bounds = [s_.end for s_ in engine.specs.values()]
             self.bucketer = GradBucketer(engine.grad, bounds, bucket_bytes, group, reduce=dp,
                                          on_bucket=self._adam_bucket if self.adam_stream is not None else None, runtime=self.rt,
                                          before_bucket=getattr(engine, "flush_reduces", None))
