@@ -62,6 +62,8 @@ int unetrir_abi_version(void);
  *      an immutable snapshot of this struct; unetrir_set_config publishes a new snapshot atomically (tests, A/B scripts:
  *      process-global; a launch issued concurrently on another thread sees the old values or the new ones, never a mixture
  *      within one read - but a dispatch reads the switches more than once, so flip them between launches).  Defaults: all 1.
+ *      The order in which the convolution switches below (all but the weight-gradient ones, head_mfma, dyn_tiles and igemm2) are
+ *      tried lives in one function, plan_conv in api.hip; the kernel-id and statistics-row queries answer from it.
  *      (Rounds 3's measured refusals - one-launch BatchNorm `bn_fused`, the LDS-DMA tap-table kernel `igemm3`, the head with
  *      BatchNorm on its load path - were removed from the library in round 4; DESIGN.md keeps their numbers.)
  *        conv3x3        UNETRIR_CONV3X3        3x3 stride-1: patch-staged kernels at all (0: tap-table implicit GEMM)
@@ -389,9 +391,10 @@ int unetrir_head6x6_wgrad_bf16(const unetrir_bf16* x, int ldx, int B, int H, int
  *      ld_in of its input) has no fused statistics; the *_colstat entry points then return UNETRIR_EINVAL. */
 long long unetrir_conv2d_colstat_rows_bf16(const unetrir_conv_geom* g, int dgrad, int ld_in);
 /* which hand-written kernel serves a 3x3 stride-1 layer (forward or data gradient) under the switches in effect: for tests and
- * measurement scripts that must know what they are looking at */
+ * measurement scripts that must know what they are looking at.  PATCH: the generic patch-staged kernel (conv3x3.hip), what is left
+ * when the switches remove every specialised one */
 enum { UNETRIR_K3_TAPTABLE = 0, UNETRIR_K3_CONV3X3R = 1, UNETRIR_K3_CONV3X3G = 2, UNETRIR_K3_CONV3X3G_PAIR = 3, UNETRIR_K3_CONV3X3H = 4,
-       UNETRIR_K3_CONV3X3S = 5, UNETRIR_K3_CONV3X3P = 6, UNETRIR_K3_STEM = 7 };
+       UNETRIR_K3_CONV3X3S = 5, UNETRIR_K3_CONV3X3P = 6, UNETRIR_K3_STEM = 7, UNETRIR_K3_PATCH = 8 };
 int unetrir_conv3x3_kernel_id_bf16(const unetrir_conv_geom* g, int dgrad, int ld_in);
 int unetrir_conv2d_fwd_colstat_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* w,
                                     const float* bias, const unetrir_bf16* addend, int ldadd, unetrir_bf16* y, int ldy,

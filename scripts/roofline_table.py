@@ -42,7 +42,7 @@ def lib():
     return unet_rir_amd._lib.lib(), unet_rir_amd._lib.ConvGeom
 
 
-K3 = ("tap-table", "conv3x3r", "conv3x3g", "conv3x3g pair", "conv3x3h", "conv3x3s", "conv3x3p", "stem")
+K3 = ("tap-table", "conv3x3r", "conv3x3g", "conv3x3g pair", "conv3x3h", "conv3x3s", "conv3x3p", "stem", "patch")
 
 
 def serving_kernel(L, ConvGeom, name, cin, cout, h, k, s, tr, what):

@@ -194,41 +194,124 @@ inline int conv_family(const unetrir_conv_geom* g, int fam) {
     return (g->Cin <= 8 || g->Cout <= 8) ? 5 : fam;     // zero-padded stem / head: not part of the MFMA roofline figure
 }
 
-// element-type policies: fp32 and bf16-storage variants share the tap-table construction
-// 3x3 stride-1 layers go to the patch-staged kernel (conv3x3.hip) when its 8 x 32 pixel tiles cover the image well
-// (config switch conv3x3 = 0 forces the tap-table kernels, for A/B measurements)
-inline bool use_conv3x3(int k, int stride, int H, int W) {
-    if (!unetrir_cfg().conv3x3 || k != 3 || stride != 1) return false;
-    const double util = (double)H * W / ((double)((H + 7) / 8 * 8) * ((W + 31) / 32 * 32));
-    return util >= 0.7;
+// ---- the kernel plan: the ONE place that decides which kernel serves a forward, data-gradient or Conv2DTranspose-forward
+//      convolution launch, and how many rows of fused column statistics that kernel writes.  The entry points below launch what it
+//      chose, the query entry points (unetrir_conv2d_colstat_rows_bf16, unetrir_conv2d_transpose_colstat_rows_bf16,
+//      unetrir_conv3x3_kernel_id_bf16) return its fields, and it is the only reader of the kernel-selection switches conv3x3,
+//      conv3x3g, conv3x3g_pair, conv3x3h, conv3x3s, conv3x3r, stem, conv3x3p, conv3x3d, upconv3x3g, upconv3x3q and pw1x1 (the
+//      kernels' *_applies predicates are shape rules).
+enum class Kern { TAPTABLE, TAPTABLE_CLASSES, PATCH, STEM, CONV3X3G_PAIR, CONV3X3P, CONV3X3G, CONV3X3S, CONV3X3H, CONV3X3R, CONV3X3D,
+                  UPCONV3X3, UPCONV3X3G, UPCONV3X3Q, PW1X1 };
+struct ConvPlan {
+    Kern kernel;
+    long long colstat_rows;     // rows the kernel writes when the launch asks for statistics; 0: the *_colstat entry points refuse
+};
+
+// Direction of a launch.  FWD: Conv2D forward (also the Conv2DTranspose data gradient, on the adjoint geometry); DGRAD: Conv2D data
+// gradient; TFWD: Conv2DTranspose forward = the data-gradient form on the adjoint geometry, with a bias.
+enum Dir { FWD, DGRAD, TFWD };
+// One launch: g is the geometry the kernels see (the adjoint one for the transposed layers); `in` is x (FWD) or dy (DGRAD, TFWD).
+struct ConvCall {
+    const unetrir_conv_geom* g; Dir dir;
+    const void* in; int ldi; const void* w; const void* wpk; const float* bias; const void* addend; int ldadd; void* out; int ldo;
+    float* colstat;
+};
+
+// share of the patch-staged kernels' 8 x 32 pixel tiles that an H x W image fills
+inline double patch_util(int H, int W) { return (double)H * W / ((double)((H + 7) / 8 * 8) * ((W + 31) / 32 * 32)); }
+
+// The Conv3Args of a 3x3 launch.  Stride 1: the forward kernels, data gradient = the same kernel with flipped taps.  Stride 2 forward:
+// conv3x3d (H, W = input size; the packed weight copy only where it is defined).  Stride 2 data-gradient form: upconv3x3* on the dy grid.
+Conv3Args conv3_args(const ConvCall& c) {
+    const unetrir_conv_geom* g = c.g;
+    const bool dg = c.dir != FWD;
+    Conv3Args a{};
+    a.in = c.in; a.ldi = c.ldi; a.w = c.w; a.bias = c.bias; a.addend = c.addend; a.ldadd = c.ldadd; a.out = c.out; a.ldo = c.ldo;
+    a.colstat = c.colstat;
+    a.B = g->B; a.H = g->H; a.W = g->W; a.C = dg ? g->Cout : g->Cin; a.N = dg ? g->Cin : g->Cout;
+    if (g->stride == 1) {
+        a.flip = dg ? 1 : UNETRIR_ABL(UNETRIR_ABL_HOST(), 256) ? 2 : 0;     // ablation build only: register-staged kernel without its stores
+    } else if (dg) {
+        a.H = same_geom(g->H, 3, 2).out; a.W = same_geom(g->W, 3, 2).out;
+    } else {
+        a.wpk = (g->Cin % 64 == 0 && g->Cout % 64 == 0) ? c.wpk : nullptr;
+    }
+    return a;
 }
 
 // 1x1 layers in bf16 storage: the register-streaming kernel (pw1x1.hip).  Forward form: gather at the convolution's stride;
 // data-gradient form (also Conv2DTranspose forward): scatter at the stride, the other pixels of a 2 x 2 cell filled with bias
 // (+ addend) - for k = 1 TF 'same' has no padding at either stride, so input pixel = stride * output pixel exactly.
-inline PwArgs pw_fwd_args(const unetrir_conv_geom* g, const void* x, int ldx, const void* w, const float* bias, const void* addend,
-                          int ldadd, void* y, int ldy, float* colstat) {
-    PwArgs a{};
+PwArgs pw_args(const ConvCall& c) {
+    const unetrir_conv_geom* g = c.g;
     const Same sy = same_geom(g->H, 1, g->stride), sx = same_geom(g->W, 1, g->stride);
-    a.in = (const __bf16*)x; a.ldi = ldx; a.IH = g->H; a.IW = g->W;
-    a.w = (const __bf16*)w; a.bias = bias; a.addend = (const __bf16*)addend; a.ldadd = ldadd;
-    a.out = (__bf16*)y; a.ldo = ldy; a.OH = sy.out; a.OW = sx.out;
-    a.B = g->B; a.PH = sy.out; a.PW = sx.out; a.SI = g->stride; a.SO = 1; a.fill = 0;
-    a.C = g->Cin; a.N = g->Cout; a.colstat = colstat;
-    return a;
-}
-inline PwArgs pw_dgrad_args(const unetrir_conv_geom* g, const void* dy, int lddy, const void* wt, const float* bias, const void* addend,
-                            int ldadd, void* dx, int lddx, float* colstat) {
     PwArgs a{};
-    const Same sy = same_geom(g->H, 1, g->stride), sx = same_geom(g->W, 1, g->stride);
-    a.in = (const __bf16*)dy; a.ldi = lddy; a.IH = sy.out; a.IW = sx.out;
-    a.w = (const __bf16*)wt; a.bias = bias; a.addend = (const __bf16*)addend; a.ldadd = ldadd;
-    a.out = (__bf16*)dx; a.ldo = lddx; a.OH = g->H; a.OW = g->W;
-    a.B = g->B; a.PH = sy.out; a.PW = sx.out; a.SI = 1; a.SO = g->stride; a.fill = g->stride == 2 ? 1 : 0;
-    a.C = g->Cout; a.N = g->Cin; a.colstat = colstat;
+    a.in = (const __bf16*)c.in; a.ldi = c.ldi; a.w = (const __bf16*)c.w; a.bias = c.bias; a.addend = (const __bf16*)c.addend;
+    a.ldadd = c.ldadd; a.out = (__bf16*)c.out; a.ldo = c.ldo; a.colstat = c.colstat;
+    a.B = g->B; a.PH = sy.out; a.PW = sx.out;
+    if (c.dir == FWD) {
+        a.IH = g->H; a.IW = g->W; a.OH = sy.out; a.OW = sx.out; a.SI = g->stride; a.SO = 1; a.C = g->Cin; a.N = g->Cout;
+    } else {
+        a.IH = sy.out; a.IW = sx.out; a.OH = g->H; a.OW = g->W; a.SI = 1; a.SO = g->stride; a.fill = g->stride == 2; a.C = g->Cout;
+        a.N = g->Cin;
+    }
     return a;
 }
 
+// rows of the tap-table kernel: one per pixel tile of its iteration grid (forward: the output grid; stride-1 data gradient: the input
+// grid; stride-2 data-gradient form: the dy grid, four parity classes with a row range each)
+long long taptable_rows(const unetrir_conv_geom* g, Dir dir) {
+    const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
+    if (dir == FWD) return igemm_colstat_rows((long long)g->B * sy.out * sx.out, g->Cout);
+    if (g->stride == 1) return igemm_colstat_rows((long long)g->B * g->H * g->W, g->Cin);
+    return 4 * igemm_colstat_rows((long long)g->B * sy.out * sx.out, g->Cin, 4);
+}
+
+ConvPlan plan_conv(const ConvCall& c, bool bf16, bool stats) {
+    const unetrir_config& cfg = unetrir_cfg();
+    const unetrir_conv_geom* g = c.g;
+    if (g->k == 3 && g->stride == 1) {
+        const Conv3Args a = conv3_args(c);
+        // patch-staged kernels where their tiles cover the image well; narrow images (the 16 x 16 level) would half-fill the 32-column
+        // tiles: bf16 has a paired-image tile for them
+        const bool pair = bf16 && cfg.conv3x3g_pair && conv3x3g_pair_applies(a, cfg.conv3x3g_pair == 2);
+        if ((cfg.conv3x3 && patch_util(g->H, g->W) >= 0.7) || pair) {
+            if (!bf16) return {Kern::PATCH, 0};
+            if (cfg.stem && !stats && stem3x3_applies(a)) return {Kern::STEM, 0};         // first layer: 8 stored channels -> 64
+            if (cfg.conv3x3g) {       // the pair, then the persistent form, then the plain LDS-DMA kernel
+                if (pair) return {Kern::CONV3X3G_PAIR, conv3x3g_colstat_rows(a, true)};
+                if (cfg.conv3x3p && conv3x3p_applies(a)) return {Kern::CONV3X3P, conv3x3p_colstat_rows(a)};
+                if (conv3x3g_applies(a)) return {Kern::CONV3X3G, conv3x3g_colstat_rows(a, false)};
+            }
+            if (cfg.conv3x3s && conv3x3s_applies(a)) return {Kern::CONV3X3S, conv3x3s_colstat_rows(a)};
+            if (cfg.conv3x3h && conv3x3h_applies(a)) return {Kern::CONV3X3H, conv3x3h_colstat_rows(a)};
+            // the row-reuse kernel unless a timing ablation asks for the generic kernel's no-store variant
+            if (cfg.conv3x3r && !(a.flip & 2)) return {Kern::CONV3X3R, conv3x3r_colstat_rows(a)};
+            return {Kern::PATCH, 0};
+        }
+    }
+    if (bf16 && g->k == 1 && cfg.pw1x1 && !(stats && c.addend) && pw1x1_applies(pw_args(c)))
+        return {Kern::PW1X1, pw1x1_colstat_rows(pw_args(c))};
+    // 3x3 stride 2 has no fused statistics in either direction: its own kernels write none, and the tap-table fallback is not offered
+    if (g->stride == 1) return {Kern::TAPTABLE, taptable_rows(g, c.dir)};
+    if (c.dir == FWD) {
+        if (bf16 && g->k == 3 && cfg.conv3x3d && conv3x3d_applies(conv3_args(c))) return {Kern::CONV3X3D, 0};
+        return {Kern::TAPTABLE, g->k == 3 ? 0 : taptable_rows(g, c.dir)};
+    }
+    // stride-2 data-gradient form.  3x3, even sizes (pad_before 0): all four output parity classes in one patch-staged launch; half-empty
+    // tiles (16-wide coarse grids) stay on the four tap-table launches: measured 0.2 ms/step faster than this kernel there
+    const Same sy = same_geom(g->H, g->k, 2), sx = same_geom(g->W, g->k, 2);
+    if (g->k == 3 && sy.before == 0 && sx.before == 0 && g->H == 2 * sy.out && g->W == 2 * sx.out && patch_util(sy.out, sx.out) >= 0.7) {
+        const Conv3Args a = conv3_args(c);
+        if (bf16 && cfg.upconv3x3g && upconv3x3g_applies(a))
+            return {cfg.upconv3x3q && upconv3x3q_applies(a) ? Kern::UPCONV3X3Q : Kern::UPCONV3X3G, 0};
+        if (cfg.conv3x3) return {Kern::UPCONV3X3, 0};
+    }
+    // the four parity classes of the tap-table kernel: statistics for the Conv2DTranspose forward only
+    return {Kern::TAPTABLE_CLASSES, c.dir == TFWD && g->k != 3 ? taptable_rows(g, c.dir) : 0};
+}
+
+// element-type policies: fp32 and bf16-storage variants share the tap-table construction
 struct F32 {
     static constexpr int is_bf16 = 0;
     using T = float; using Args = IgemmArgs;
@@ -247,97 +330,37 @@ struct BF16 {
     }
 };
 
-// ---- Conv2D forward: iteration grid = output grid ----
-template <class P>
-int conv_fwd_impl(const unetrir_conv_geom* g, const typename P::T* x, int ldx, const typename P::T* w, const float* bias,
-                  const typename P::T* addend, int ldadd, typename P::T* y, int ldy, hipStream_t s, float* colstat = nullptr,
-                  const void* wpk = nullptr) {
-    if (g->k == 3 && g->stride == 1) {
-        Conv3Args c{};
-        c.colstat = colstat;
-        c.in = x; c.ldi = ldx; c.w = w; c.bias = bias; c.addend = addend; c.ldadd = ldadd; c.out = y; c.ldo = ldy;
-        c.B = g->B; c.H = g->H; c.W = g->W; c.C = g->Cin; c.N = g->Cout;
-        c.flip = UNETRIR_ABL(UNETRIR_ABL_HOST(), 256) ? 2 : 0;      // ablation build only: register-staged kernel without its stores
-        // narrow images (the 16 x 16 level) would half-fill the 32-column tiles: bf16 has a paired-image tile for them
-        if (use_conv3x3(g->k, g->stride, g->H, g->W) || (P::is_bf16 && conv3x3g_pair_applies(c))) return launch_conv3x3(c, P::is_bf16, s);
-    }
-    if constexpr (P::is_bf16) {
-        if (g->k == 3 && g->stride == 2 && !colstat) {      // strided Conv2D / Conv2DTranspose data gradient: persistent LDS-DMA kernel
-            Conv3Args c{};
-            c.in = x; c.ldi = ldx; c.w = w; c.bias = bias; c.addend = addend; c.ldadd = ldadd; c.out = y; c.ldo = ldy;
-            c.B = g->B; c.H = g->H; c.W = g->W; c.C = g->Cin; c.N = g->Cout;
-            c.wpk = (g->Cin % 64 == 0 && g->Cout % 64 == 0) ? wpk : nullptr;
-            if (conv3x3d_applies(c)) return launch_conv3x3d_bf16(c, s);
-        }
-    }
-    if constexpr (P::is_bf16) {
-        if (g->k == 1) {
-            const PwArgs pw = pw_fwd_args(g, x, ldx, w, bias, addend, ldadd, y, ldy, colstat);
-            if (pw1x1_applies(pw)) return launch_pw1x1_bf16(pw, s);
-        }
-    }
-    const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
-    typename P::Args a{};
-    a.g.B = g->B; a.g.PH = sy.out; a.g.PW = sx.out;
-    a.g.IH = g->H; a.g.IW = g->W; a.g.C = g->Cin; a.g.ldi = ldx;
-    a.g.OH = sy.out; a.g.OW = sx.out; a.g.N = g->Cout; a.g.ldo = ldy;
-    a.g.SI = g->stride; a.g.SO = 1; a.g.ooy = 0; a.g.oox = 0;
-    a.g.ntaps = g->k * g->k; a.g.wtaps = g->k * g->k;
-    for (int kh = 0; kh < g->k; ++kh)
-        for (int kw = 0; kw < g->k; ++kw)
-            a.g.tap[kh * g->k + kw] = pack_tap(kh - sy.before, kw - sx.before, kh * g->k + kw);
-    a.in = x; a.w = w; a.bias = bias; a.addend = addend; a.ldadd = ldadd; a.out = y;
-    if constexpr (P::is_bf16) a.colstat = colstat;      // tap-table kernel: one row of column statistics per 128-pixel tile
-    return P::launch(a, s);
-}
-
-// ---- Conv2D data gradient (also Conv2DTranspose forward when `bias` is given) ----
+// ---- the tap-table launches.  Forward: iteration grid = output grid.  Data-gradient form:
 // dx[q][ci] = sum_t sum_co dy[p][co] * wt[ci][t][co]  with q = p*s + (k_t - pad_before)
 template <class P>
-int conv_dgrad_impl(const unetrir_conv_geom* g, const typename P::T* dy, int lddy, const typename P::T* wt, const float* bias,
-                    const typename P::T* addend, int ldadd, typename P::T* dx, int lddx, hipStream_t s, float* colstat = nullptr) {
-    if (g->k == 3 && g->stride == 1) {     // dgrad of a stride-1 3x3 conv = the same conv with flipped taps
-        Conv3Args c{};
-        c.colstat = colstat;
-        c.in = dy; c.ldi = lddy; c.w = wt; c.bias = bias; c.addend = addend; c.ldadd = ldadd; c.out = dx; c.ldo = lddx;
-        c.B = g->B; c.H = g->H; c.W = g->W; c.C = g->Cout; c.N = g->Cin; c.flip = 1;
-        if (use_conv3x3(g->k, g->stride, g->H, g->W) || (P::is_bf16 && conv3x3g_pair_applies(c))) return launch_conv3x3(c, P::is_bf16, s);
-    }
-    if constexpr (P::is_bf16) {
-        if (g->k == 1) {
-            const PwArgs pw = pw_dgrad_args(g, dy, lddy, wt, bias, addend, ldadd, dx, lddx, colstat);
-            if (pw1x1_applies(pw)) return launch_pw1x1_bf16(pw, s);
-        }
-    }
+int launch_taptable(const ConvCall& c, hipStream_t s) {
+    const unetrir_conv_geom* g = c.g;
     const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
     typename P::Args a{};
-    a.g.B = g->B;
-    a.g.IH = sy.out; a.g.IW = sx.out; a.g.C = g->Cout; a.g.ldi = lddy;
-    a.g.OH = g->H; a.g.OW = g->W; a.g.N = g->Cin; a.g.ldo = lddx;
-    a.g.wtaps = g->k * g->k;
-    a.in = dy; a.w = wt; a.bias = bias; a.addend = addend; a.ldadd = ldadd; a.out = dx;
-    if constexpr (P::is_bf16) a.colstat = colstat;
-    if (g->stride == 1) {
-        a.g.PH = g->H; a.g.PW = g->W; a.g.SI = 1; a.g.SO = 1; a.g.ooy = 0; a.g.oox = 0;
-        a.g.ntaps = g->k * g->k;
+    a.g.B = g->B; a.g.wtaps = g->k * g->k; a.g.ntaps = g->k * g->k; a.g.SI = 1; a.g.SO = 1; a.g.ooy = 0; a.g.oox = 0;
+    a.g.ldi = c.ldi; a.g.ldo = c.ldo;
+    a.in = (const typename P::T*)c.in; a.w = (const typename P::T*)c.w; a.bias = c.bias; a.addend = (const typename P::T*)c.addend;
+    a.ldadd = c.ldadd; a.out = (typename P::T*)c.out;
+    if constexpr (P::is_bf16) a.colstat = c.colstat;      // one row of column statistics per pixel tile
+    if (c.dir == FWD) {
+        a.g.PH = sy.out; a.g.PW = sx.out; a.g.IH = g->H; a.g.IW = g->W; a.g.C = g->Cin;
+        a.g.OH = sy.out; a.g.OW = sx.out; a.g.N = g->Cout; a.g.SI = g->stride;
+        for (int kh = 0; kh < g->k; ++kh)
+            for (int kw = 0; kw < g->k; ++kw)
+                a.g.tap[kh * g->k + kw] = pack_tap(kh - sy.before, kw - sx.before, kh * g->k + kw);
+        return P::launch(a, s);
+    }
+    a.g.IH = sy.out; a.g.IW = sx.out; a.g.C = g->Cout;
+    a.g.OH = g->H; a.g.OW = g->W; a.g.N = g->Cin;
+    if (g->stride == 1) {      // dgrad of a stride-1 conv = the same conv with flipped taps
+        a.g.PH = g->H; a.g.PW = g->W;
         for (int kh = 0; kh < g->k; ++kh)
             for (int kw = 0; kw < g->k; ++kw)
                 a.g.tap[kh * g->k + kw] = pack_tap(-(kh - sy.before), -(kw - sx.before), kh * g->k + kw);
         return P::launch(a, s);
     }
-    // stride 2, 3x3, even sizes (pad_before 0): all four output parity classes in one patch-staged launch (upconv3x3.hip)
-    if (g->k == 3 && sy.before == 0 && sx.before == 0 && g->H == 2 * sy.out && g->W == 2 * sx.out) {
-        Conv3Args c{};
-        c.in = dy; c.ldi = lddy; c.w = wt; c.bias = bias; c.addend = addend; c.ldadd = ldadd; c.out = dx; c.ldo = lddx;
-        c.B = g->B; c.H = sy.out; c.W = sx.out; c.C = g->Cout; c.N = g->Cin; c.flip = 0;
-        // half-empty tiles (16-wide coarse grids) stay on the four tap-table launches: measured 0.2 ms/step faster than this kernel there
-        const double min_util = 0.7;
-        const double util = (double)c.H * c.W / ((double)((c.H + 7) / 8 * 8) * ((c.W + 31) / 32 * 32));
-        if (!colstat && (use_conv3x3(3, 1, sy.out, sx.out) || (P::is_bf16 && upconv3x3g_applies(c) && util >= min_util)))
-            return launch_upconv3x3(c, P::is_bf16, s);
-    }
     // stride 2: one launch per output parity class (ay, ax); q = 2p' + a, p = p' + (a - off)/2
-    a.g.PH = (g->H + 1) / 2; a.g.PW = (g->W + 1) / 2; a.g.SI = 1; a.g.SO = 2;
+    a.g.PH = (g->H + 1) / 2; a.g.PW = (g->W + 1) / 2; a.g.SO = 2;
     typename P::Args cls[4];
     for (int ay = 0; ay < 2; ++ay)
         for (int ax = 0; ax < 2; ++ax) {
@@ -353,11 +376,48 @@ int conv_dgrad_impl(const unetrir_conv_geom* g, const typename P::T* dy, int ldd
             }
             a.g.ntaps = nt; a.g.ooy = ay; a.g.oox = ax;
             if constexpr (P::is_bf16) {      // column statistics: the four classes write consecutive row ranges
-                if (colstat) a.colstat = colstat + (size_t)(ay * 2 + ax) * igemm_colstat_rows((long long)g->B * a.g.PH * a.g.PW, g->Cin, 4) * g->Cin * 2;
+                if (c.colstat) a.colstat = c.colstat + (size_t)(ay * 2 + ax) * igemm_colstat_rows((long long)g->B * a.g.PH * a.g.PW, g->Cin, 4) * g->Cin * 2;
             }
             cls[ay * 2 + ax] = a;
         }
     return P::launch_classes(cls, s);       // bf16: the four classes share one grid
+}
+
+template <class P>
+int launch_planned(const ConvCall& c, Kern k, hipStream_t s) {
+    switch (k) {
+        case Kern::TAPTABLE: case Kern::TAPTABLE_CLASSES: return launch_taptable<P>(c, s);
+        case Kern::PATCH: return launch_conv3x3(conv3_args(c), P::is_bf16, s);
+        case Kern::STEM: return launch_stem3x3_bf16(conv3_args(c), s);
+        case Kern::CONV3X3G_PAIR: return launch_conv3x3g_bf16(conv3_args(c), true, s);
+        case Kern::CONV3X3P: return launch_conv3x3p_bf16(conv3_args(c), s);
+        case Kern::CONV3X3G: return launch_conv3x3g_bf16(conv3_args(c), false, s);
+        case Kern::CONV3X3S: return launch_conv3x3s_bf16(conv3_args(c), s);
+        case Kern::CONV3X3H: return launch_conv3x3h_bf16(conv3_args(c), s);
+        case Kern::CONV3X3R: return launch_conv3x3r_bf16(conv3_args(c), s);
+        case Kern::CONV3X3D: return launch_conv3x3d_bf16(conv3_args(c), s);
+        case Kern::UPCONV3X3: return launch_upconv3x3(conv3_args(c), P::is_bf16, s);
+        case Kern::UPCONV3X3G: return launch_upconv3x3g_bf16(conv3_args(c), s);
+        case Kern::UPCONV3X3Q: return launch_upconv3x3q_bf16(conv3_args(c), s);
+        case Kern::PW1X1: return launch_pw1x1_bf16(pw_args(c), s);
+    }
+    return UNETRIR_EINVAL;
+}
+
+// Plan and launch.  With a statistics buffer the plan must offer statistics (else UNETRIR_EINVAL).  dominant: profile the launch under
+// UNETRIR_FAM_DOMINANT as well when the plan picked conv3x3p (the dominant kernel of the bf16 step).
+template <class P>
+int run_conv(const ConvCall& c, int fam, double flops, hipStream_t s, bool dominant = false) {
+    const ConvPlan p = plan_conv(c, P::is_bf16, c.colstat != nullptr);
+    if (c.colstat && p.colstat_rows == 0) return UNETRIR_EINVAL;
+    ProfScope ps(fam, flops, s, dominant && p.kernel == Kern::CONV3X3P ? UNETRIR_FAM_DOMINANT : -1);
+    return launch_planned<P>(c, p.kernel, s);
+}
+
+// what the query entry points describe: a bf16 launch with aligned buffers, no addend, output rows as wide as the output channels
+ConvPlan plan_query(const unetrir_conv_geom* g, Dir dir, int ld_in, bool stats) {
+    const ConvCall c{g, dir, nullptr, ld_in, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dir == FWD ? g->Cout : g->Cin, nullptr};
+    return plan_conv(c, true, stats);
 }
 
 void wgrad_args(const unetrir_conv_geom* g, int ldx, int lddy, WgradArgs* a) {
@@ -447,15 +507,15 @@ int unetrir_abi_version(void) { return UNETRIR_ABI_VERSION; }
 int unetrir_conv2d_fwd_f32(const unetrir_conv_geom* g, const float* x, int ldx, const float* w, const float* bias,
                            const float* addend, int ldadd, float* y, int ldy, unetrir_stream_t stream) {
     if (!geom_ok(g) || !x || !w || !y || (g->Cin & 3) || !ld_ok(ldx, g->Cin) || ldy < g->Cout) return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_FWD), conv_flops(g), (hipStream_t)stream);
-    return conv_fwd_impl<F32>(g, x, ldx, w, bias, addend, ldadd, y, ldy, (hipStream_t)stream);
+    return run_conv<F32>({g, FWD, x, ldx, w, nullptr, bias, addend, ldadd, y, ldy, nullptr}, conv_family(g, UNETRIR_FAM_CONV_FWD),
+                         conv_flops(g), (hipStream_t)stream);
 }
 
 int unetrir_conv2d_dgrad_f32(const unetrir_conv_geom* g, const float* dy, int lddy, const float* wt,
                              const float* addend, int ldadd, float* dx, int lddx, unetrir_stream_t stream) {
     if (!geom_ok(g) || !dy || !wt || !dx || (g->Cout & 3) || !ld_ok(lddy, g->Cout) || lddx < g->Cin) return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(g), (hipStream_t)stream);
-    return conv_dgrad_impl<F32>(g, dy, lddy, wt, nullptr, addend, ldadd, dx, lddx, (hipStream_t)stream);
+    return run_conv<F32>({g, DGRAD, dy, lddy, wt, nullptr, nullptr, addend, ldadd, dx, lddx, nullptr},
+                         conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(g), (hipStream_t)stream);
 }
 
 size_t unetrir_conv2d_wgrad_ws_bytes(const unetrir_conv_geom* g) { return geom_ok(g) ? wgrad_ws_bytes(g) : 0; }
@@ -474,8 +534,8 @@ int unetrir_conv2d_transpose_fwd_f32(const unetrir_conv_geom* g, const float* x,
     if (!geom_ok(g) || !x || !wt || !y || (g->Cin & 3) || !ld_ok(ldx, g->Cin) || ldy < g->Cout)
         return UNETRIR_EINVAL;
     const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_FWD), conv_flops(&c), (hipStream_t)stream);
-    return conv_dgrad_impl<F32>(&c, x, ldx, wt, bias, nullptr, 0, y, ldy, (hipStream_t)stream);
+    return run_conv<F32>({&c, TFWD, x, ldx, wt, nullptr, bias, nullptr, 0, y, ldy, nullptr}, conv_family(g, UNETRIR_FAM_CONV_FWD),
+                         conv_flops(&c), (hipStream_t)stream);
 }
 
 int unetrir_conv2d_transpose_dgrad_f32(const unetrir_conv_geom* g, const float* dy, int lddy, const float* w,
@@ -483,8 +543,8 @@ int unetrir_conv2d_transpose_dgrad_f32(const unetrir_conv_geom* g, const float* 
     if (!geom_ok(g) || !dy || !w || !dx || (g->Cout & 3) || !ld_ok(lddy, g->Cout) || lddx < g->Cin)
         return UNETRIR_EINVAL;
     const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(&c), (hipStream_t)stream);
-    return conv_fwd_impl<F32>(&c, dy, lddy, w, nullptr, addend, ldadd, dx, lddx, (hipStream_t)stream);
+    return run_conv<F32>({&c, FWD, dy, lddy, w, nullptr, nullptr, addend, ldadd, dx, lddx, nullptr},
+                         conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(&c), (hipStream_t)stream);
 }
 
 size_t unetrir_conv2d_transpose_wgrad_ws_bytes(const unetrir_conv_geom* g) {
@@ -506,18 +566,11 @@ int unetrir_conv2d_transpose_wgrad_f32(const unetrir_conv_geom* g, const float* 
 }
 
 /* ---- bf16-storage variants: x / dy / y / dx and the weight work copies are bf16, bias fp32, weight gradients fp32 ---- */
-int unetrir_conv3x3_kernel_id_bf16(const unetrir_conv_geom* g, int dgrad, int ld_in);
-// profiling only: launches the dominant kernel of the step (conv3x3p) serves are also counted under UNETRIR_FAM_DOMINANT
-static inline int dominant_tag(const unetrir_conv_geom* g, int dgrad, int ld_in) {
-    if (!g_prof_on || !geom_ok(g) || g->k != 3 || g->stride != 1) return -1;
-    return unetrir_conv3x3_kernel_id_bf16(g, dgrad, ld_in) == UNETRIR_K3_CONV3X3P ? UNETRIR_FAM_DOMINANT : -1;
-}
 int unetrir_conv2d_fwd_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* w, const float* bias,
                             const unetrir_bf16* addend, int ldadd, unetrir_bf16* y, int ldy, unetrir_stream_t stream) {
     if (!geom_ok(g) || !x || !w || !y || (g->Cin & 7) || !ldh_ok(ldx, g->Cin) || ldy < g->Cout) return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_FWD), conv_flops(g), (hipStream_t)stream, dominant_tag(g, 0, ldx));
-    return conv_fwd_impl<BF16>(g, (const __bf16*)x, ldx, (const __bf16*)w, bias, (const __bf16*)addend, ldadd, (__bf16*)y, ldy,
-                               (hipStream_t)stream);
+    return run_conv<BF16>({g, FWD, x, ldx, w, nullptr, bias, addend, ldadd, y, ldy, nullptr}, conv_family(g, UNETRIR_FAM_CONV_FWD),
+                          conv_flops(g), (hipStream_t)stream, true);
 }
 
 size_t unetrir_conv3x3s2_packed_elems(int N, int C) {
@@ -529,111 +582,66 @@ int unetrir_conv2d_fwd_packed_bf16(const unetrir_conv_geom* g, const unetrir_bf1
                                    const unetrir_bf16* w_packed, const float* bias, const unetrir_bf16* addend, int ldadd,
                                    unetrir_bf16* y, int ldy, unetrir_stream_t stream) {
     if (!geom_ok(g) || !x || !w || !y || (g->Cin & 7) || !ldh_ok(ldx, g->Cin) || ldy < g->Cout) return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_FWD), conv_flops(g), (hipStream_t)stream);
-    return conv_fwd_impl<BF16>(g, (const __bf16*)x, ldx, (const __bf16*)w, bias, (const __bf16*)addend, ldadd, (__bf16*)y, ldy,
-                               (hipStream_t)stream, nullptr, w_packed);
+    return run_conv<BF16>({g, FWD, x, ldx, w, w_packed, bias, addend, ldadd, y, ldy, nullptr}, conv_family(g, UNETRIR_FAM_CONV_FWD),
+                          conv_flops(g), (hipStream_t)stream);
 }
 
 int unetrir_conv2d_dgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* wt,
                               const unetrir_bf16* addend, int ldadd, unetrir_bf16* dx, int lddx, unetrir_stream_t stream) {
     if (!geom_ok(g) || !dy || !wt || !dx || (g->Cout & 7) || !ldh_ok(lddy, g->Cout) || lddx < g->Cin) return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(g), (hipStream_t)stream, dominant_tag(g, 1, lddy));
-    return conv_dgrad_impl<BF16>(g, (const __bf16*)dy, lddy, (const __bf16*)wt, nullptr, (const __bf16*)addend, ldadd, (__bf16*)dx,
-                                 lddx, (hipStream_t)stream);
+    return run_conv<BF16>({g, DGRAD, dy, lddy, wt, nullptr, nullptr, addend, ldadd, dx, lddx, nullptr},
+                          conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(g), (hipStream_t)stream, true);
 }
 
-/* Fused column statistics: the 3x3 stride-1 kernels conv3x3g / conv3x3r<4,1> can emit, per 16 x 32 pixel tile, the
- * per-channel (sum, sum of squares) of the bf16 output they store.  rows == 0: the kernel serving this layer cannot. */
-static long long colstat_rows(const unetrir_conv_geom* g, int dgrad, int ld_in) {
-    if (!geom_ok(g)) return 0;
-    const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
-    // rows the tap-table kernel writes: one per 128-pixel tile of its iteration grid (forward: the output grid; data gradient at
-    // stride 1: the input grid).  Strided data gradients have no fused statistics through this entry point.
-    const long long igemm_rows = dgrad ? (g->stride == 1 ? igemm_colstat_rows((long long)g->B * g->H * g->W, g->Cin) : 0)
-                                       : igemm_colstat_rows((long long)g->B * sy.out * sx.out, g->Cout);
-    if (g->k == 1) {          // the register-streaming 1x1 kernel: one row per persistent workgroup
-        const PwArgs pw = dgrad ? pw_dgrad_args(g, nullptr, ld_in, nullptr, nullptr, nullptr, 0, nullptr, g->Cin, nullptr)
-                                : pw_fwd_args(g, nullptr, ld_in, nullptr, nullptr, nullptr, 0, nullptr, g->Cout, nullptr);
-        if (pw1x1_applies(pw)) return pw1x1_colstat_rows(pw);
-    }
-    if (g->k != 3 || g->stride != 1) return (g->k == 3 && g->stride == 2 && !dgrad) ? 0 : igemm_rows;    // 3x3 stride 2 forward: conv3x3d (none)
-    Conv3Args c{};
-    c.B = g->B; c.H = g->H; c.W = g->W; c.ldi = ld_in;
-    c.C = dgrad ? g->Cout : g->Cin; c.N = dgrad ? g->Cin : g->Cout; c.flip = dgrad ? 1 : 0;
-    if (conv3x3g_pair_applies(c)) return conv3x3g_colstat_rows(c);          // two images per tile row
-    if (!use_conv3x3(g->k, g->stride, g->H, g->W)) return igemm_rows;
-    if (!conv3x3_has_colstat(c)) return 0;
-    if (conv3x3s_applies(c)) return conv3x3s_colstat_rows(c);               // one row per persistent workgroup
-    if (unetrir_cfg().conv3x3g && conv3x3p_applies(c)) return conv3x3p_colstat_rows(c);    // one row per group of N / 128 workgroups
-    return (long long)g->B * ((g->H + 15) / 16) * ((g->W + 31) / 32);
+/* Fused column statistics and the kernel serving a 3x3 stride-1 layer: fields of the plan (plan_conv) of the launch as the query
+ * describes it.  rows == 0: the kernel serving this layer cannot emit statistics. */
+long long unetrir_conv2d_colstat_rows_bf16(const unetrir_conv_geom* g, int dgrad, int ld_in) {
+    return geom_ok(g) ? plan_query(g, dgrad ? DGRAD : FWD, ld_in, true).colstat_rows : 0;
 }
-// Conv2DTranspose forward (g: the transposed layer's own geometry).  Stride 1: the data-gradient form of the adjoint conv on
-// the same grid.  Stride 2: the four output-parity classes of the tap-table path, each with its own row range; the patch-staged
-// 3x3 kernels of that path (upconv3x3*) have no fused statistics, so a 3x3 stride-2 layer on even sizes reports 0 unless the
-// caller forces the tap-table path by asking for statistics (the launch then takes it).
-static long long colstat_rows_transpose(const unetrir_conv_geom* g, int ld_in) {
+
+long long unetrir_conv2d_transpose_colstat_rows_bf16(const unetrir_conv_geom* g, int ld_in) {
     if (!geom_ok(g)) return 0;
-    if (g->stride == 1) {
-        unetrir_conv_geom c = *g;
-        c.Cin = g->Cout; c.Cout = g->Cin;
-        return colstat_rows(&c, 1, ld_in);
-    }
-    if (g->k == 3) return 0;
-    if (g->k == 1) {
-        const unetrir_conv_geom c = adjoint_geom(g);
-        const PwArgs pw = pw_dgrad_args(&c, nullptr, ld_in, nullptr, nullptr, nullptr, 0, nullptr, g->Cout, nullptr);
-        if (pw1x1_applies(pw)) return pw1x1_colstat_rows(pw);
-    }
-    return 4 * igemm_colstat_rows((long long)g->B * g->H * g->W, g->Cout, 4);
+    const unetrir_conv_geom c = adjoint_geom(g);
+    return plan_query(&c, TFWD, ld_in, true).colstat_rows;
 }
-long long unetrir_conv2d_colstat_rows_bf16(const unetrir_conv_geom* g, int dgrad, int ld_in) { return colstat_rows(g, dgrad, ld_in); }
 
 int unetrir_conv3x3_kernel_id_bf16(const unetrir_conv_geom* g, int dgrad, int ld_in) {
     if (!geom_ok(g) || g->k != 3 || g->stride != 1) return UNETRIR_K3_TAPTABLE;
-    Conv3Args c{};
-    c.B = g->B; c.H = g->H; c.W = g->W; c.ldi = ld_in;
-    c.C = dgrad ? g->Cout : g->Cin; c.N = dgrad ? g->Cin : g->Cout; c.flip = dgrad ? 1 : 0;
-    const bool dma = unetrir_cfg().conv3x3g != 0;
-    if (conv3x3g_pair_applies(c) && dma) return UNETRIR_K3_CONV3X3G_PAIR;
-    if (!use_conv3x3(g->k, g->stride, g->H, g->W)) return UNETRIR_K3_TAPTABLE;
-    if (unetrir_cfg().stem && stem3x3_applies(c)) return UNETRIR_K3_STEM;
-    if (dma && conv3x3p_applies(c)) return UNETRIR_K3_CONV3X3P;
-    if (dma && conv3x3g_applies(c)) return UNETRIR_K3_CONV3X3G;
-    if (conv3x3s_applies(c)) return UNETRIR_K3_CONV3X3S;
-    if (conv3x3h_applies(c)) return UNETRIR_K3_CONV3X3H;
-    return UNETRIR_K3_CONV3X3R;
+    switch (plan_query(g, dgrad ? DGRAD : FWD, ld_in, false).kernel) {
+        case Kern::PATCH: return UNETRIR_K3_PATCH;
+        case Kern::STEM: return UNETRIR_K3_STEM;
+        case Kern::CONV3X3G_PAIR: return UNETRIR_K3_CONV3X3G_PAIR;
+        case Kern::CONV3X3P: return UNETRIR_K3_CONV3X3P;
+        case Kern::CONV3X3G: return UNETRIR_K3_CONV3X3G;
+        case Kern::CONV3X3S: return UNETRIR_K3_CONV3X3S;
+        case Kern::CONV3X3H: return UNETRIR_K3_CONV3X3H;
+        case Kern::CONV3X3R: return UNETRIR_K3_CONV3X3R;
+        default: return UNETRIR_K3_TAPTABLE;
+    }
 }
 
 int unetrir_conv2d_fwd_colstat_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* w, const float* bias,
                                     const unetrir_bf16* addend, int ldadd, unetrir_bf16* y, int ldy, float* colstat,
                                     unetrir_stream_t stream) {
-    if (!geom_ok(g) || !x || !w || !y || !colstat || (g->Cin & 7) || !ldh_ok(ldx, g->Cin) || ldy < g->Cout || colstat_rows(g, 0, ldx) == 0)
-        return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_FWD), conv_flops(g), (hipStream_t)stream, dominant_tag(g, 0, ldx));
-    return conv_fwd_impl<BF16>(g, (const __bf16*)x, ldx, (const __bf16*)w, bias, (const __bf16*)addend, ldadd, (__bf16*)y, ldy,
-                               (hipStream_t)stream, colstat);
+    if (!geom_ok(g) || !x || !w || !y || !colstat || (g->Cin & 7) || !ldh_ok(ldx, g->Cin) || ldy < g->Cout) return UNETRIR_EINVAL;
+    return run_conv<BF16>({g, FWD, x, ldx, w, nullptr, bias, addend, ldadd, y, ldy, colstat}, conv_family(g, UNETRIR_FAM_CONV_FWD),
+                          conv_flops(g), (hipStream_t)stream, true);
 }
 
 int unetrir_conv2d_dgrad_colstat_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* wt,
                                       const unetrir_bf16* addend, int ldadd, unetrir_bf16* dx, int lddx, float* colstat,
                                       unetrir_stream_t stream) {
-    if (!geom_ok(g) || !dy || !wt || !dx || !colstat || (g->Cout & 7) || !ldh_ok(lddy, g->Cout) || lddx < g->Cin ||
-        colstat_rows(g, 1, lddy) == 0)
-        return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(g), (hipStream_t)stream, dominant_tag(g, 1, lddy));
-    return conv_dgrad_impl<BF16>(g, (const __bf16*)dy, lddy, (const __bf16*)wt, nullptr, (const __bf16*)addend, ldadd, (__bf16*)dx,
-                                 lddx, (hipStream_t)stream, colstat);
+    if (!geom_ok(g) || !dy || !wt || !dx || !colstat || (g->Cout & 7) || !ldh_ok(lddy, g->Cout) || lddx < g->Cin) return UNETRIR_EINVAL;
+    return run_conv<BF16>({g, DGRAD, dy, lddy, wt, nullptr, nullptr, addend, ldadd, dx, lddx, colstat},
+                          conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(g), (hipStream_t)stream, true);
 }
-
-long long unetrir_conv2d_transpose_colstat_rows_bf16(const unetrir_conv_geom* g, int ld_in) { return colstat_rows_transpose(g, ld_in); }
 
 int unetrir_conv2d_transpose_fwd_colstat_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* wt,
                                               const float* bias, unetrir_bf16* y, int ldy, float* colstat, unetrir_stream_t stream) {
-    if (!geom_ok(g) || !x || !wt || !y || !colstat || (g->Cin & 7) || !ldh_ok(ldx, g->Cin) || ldy < g->Cout || colstat_rows_transpose(g, ldx) == 0)
-        return UNETRIR_EINVAL;
+    if (!geom_ok(g) || !x || !wt || !y || !colstat || (g->Cin & 7) || !ldh_ok(ldx, g->Cin) || ldy < g->Cout) return UNETRIR_EINVAL;
     const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_FWD), conv_flops(&c), (hipStream_t)stream);
-    return conv_dgrad_impl<BF16>(&c, (const __bf16*)x, ldx, (const __bf16*)wt, bias, nullptr, 0, (__bf16*)y, ldy, (hipStream_t)stream, colstat);
+    return run_conv<BF16>({&c, TFWD, x, ldx, wt, nullptr, bias, nullptr, 0, y, ldy, colstat}, conv_family(g, UNETRIR_FAM_CONV_FWD),
+                          conv_flops(&c), (hipStream_t)stream);
 }
 
 int unetrir_conv2d_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy,
@@ -673,8 +681,8 @@ int unetrir_conv2d_transpose_fwd_bf16(const unetrir_conv_geom* g, const unetrir_
     if (!geom_ok(g) || !x || !wt || !y || (g->Cin & 7) || !ldh_ok(ldx, g->Cin) || ldy < g->Cout)
         return UNETRIR_EINVAL;
     const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_FWD), conv_flops(&c), (hipStream_t)stream);
-    return conv_dgrad_impl<BF16>(&c, (const __bf16*)x, ldx, (const __bf16*)wt, bias, nullptr, 0, (__bf16*)y, ldy, (hipStream_t)stream);
+    return run_conv<BF16>({&c, TFWD, x, ldx, wt, nullptr, bias, nullptr, 0, y, ldy, nullptr}, conv_family(g, UNETRIR_FAM_CONV_FWD),
+                          conv_flops(&c), (hipStream_t)stream);
 }
 
 int unetrir_conv2d_transpose_dgrad_packed_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* w,
@@ -683,9 +691,8 @@ int unetrir_conv2d_transpose_dgrad_packed_bf16(const unetrir_conv_geom* g, const
     if (!geom_ok(g) || !dy || !w || !dx || (g->Cout & 7) || !ldh_ok(lddy, g->Cout) || lddx < g->Cin)
         return UNETRIR_EINVAL;
     const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(&c), (hipStream_t)stream);
-    return conv_fwd_impl<BF16>(&c, (const __bf16*)dy, lddy, (const __bf16*)w, nullptr, (const __bf16*)addend, ldadd, (__bf16*)dx, lddx,
-                               (hipStream_t)stream, nullptr, w_packed);
+    return run_conv<BF16>({&c, FWD, dy, lddy, w, w_packed, nullptr, addend, ldadd, dx, lddx, nullptr},
+                          conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(&c), (hipStream_t)stream);
 }
 
 int unetrir_conv2d_transpose_dgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* w,
@@ -694,9 +701,8 @@ int unetrir_conv2d_transpose_dgrad_bf16(const unetrir_conv_geom* g, const unetri
     if (!geom_ok(g) || !dy || !w || !dx || (g->Cout & 7) || !ldh_ok(lddy, g->Cout) || lddx < g->Cin)
         return UNETRIR_EINVAL;
     const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(&c), (hipStream_t)stream);
-    return conv_fwd_impl<BF16>(&c, (const __bf16*)dy, lddy, (const __bf16*)w, nullptr, (const __bf16*)addend, ldadd, (__bf16*)dx, lddx,
-                               (hipStream_t)stream);
+    return run_conv<BF16>({&c, FWD, dy, lddy, w, nullptr, nullptr, addend, ldadd, dx, lddx, nullptr},
+                          conv_family(g, UNETRIR_FAM_CONV_DGRAD), conv_flops(&c), (hipStream_t)stream);
 }
 
 int unetrir_conv2d_transpose_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy,

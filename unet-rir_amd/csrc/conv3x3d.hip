@@ -358,7 +358,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
 
 bool conv3x3d_applies(const Conv3Args& a) {
     const size_t img_bytes = (((size_t)a.H * a.W - 1) * a.ldi + a.C) * 2, w_bytes = (size_t)((a.N + 127) / 128) * 128 * 9 * a.C * 2;
-    return unetrir_cfg().conv3x3d && !a.colstat && (a.H & 1) == 0 && (a.W & 1) == 0 && (a.H / 2) % DTR == 0 && (a.W / 2) % DTC == 0 &&
+    return (a.H & 1) == 0 && (a.W & 1) == 0 && (a.H / 2) % DTR == 0 && (a.W / 2) % DTC == 0 &&
            a.C >= 32 && a.C % 16 == 0 && a.N >= 32 && a.N % 32 == 0 && a.N <= DMAXN && a.ldi >= a.C && (a.ldi & 7) == 0 &&
            (a.ldo & 7) == 0 && (!a.addend || (a.ldadd & 7) == 0) && img_bytes < 0x70000000u && w_bytes < 0x70000000u;
 }

@@ -307,10 +307,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3h_bf16_kernel(const Conv3Args a
 }
 
 bool conv3x3h_applies(const Conv3Args& a) {
-    const bool on = unetrir_cfg().conv3x3h != 0;
     const size_t img_bytes = (((size_t)a.H * a.W - 1) * a.ldi + a.C) * 2, w_bytes = (size_t)a.N * 9 * a.C * 2;
-    return on && a.C % 32 == 0 && a.N <= 64 && !(a.flip & 2) && img_bytes < 0x70000000u && w_bytes < 0x70000000u;
+    return a.C % 32 == 0 && a.N <= 64 && !(a.flip & 2) && img_bytes < 0x70000000u && w_bytes < 0x70000000u;
 }
+
+long long conv3x3h_colstat_rows(const Conv3Args& a) { return (long long)a.B * ((a.H + HTR - 1) / HTR) * ((a.W + 31) / 32); }
 
 int launch_conv3x3h_bf16(const Conv3Args& a, hipStream_t s) {
     const long long tiles = (long long)a.B * ((a.H + HTR - 1) / HTR) * ((a.W + 31) / 32);

@@ -246,6 +246,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3r_bf16_kernel(const Conv3Args a
     }
 }
 
+// the N > 64 tile (<2, 2>) has no statistics path
+long long conv3x3r_colstat_rows(const Conv3Args& a) { return a.N > 64 ? 0 : (long long)a.B * ((a.H + 15) / 16) * ((a.W + 31) / 32); }
+
 int launch_conv3x3r_bf16(const Conv3Args& a, hipStream_t s) {
     const long long tx = (a.W + 31) / 32;
     if (a.N > 64) {

@@ -488,7 +488,7 @@ inline SPlan splan(const Conv3Args& a) {
 
 bool conv3x3s_applies(const Conv3Args& a) {
     const size_t img_bytes = (((size_t)a.H * a.W - 1) * a.ldi + a.C) * 2;
-    return unetrir_cfg().conv3x3s && ((a.C == 64 && a.N == 64) || (a.C == 32 && a.N == 32)) && !(a.flip & 2) && a.ldi >= a.C && (a.ldi & 7) == 0 &&
+    return ((a.C == 64 && a.N == 64) || (a.C == 32 && a.N == 32)) && !(a.flip & 2) && a.ldi >= a.C && (a.ldi & 7) == 0 &&
            img_bytes < 0x70000000u;
 }
 

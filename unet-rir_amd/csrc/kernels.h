@@ -134,10 +134,14 @@ struct Conv3Args {
     int B, H, W, C, N;
     int flip;                 // 0: forward (weight tap t at offset t); 1: data gradient (weight tap 8-t at offset t)
     const void* wpk;          // nullable; conv3x3d only: the packed copy of w (unetrir_conv3x3s2_packed_elems)
-    float* colstat;           // nullable; conv3x3g / conv3x3r<4,1> only: [pixel tile][N][2] per-channel (sum, sum of squares) of the
-                              // stored output, one row per 16 x 32 pixel tile (row = (img * tiles_y + ty) * tiles_x + tx)
+    float* colstat;           // nullable; the kernels with a *_colstat_rows function only: [row][N][2] per-channel (sum, sum of squares)
+                              // of the stored output, that many rows (conv3x3g / h / r: one per 16 x 32 pixel tile, row =
+                              // (img * tiles_y + ty) * tiles_x + tx)
 };
-int launch_conv3x3(const Conv3Args& a, int bf16, hipStream_t s);
+// Which of the kernels below serves a launch - and that includes the kernel-selection switches they belong to - is decided in ONE
+// place, plan_conv (api.hip).  The *_applies predicates are shape rules only.
+int launch_conv3x3(const Conv3Args& a, int bf16, hipStream_t s);     // the generic patch-staged kernel (conv3x3.hip); no statistics
+long long conv3x3r_colstat_rows(const Conv3Args& a);
 int launch_conv3x3r_bf16(const Conv3Args& a, hipStream_t s);
 bool head_mfma_applies(int W, int C);
 int launch_head_fwd_mfma(const void* x, int ldx, int B, int H, int W, int C, const float* w, const float* bias, float* y, int ldy, hipStream_t s);
@@ -150,11 +154,11 @@ bool upconv3x3q_applies(const Conv3Args& a);        // upconv3x3g's layers with 
 int launch_upconv3x3q_bf16(const Conv3Args& a, hipStream_t s);
 int launch_upconv3x3g_bf16(const Conv3Args& a, hipStream_t s);
 bool conv3x3g_applies(const Conv3Args& a);
-bool conv3x3g_pair_applies(const Conv3Args& a);     // images <= 16 pixels wide: two images per tile
-long long conv3x3g_colstat_rows(const Conv3Args& a);
+bool conv3x3g_pair_applies(const Conv3Args& a, bool any_size);     // images <= 16 pixels wide: two images per tile
+long long conv3x3g_colstat_rows(const Conv3Args& a, bool pair);
+int launch_conv3x3g_bf16(const Conv3Args& a, bool pair, hipStream_t s);
 bool stem3x3_applies(const Conv3Args& a);
 int launch_stem3x3_bf16(const Conv3Args& a, hipStream_t s);
-bool conv3x3_has_colstat(const Conv3Args& a);
 bool conv3x3s_applies(const Conv3Args& a);          // 64 -> 64 channels: strip kernel with the whole 3x3 kernel resident in LDS
 long long conv3x3s_colstat_rows(const Conv3Args& a);
 int launch_conv3x3s_bf16(const Conv3Args& a, hipStream_t s);
@@ -168,8 +172,8 @@ int launch_conv3x3p_bf16(const Conv3Args& a, hipStream_t s);
 bool conv3x3d_applies(const Conv3Args& a);          // 3x3 stride 2, forward form (H, W = input size): persistent LDS-DMA kernel
 int launch_conv3x3d_bf16(const Conv3Args& a, hipStream_t s);
 bool conv3x3h_applies(const Conv3Args& a);
+long long conv3x3h_colstat_rows(const Conv3Args& a);
 int launch_conv3x3h_bf16(const Conv3Args& a, hipStream_t s);
-int launch_conv3x3g_bf16(const Conv3Args& a, hipStream_t s);
 int launch_dense_fwd(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int B, int K, int N,
                      void* ws, size_t ws_bytes, hipStream_t s);
 size_t dense_fwd_ws_bytes(int B, int K, int N);
@@ -178,7 +182,7 @@ bool dense_dgrad_applies(int B, int K, int N);
 size_t dense_dgrad_ws_bytes(int B, int K, int N);
 int launch_dense_dgrad(const float* dy, int lddy, const float* w, float* dx, int lddx, int B, int K, int N, void* ws, size_t ws_bytes,
                        hipStream_t s);
-int launch_upconv3x3(const Conv3Args& a, int bf16, hipStream_t s);
+int launch_upconv3x3(const Conv3Args& a, int bf16, hipStream_t s);   // the generic strided data-gradient kernel (upconv3x3.hip)
 
 // 1x1 convolutions (pw1x1.hip): out[opix(p)][n] = sum_c in[ipix(p)][c] w[n][c] + bias[n] (+ addend) over the iteration grid
 // B x PH x PW; ipix = (b, py SI, px SI) of the IH x IW input grid, opix = (b, py SO, px SO) of the OH x OW output grid; fill
@@ -191,7 +195,7 @@ struct PwArgs {
     __bf16* out; int ldo; int OH, OW;
     int B, PH, PW, SI, SO, fill;
     int C, N;
-    float* colstat;                  // nullable: [pw1x1_colstat_rows][N][2]; requires addend == nullptr
+    float* colstat;                  // nullable: [pw1x1_colstat_rows][N][2]; not together with an addend
 };
 bool pw1x1_applies(const PwArgs& a);
 long long pw1x1_colstat_rows(const PwArgs& a);

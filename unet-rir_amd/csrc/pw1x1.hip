@@ -259,7 +259,6 @@ int launch_kb(const PwArgs& a, int nb, unsigned grid, hipStream_t s) {
 }  // namespace
 
 bool pw1x1_applies(const PwArgs& a) {
-    if (!unetrir_cfg().pw1x1) return false;
     const long long M = (long long)a.B * a.PH * a.PW;
     if (M <= 0 || M >= (1ll << 31) || (long long)a.B * a.OH * a.OW >= (1ll << 31) || (long long)a.B * a.IH * a.IW >= (1ll << 31)) return false;
     if (a.N % 32 != 0 || a.N > 1024) return false;
@@ -270,7 +269,6 @@ bool pw1x1_applies(const PwArgs& a) {
     if (a.SI != 1 && a.SI != 2) return false;
     if (a.SO != 1 && a.SO != 2) return false;
     if (a.fill && a.SO != 2) return false;
-    if (a.colstat && a.addend) return false;
     return true;
 }
 

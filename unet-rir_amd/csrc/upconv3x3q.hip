@@ -389,7 +389,7 @@ inline long long q_pixel_tiles(const Conv3Args& a) { return (long long)a.B * ((a
 bool upconv3x3q_applies(const Conv3Args& a) {
     const int ntN = (a.N + QBN - 1) / QBN;
     const size_t out_bytes = (((size_t)4 * a.H * a.W - 1) * a.ldo + a.N) * 2;
-    return unetrir_cfg().upconv3x3q && upconv3x3g_applies(a) && a.C >= 96 && (a.N & 7) == 0 && (a.ldo & 7) == 0 &&
+    return upconv3x3g_applies(a) && a.C >= 96 && (a.N & 7) == 0 && (a.ldo & 7) == 0 &&
            (!a.addend || (a.ldadd & 7) == 0) && (ntN == 1 || ntN == 2 || ntN == 4 || ntN == 8) && q_pixel_tiles(a) * ntN >= 1024 &&
            out_bytes < 0x70000000u;
 }

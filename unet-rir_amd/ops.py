@@ -119,7 +119,7 @@ def conv2d_colstat_rows(g, dgrad, x: Act):
     return int(_lib.lib().unetrir_conv2d_colstat_rows_bf16(C.byref(g), int(bool(dgrad)), x.ld))
 
 
-K3_NAMES = ("tap-table", "conv3x3r", "conv3x3g", "conv3x3g pair", "conv3x3h", "conv3x3s", "conv3x3p", "stem")
+K3_NAMES = ("tap-table", "conv3x3r", "conv3x3g", "conv3x3g pair", "conv3x3h", "conv3x3s", "conv3x3p", "stem", "patch")
 
 
 def conv3x3_kernel(g, dgrad, x: Act):
