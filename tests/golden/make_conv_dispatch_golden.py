@@ -1,6 +1,7 @@
 """Generates tests/golden/conv_dispatch.json: which bf16 convolution kernel the library picks for every convolution layer of
 the benchmarked workloads, and how many rows of fused column statistics it reports, under the default kernel-selection switches,
-under each dispatch switch set to 0 on its own, and with conv3x3g_pair = 2.
+under each dispatch switch set to 0 on its own, and with conv3x3g_pair = 2.  Also tests/golden/wgrad_ws.json: the workspace the
+library asks for every weight-gradient layer of the same workloads.
 
 The layers are collected from one train step of each workload on the simulated runtime (tests/sim_runtime.py) with the
 convolution launches recorded instead of computed: the geometry of every Conv2D / Conv2DTranspose call and the pixel stride of
@@ -9,6 +10,9 @@ of the library - no GPU needed:
     k3_fwd / k3_dgrad      unetrir_conv3x3_kernel_id_bf16 (ops.K3_NAMES), forward and data gradient
     rows_fwd / rows_dgrad  unetrir_conv2d_colstat_rows_bf16, forward and data gradient
     rows_t                 unetrir_conv2d_transpose_colstat_rows_bf16
+The weight-gradient calls are recorded with both pixel strides (x, dy) and whether the layer is a Conv2DTranspose; every layer's
+geometry is asked of
+    ws / ws_t              unetrir_conv2d_wgrad_ws_bytes / unetrir_conv2d_transpose_wgrad_ws_bytes
 
     python tests/golden/make_conv_dispatch_golden.py [libunetrir.so to ask instead of the in-tree build]
 """
@@ -26,6 +30,7 @@ import unet_rir_amd as U  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "conv_dispatch.json")
+WS_OUT = os.path.join(HERE, "wgrad_ws.json")
 
 # the switches the dispatch of forward / data-gradient / Conv2DTranspose-forward launches reads
 SWITCHES = ("conv3x3", "conv3x3g", "conv3x3g_pair", "conv3x3h", "conv3x3s", "conv3x3r", "stem", "conv3x3p", "conv3x3d",
@@ -43,21 +48,29 @@ WORKLOADS = {
 }
 CONV_CALLS = ("conv2d_fwd", "conv2d_fwd_colstat", "conv2d_dgrad", "conv2d_dgrad_colstat", "conv2d_transpose_fwd",
               "conv2d_transpose_fwd_colstat", "conv2d_transpose_dgrad")
+WGRAD_CALLS = ("conv2d_wgrad", "conv2d_transpose_wgrad")
 # simulated operators whose answer the engines use; every other one is skipped (only the calls are of interest, not the values)
 KEEP = ("_elems", "_supported", "_rows", "_ws_bytes", "_table")
 
 
 def collect_layers():
-    """{(B, H, W, Cin, Cout, k, stride, ld)} over every convolution call of one train step of each workload."""
+    """{(B, H, W, Cin, Cout, k, stride, ld)} over every convolution call of one train step of each workload, and
+    {(B, H, W, Cin, Cout, k, stride, ldx, lddy, transposed)} over every weight-gradient call."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import cpu_ops
     from oracle import torch_ref as R
     from sim_runtime import SimRuntime
-    seen = set()
+    seen, wseen = set(), set()
 
     def recorder(name):
         def rec(g, x, *a, **k):
             seen.add((g.B, g.H, g.W, g.Cin, g.Cout, g.k, g.stride, x.ld))
+        rec.__name__ = name
+        return rec
+
+    def wgrad_recorder(name):
+        def rec(g, x, dy, *a, **k):
+            wseen.add((g.B, g.H, g.W, g.Cin, g.Cout, g.k, g.stride, x.ld, dy.ld, int(name == "conv2d_transpose_wgrad")))
         rec.__name__ = name
         return rec
 
@@ -68,7 +81,8 @@ def collect_layers():
             impl = cpu_ops.install(mp, rt)
             for c in dir(impl):
                 if not c.startswith("_") and c != "rt" and not c.endswith(KEEP):
-                    mp.setattr(U.ops, c, recorder(c) if c in CONV_CALLS else (lambda *a, **k: None))
+                    mp.setattr(U.ops, c, recorder(c) if c in CONV_CALLS else wgrad_recorder(c) if c in WGRAD_CALLS else
+                               (lambda *a, **k: None))
             model = make(rt)
             tr = U.Trainer(model, lr=1e-3, dropout=False) if name != "resae" else U.Trainer(model, lr=1e-3)
             eng = getattr(model, "engine", model)
@@ -78,8 +92,8 @@ def collect_layers():
             del tr, model, eng
         finally:
             mp.undo()
-        print(f"{name}: {len(seen)} layers so far", file=sys.stderr)
-    return sorted(seen)
+        print(f"{name}: {len(seen)} layers, {len(wseen)} weight-gradient layers so far", file=sys.stderr)
+    return sorted(seen), sorted(wseen)
 
 
 def query(layers):
@@ -105,10 +119,22 @@ def query(layers):
     return out
 
 
+def query_ws(wlayers):
+    """[ws, ws_t] per weight-gradient layer: the two workspace queries on its geometry (they read no switch and no pixel stride)."""
+    import ctypes as C
+    from unet_rir_amd import _lib
+    L = _lib.lib()
+    out = []
+    for (B, H, W, Cin, Cout, k, s, ldx, lddy, tr) in wlayers:
+        g = _lib.ConvGeom(B, H, W, Cin, Cout, k, s)
+        out.append([int(L.unetrir_conv2d_wgrad_ws_bytes(C.byref(g))), int(L.unetrir_conv2d_transpose_wgrad_ws_bytes(C.byref(g)))])
+    return out
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         U._lib.use_library(os.path.abspath(sys.argv[1]))
-    layers = collect_layers()
+    layers, wlayers = collect_layers()
     doc = {"fields": ["k3_fwd", "k3_dgrad", "rows_fwd", "rows_dgrad", "rows_t"],
            "layer_fields": ["B", "H", "W", "Cin", "Cout", "k", "stride", "ld"],
            "layers": [list(x) for x in layers], "settings": query(layers)}
@@ -116,3 +142,9 @@ if __name__ == "__main__":
         json.dump(doc, f, separators=(",", ":"))
         f.write("\n")
     print(f"wrote {OUT}: {len(layers)} layers x {len(SETTINGS)} settings", file=sys.stderr)
+    doc = {"fields": ["ws", "ws_t"], "layer_fields": ["B", "H", "W", "Cin", "Cout", "k", "stride", "ldx", "lddy", "transposed"],
+           "layers": [list(x) for x in wlayers], "ws": query_ws(wlayers)}
+    with open(WS_OUT, "w") as f:
+        json.dump(doc, f, separators=(",", ":"))
+        f.write("\n")
+    print(f"wrote {WS_OUT}: {len(wlayers)} weight-gradient layers", file=sys.stderr)

@@ -1,7 +1,9 @@
 """The kernel plan of the bf16 convolutions (plan_conv, api.hip) gives the answers the library gave before it existed: which kernel
 serves each convolution layer of the benchmarked workloads and how many rows of fused column statistics it reports, under the
 default switches, under each dispatch switch set to 0 on its own and with conv3x3g_pair = 2 (tests/golden/conv_dispatch.json,
-recorded by tests/golden/make_conv_dispatch_golden.py).  The library loads without a GPU; no compute calls here."""
+recorded by tests/golden/make_conv_dispatch_golden.py).  The weight-gradient workspace query, computed from the weight-gradient
+plans (plan_wgrad), keeps the values the library gave before they existed (tests/golden/wgrad_ws.json, same generator).  The
+library loads without a GPU; no compute calls here."""
 import importlib.util
 import json
 import os
@@ -47,3 +49,15 @@ def test_plan_reproduces_the_recorded_dispatch():
     # the recording covers every kind of kernel the queries can name, the paired 16-wide levels included
     seen = {k for recs in doc["settings"].values() for r in recs for k in r[:2]}
     assert {"tap-table", "conv3x3r", "conv3x3g", "conv3x3g pair", "conv3x3h", "conv3x3s", "conv3x3p", "stem"} <= seen
+
+
+def test_wgrad_workspace_query_keeps_the_recorded_values():
+    doc = json.load(open(os.path.join(GOLDEN, "wgrad_ws.json")))
+    layers = [tuple(x) for x in doc["layers"]]
+    got = _generator().query_ws(layers)
+    bad = [(layer, want, now) for layer, want, now in zip(layers, doc["ws"], got) if now != want]
+    assert not bad, bad[:10]
+    # the recording covers stride-1 and stride-2 3x3 layers, the 1x1 layers of the residual graphs and transposed layers
+    kinds = {(k, s) for (B, H, W, Ci, Co, k, s, ldx, lddy, tr) in layers}
+    assert {(3, 1), (3, 2), (1, 1), (1, 2)} <= kinds
+    assert any(tr for *_, tr in layers) and not all(tr for *_, tr in layers)

@@ -337,6 +337,12 @@ BF16_CONV_CASES = [
 ]
 
 
+# The weight gradients of the two tests below run under the defaults and with each kernel plan_wgrad prefers switched off in turn, so
+# that wgrad3x3r and the generic patch kernel also run on the layers wgrad3x3g and wgrad3x3d take.
+WGRAD_SETTINGS = [dict(wgrad3x3g=1, wgrad3x3r=1, wgrad3x3d=1), dict(wgrad3x3g=0, wgrad3x3r=1, wgrad3x3d=1),
+                  dict(wgrad3x3g=0, wgrad3x3r=0, wgrad3x3d=1), dict(wgrad3x3g=1, wgrad3x3r=1, wgrad3x3d=0)]
+
+
 @pytest.mark.parametrize("case", BF16_CONV_CASES)
 def test_conv2d_bf16(U, case, monkeypatch):
     ops = U.ops
@@ -388,11 +394,14 @@ def test_conv2d_bf16(U, case, monkeypatch):
     close(dxa.dense().permute(0, 3, 1, 2), x.grad, 1e-2, "bf16 dgrad")
 
     if k == 3:
-        ws = ops.Workspace(DEV)
-        dw = torch.full((Co, k, k, Ci), 111.0, device=DEV)
-        ops.conv2d_wgrad(g, xa, ops.Act(to_nhwc_bf16(gy, Co, 0, DEV)), dw, ws, reg=0.002, w=w32)
-        torch.cuda.synchronize()
-        close(dw, (w.grad + 0.002 * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * Ho * Wo) + 1e-6, "bf16 wgrad")
+        gyw = ops.Act(to_nhwc_bf16(gy, Co, 0, DEV))
+        for sw in WGRAD_SETTINGS:
+            ops.set_config(**sw)
+            ws = ops.Workspace(DEV)
+            dw = torch.full((Co, k, k, Ci), 111.0, device=DEV)
+            ops.conv2d_wgrad(g, xa, gyw, dw, ws, reg=0.002, w=w32)
+            torch.cuda.synchronize()
+            close(dw, (w.grad + 0.002 * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * Ho * Wo) + 1e-6, f"bf16 wgrad {sw}")
 
 
 @pytest.mark.parametrize("case", [(2, 6, 5, 16, 8, 3), (1, 4, 4, 64, 32, 3), (2, 3, 3, 128, 64, 3), (2, 12, 40, 48, 72, 3),
@@ -426,11 +435,13 @@ def test_conv2d_transpose_bf16(U, case):
     ops.conv2d_transpose_dgrad(g, gya, wprim, dxa)
     torch.cuda.synchronize()
     close(dxa.dense().permute(0, 3, 1, 2), x.grad, 1e-2, "bf16 convT dgrad")
-    ws = ops.Workspace(DEV)
-    dw = torch.full((Ci, k, k, Co), 111.0, device=DEV)
-    ops.conv2d_transpose_wgrad(g, xa, gya, dw, ws, reg=0.002, w=w32)
-    torch.cuda.synchronize()
-    close(dw, (w.grad + 0.002 * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * H * W) + 1e-6, "bf16 convT wgrad")
+    for sw in WGRAD_SETTINGS:
+        ops.set_config(**sw)
+        ws = ops.Workspace(DEV)
+        dw = torch.full((Ci, k, k, Co), 111.0, device=DEV)
+        ops.conv2d_transpose_wgrad(g, xa, gya, dw, ws, reg=0.002, w=w32)
+        torch.cuda.synchronize()
+        close(dw, (w.grad + 0.002 * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * H * W) + 1e-6, f"bf16 convT wgrad {sw}")
 
 
 @pytest.mark.parametrize("shape", [(2, 12, 10, 16), (1, 4, 4, 1024), (2, 33, 31, 8)])

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <utility>
 #include <vector>
 #include "kernels.h"
 
@@ -199,7 +200,7 @@ inline int conv_family(const unetrir_conv_geom* g, int fam) {
 //      chose, the query entry points (unetrir_conv2d_colstat_rows_bf16, unetrir_conv2d_transpose_colstat_rows_bf16,
 //      unetrir_conv3x3_kernel_id_bf16) return its fields, and it is the only reader of the kernel-selection switches conv3x3,
 //      conv3x3g, conv3x3g_pair, conv3x3h, conv3x3s, conv3x3r, stem, conv3x3p, conv3x3d, upconv3x3g, upconv3x3q and pw1x1 (the
-//      kernels' *_applies predicates are shape rules).
+//      kernels' *_applies predicates are shape rules).  The weight gradients have their own plan, plan_wgrad below.
 enum class Kern { TAPTABLE, TAPTABLE_CLASSES, PATCH, STEM, CONV3X3G_PAIR, CONV3X3P, CONV3X3G, CONV3X3S, CONV3X3H, CONV3X3R, CONV3X3D,
                   UPCONV3X3, UPCONV3X3G, UPCONV3X3Q, PW1X1 };
 struct ConvPlan {
@@ -420,6 +421,17 @@ ConvPlan plan_query(const unetrir_conv_geom* g, Dir dir, int ld_in, bool stats) 
     return plan_conv(c, true, stats);
 }
 
+// ---- the weight-gradient plan: the ONE place that decides which kernel serves a weight gradient and how it splits K, and the only
+//      reader of the switches wgrad3x3g, wgrad3x3r and wgrad3x3d.  run_wgrad launches what it chose; the workspace query sizes every
+//      plan it could choose.
+enum class WgKern { TAPTABLE, PATCH, PATCH1X1, WGRAD3X3G, WGRAD3X3R, WGRAD3X3D };
+struct WgradPlan {
+    WgKern kernel;
+    int nslabs;              // fp32 partial slabs the kernel writes (grid.y); 1 and no l2 term: dw itself
+    long long per_split;     // K per slice: patches (patch kernels) or 32-pixel chunks (tap-table kernel)
+    int npy, npx;            // patch grid of one image (patch kernels)
+};
+
 void wgrad_args(const unetrir_conv_geom* g, int ldx, int lddy, WgradArgs* a) {
     const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
     a->g.B = g->B; a->g.PH = sy.out; a->g.PW = sx.out;
@@ -432,58 +444,121 @@ void wgrad_args(const unetrir_conv_geom* g, int ldx, int lddy, WgradArgs* a) {
     a->lddy = lddy;
 }
 
-size_t wgrad_ws_bytes(const unetrir_conv_geom* g) {
-    if (g->k == 3) {
-        const Same sy = same_geom(g->H, 3, g->stride), sx = same_geom(g->W, 3, g->stride);
-        return wgrad3x3_ws_bytes(g->stride, g->B, sy.out, sx.out, g->Cout, g->Cin);
-    }
+// the Wgrad3Args / Wgrad3ArgsH of a patch-kernel launch; part and the split are the caller's
+template <class A>
+A wgrad3_args(const unetrir_conv_geom* g, const void* x, int ldx, const void* dy, int lddy) {
+    const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
+    A a{};
+    a.x = (decltype(a.x))x; a.ldx = ldx; a.IH = g->H; a.IW = g->W;
+    a.dy = (decltype(a.dy))dy; a.lddy = lddy; a.OH = sy.out; a.OW = sx.out;
+    a.B = g->B; a.C = g->Cin; a.N = g->Cout;
+    a.pad_t = sy.before; a.pad_l = sx.before;
+    return a;
+}
+
+// The split of the patch kernels but wgrad3x3d: tph x tpw patches, about 512 workgroups over the 64 x 64 (N, C) tiles, at least 4
+// patches per slice.
+WgradPlan plan_patch(WgKern kernel, int tph, int tpw, const unetrir_conv_geom* g) {
+    const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
+    WgradPlan p{kernel};
+    p.npy = (sy.out + tph - 1) / tph;
+    p.npx = (sx.out + tpw - 1) / tpw;
+    const long long G = (long long)g->B * p.npy * p.npx;
+    const long long tiles = (long long)((g->Cout + 63) / 64) * ((g->Cin + 63) / 64);
+    long long want = (512 + tiles - 1) / tiles;
+    long long maxs = (G + 3) / 4;
+    if (maxs < 1) maxs = 1;
+    if (want > maxs) want = maxs;
+    if (want < 1) want = 1;
+    p.per_split = (G + want - 1) / want;
+    p.nslabs = (int)((G + p.per_split - 1) / p.per_split);
+    return p;
+}
+// wgrad3x3g: two split-K slices per workgroup share one slab
+WgradPlan plan_wgrad3x3g(const unetrir_conv_geom* g) {
+    WgradPlan p = plan_patch(WgKern::WGRAD3X3G, WG_ROW_TPH, WG_ROW_TPW, g);
+    p.nslabs = (p.nslabs + 1) / 2;
+    return p;
+}
+WgradPlan plan_wgrad3x3d(const unetrir_conv_geom* g) {
+    const Same sy = same_geom(g->H, 3, 2), sx = same_geom(g->W, 3, 2);
+    WgradPlan p{WgKern::WGRAD3X3D};
+    int per;
+    wgrad3x3d_plan(g->B, sy.out, sx.out, g->Cout, g->Cin, &p.nslabs, &per, &p.npy, &p.npx);
+    p.per_split = per;
+    return p;
+}
+WgradPlan plan_taptable(const unetrir_conv_geom* g) {
     WgradArgs a{};
     wgrad_args(g, g->Cin, g->Cout, &a);
-    int ns; long long per;
-    wgrad_plan(a.g, &ns, &per);
-    size_t bytes = (size_t)ns * g->Cout * g->k * g->k * g->Cin * sizeof(float);
-    if (g->k == 1) {          // the bf16 1x1 kernel has its own split plan: the workspace serves both storage modes
-        const Same sy = same_geom(g->H, 1, g->stride), sx = same_geom(g->W, 1, g->stride);
-        const size_t b16 = wgrad1x1_bf16_ws_bytes(g->B, sy.out, sx.out, g->Cout, g->Cin);
-        if (b16 > bytes) bytes = b16;
-    }
-    return bytes;
+    WgradPlan p{WgKern::TAPTABLE};
+    wgrad_plan(a.g, &p.nslabs, &p.per_split);
+    return p;
 }
 
-int conv_wgrad_impl(const unetrir_conv_geom* g, const float* x, int ldx, const float* dy, int lddy, float* dw,
-                    float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (g->k == 3) {   // 3x3: halo-staged patch kernel (wgrad3x3.hip)
-        const Same sy = same_geom(g->H, 3, g->stride), sx = same_geom(g->W, 3, g->stride);
-        Wgrad3Args a3{};
-        a3.x = x; a3.ldx = ldx; a3.IH = g->H; a3.IW = g->W;
-        a3.dy = dy; a3.lddy = lddy; a3.OH = sy.out; a3.OW = sx.out;
-        a3.B = g->B; a3.C = g->Cin; a3.N = g->Cout;
-        a3.pad_t = sy.before; a3.pad_l = sx.before;
-        return launch_wgrad3x3(a3, g->stride, dw, reg, w, ws, ws_bytes, s);
+// g is the geometry the kernels see (the adjoint one for the transposed layers), ldx / lddy the pixel strides of x / dy
+WgradPlan plan_wgrad(const unetrir_conv_geom* g, bool bf16, int ldx, int lddy) {
+    const unetrir_config& cfg = unetrir_cfg();
+    const bool s1 = g->stride == 1;
+    if (g->k == 3 && !bf16) return plan_patch(WgKern::PATCH, s1 ? WG_F32_TPH_S1 : WG_F32_TPH_S2, WG_TPW, g);
+    if (g->k == 3) {          // LDS-DMA kernels first, then (stride 1) the register-staged twin, then the generic patch kernel
+        const Wgrad3ArgsH a = wgrad3_args<Wgrad3ArgsH>(g, nullptr, ldx, nullptr, lddy);
+        if (s1 && cfg.wgrad3x3g && wgrad3x3g_applies(a, true)) return plan_wgrad3x3g(g);
+        if (s1 && cfg.wgrad3x3r && wgrad3x3r_applies(a)) return plan_patch(WgKern::WGRAD3X3R, WG_ROW_TPH, WG_ROW_TPW, g);
+        if (!s1 && cfg.wgrad3x3d && wgrad3x3d_applies(a, true)) return plan_wgrad3x3d(g);
+        return plan_patch(WgKern::PATCH, s1 ? WG_BF16_TPH_S1 : WG_BF16_TPH_S2, WG_TPW, g);
     }
-    WgradArgs a{};
-    wgrad_args(g, ldx, lddy, &a);
-    a.x = x; a.dy = dy;
-    return launch_igemm_wgrad(a, dw, reg, w, ws, ws_bytes, s);
+    if (g->k == 1 && bf16) return plan_patch(WgKern::PATCH1X1, s1 ? WG_1X1_TPH_S1 : WG_1X1_TPH_S2, WG_TPW, g);
+    return plan_taptable(g);  // other kernel sizes, and fp32 1x1: the tap-table kernel (bf16: on the bf16 tensors as stored)
 }
 
-int conv_wgrad_bf16_impl(const unetrir_conv_geom* g, const __bf16* x, int ldx, const __bf16* dy, int lddy, float* dw, float reg,
-                         const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (g->k != 3 && g->k != 1) {      // other kernel sizes (kernels = 6: the reference's constructor default): the tap-table weight
-                                       // gradient on the bf16 tensors as stored, fp32 MFMA arithmetic
+// The workspace of a weight gradient: the largest slab set of every plan that could serve the geometry - either storage type, any
+// switches, any pixel strides (the shape rules without their ld limits) - so run_wgrad never needs more.  The 1x1 kernel is sized at
+// both of its patch heights whatever the stride, as the query always has (ReduceBatch's packing follows its value).
+size_t wgrad_ws_bytes(const unetrir_conv_geom* g) {
+    int slabs = 0;
+    auto cover = [&](const WgradPlan& p) { if (p.nslabs > slabs) slabs = p.nslabs; };
+    if (g->k == 3) {
+        const Wgrad3ArgsH a = wgrad3_args<Wgrad3ArgsH>(g, nullptr, g->Cin, nullptr, g->Cout);
+        const bool s1 = g->stride == 1;
+        cover(plan_patch(WgKern::PATCH, s1 ? WG_F32_TPH_S1 : WG_F32_TPH_S2, WG_TPW, g));
+        cover(plan_patch(WgKern::PATCH, s1 ? WG_BF16_TPH_S1 : WG_BF16_TPH_S2, WG_TPW, g));
+        if (s1 && wgrad3x3g_applies(a, false)) cover(plan_wgrad3x3g(g));
+        if (s1 && wgrad3x3r_applies(a)) cover(plan_patch(WgKern::WGRAD3X3R, WG_ROW_TPH, WG_ROW_TPW, g));
+        if (!s1 && wgrad3x3d_applies(a, false)) cover(plan_wgrad3x3d(g));
+    } else {
+        cover(plan_taptable(g));
+        if (g->k == 1) {
+            cover(plan_patch(WgKern::PATCH1X1, WG_1X1_TPH_S1, WG_TPW, g));
+            cover(plan_patch(WgKern::PATCH1X1, WG_1X1_TPH_S2, WG_TPW, g));
+        }
+    }
+    return (size_t)slabs * g->Cout * g->k * g->k * g->Cin * sizeof(float);
+}
+
+// the partial-sum kernel of plan p into part
+int launch_wgrad(const unetrir_conv_geom* g, const WgradPlan& p, bool bf16, const void* x, int ldx, const void* dy, int lddy, float* part,
+                 hipStream_t s) {
+    if (p.kernel == WgKern::TAPTABLE) {
         WgradArgs a{};
         wgrad_args(g, ldx, lddy, &a);
-        a.x = (const float*)x; a.dy = (const float*)dy;
-        return launch_igemm_wgrad(a, dw, reg, w, ws, ws_bytes, s, 1);
+        a.x = (const float*)x; a.dy = (const float*)dy; a.part = part; a.chunks_per_split = p.per_split;
+        return launch_igemm_wgrad(a, p.nslabs, s, bf16);
     }
-    const Same sy = same_geom(g->H, g->k, g->stride), sx = same_geom(g->W, g->k, g->stride);
-    Wgrad3ArgsH a3{};
-    a3.x = x; a3.ldx = ldx; a3.IH = g->H; a3.IW = g->W;
-    a3.dy = dy; a3.lddy = lddy; a3.OH = sy.out; a3.OW = sx.out;
-    a3.B = g->B; a3.C = g->Cin; a3.N = g->Cout;
-    a3.pad_t = sy.before; a3.pad_l = sx.before;
-    if (g->k == 1) return launch_wgrad1x1_bf16(a3, g->stride, dw, reg, w, ws, ws_bytes, s);
-    return launch_wgrad3x3_bf16(a3, g->stride, dw, reg, w, ws, ws_bytes, s);
+    if (!bf16) {
+        Wgrad3Args a = wgrad3_args<Wgrad3Args>(g, x, ldx, dy, lddy);
+        a.part = part; a.patches_per_split = (int)p.per_split; a.npy = p.npy; a.npx = p.npx;
+        return launch_wgrad3x3(a, g->stride, p.nslabs, s);
+    }
+    Wgrad3ArgsH a = wgrad3_args<Wgrad3ArgsH>(g, x, ldx, dy, lddy);
+    a.part = part; a.patches_per_split = (int)p.per_split; a.npy = p.npy; a.npx = p.npx;
+    switch (p.kernel) {
+        case WgKern::WGRAD3X3G: return launch_wgrad3x3g_bf16(a, p.nslabs, s);
+        case WgKern::WGRAD3X3R: return launch_wgrad3x3r_bf16(a, p.nslabs, s);
+        case WgKern::WGRAD3X3D: return launch_wgrad3x3d_bf16(a, p.nslabs, s);
+        case WgKern::PATCH1X1: return launch_wgrad1x1_bf16(a, g->stride, p.nslabs, s);
+        default: return launch_wgrad3x3_bf16(a, g->stride, p.nslabs, s);
+    }
 }
 
 // Conv2DTranspose(k, s=2, 'same') on an H x W input is the adjoint of Conv2D(k, s=2, 'same') that maps the
@@ -497,6 +572,32 @@ inline unetrir_conv_geom adjoint_geom(const unetrir_conv_geom* g) {
 
 inline bool ld_ok(int ld, int c) { return ld >= c && (ld & 3) == 0; }
 inline bool ldh_ok(int ld, int c) { return ld >= c && (ld & 7) == 0; }     // bf16: 16-byte rows
+
+// One weight gradient dw[Cout][k][k][Cin] = sum_pixels dy * x + reg * w (transposed: of the Conv2DTranspose, whose weight gradient is
+// that of its adjoint Conv2D - with our dy as its x and our x as its dy).  The planned kernel writes dw itself (one slab, reg == 0) or
+// its slabs into ws; then the fixed-order reduction is launched or, with `defer`, described there for unetrir_splitk_reduce_batched.
+template <class P>
+int run_wgrad(const unetrir_conv_geom* gin, bool transposed, const void* x, int ldx, const void* dy, int lddy, float* dw, float reg,
+              const float* w, void* ws, size_t ws_bytes, unetrir_reduce_desc* defer, hipStream_t s) {
+    if (defer) *defer = unetrir_reduce_desc{};          // nsplit == 0: nothing to reduce
+    if (!geom_ok(gin)) return UNETRIR_EINVAL;
+    const unetrir_conv_geom g = transposed ? adjoint_geom(gin) : *gin;
+    if (transposed) { std::swap(x, dy); std::swap(ldx, lddy); }
+    const bool ld_fits = P::is_bf16 ? (g.Cin & 7) == 0 && (g.Cout & 7) == 0 && ldh_ok(ldx, g.Cin) && ldh_ok(lddy, g.Cout)
+                                    : (g.Cin & 3) == 0 && ld_ok(ldx, g.Cin) && ld_ok(lddy, g.Cout);
+    if (!x || !dy || !dw || !ld_fits || (reg != 0.f && !w)) return UNETRIR_EINVAL;
+    ProfScope ps(conv_family(&g, UNETRIR_FAM_CONV_WGRAD), conv_flops(&g), s);
+    const WgradPlan p = plan_wgrad(&g, P::is_bf16, ldx, lddy);
+    const size_t nout = (size_t)g.Cout * g.k * g.k * g.Cin;
+    const bool direct = p.nslabs == 1 && reg == 0.f;
+    if (!direct && ws_bytes < (size_t)p.nslabs * nout * sizeof(float)) return UNETRIR_EINVAL;
+    float* part = direct ? dw : (float*)ws;
+    const int err = launch_wgrad(&g, p, P::is_bf16, x, ldx, dy, lddy, part, s);
+    if (err || direct) return err;
+    if (!defer) return launch_splitk_reduce(part, p.nslabs, nout, dw, reg, w, s);
+    *defer = unetrir_reduce_desc{part, p.nslabs, nout, dw, reg, w};
+    return 0;
+}
 
 }  // namespace
 
@@ -522,11 +623,7 @@ size_t unetrir_conv2d_wgrad_ws_bytes(const unetrir_conv_geom* g) { return geom_o
 
 int unetrir_conv2d_wgrad_f32(const unetrir_conv_geom* g, const float* x, int ldx, const float* dy, int lddy, float* dw,
                              float reg_coef, const float* w, void* ws, size_t ws_bytes, unetrir_stream_t stream) {
-    if (!geom_ok(g) || !x || !dy || !dw || (g->Cin & 3) || !ld_ok(ldx, g->Cin) || (lddy & 3) || lddy < g->Cout ||
-        (reg_coef != 0.f && !w))
-        return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_WGRAD), conv_flops(g), (hipStream_t)stream);
-    return conv_wgrad_impl(g, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, (hipStream_t)stream);
+    return run_wgrad<F32>(g, false, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, nullptr, (hipStream_t)stream);
 }
 
 int unetrir_conv2d_transpose_fwd_f32(const unetrir_conv_geom* g, const float* x, int ldx, const float* wt,
@@ -556,13 +653,7 @@ size_t unetrir_conv2d_transpose_wgrad_ws_bytes(const unetrir_conv_geom* g) {
 int unetrir_conv2d_transpose_wgrad_f32(const unetrir_conv_geom* g, const float* x, int ldx, const float* dy, int lddy,
                                        float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
                                        unetrir_stream_t stream) {
-    if (!geom_ok(g) || !x || !dy || !dw || (g->Cout & 3) || !ld_ok(lddy, g->Cout) || (ldx & 3) ||
-        ldx < g->Cin || (reg_coef != 0.f && !w))
-        return UNETRIR_EINVAL;
-    const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_WGRAD), conv_flops(&c), (hipStream_t)stream);
-    // adjoint conv: its "x" is our dy (2H x 2W, Cout channels), its "dy" is our x (H x W, Cin channels)
-    return conv_wgrad_impl(&c, dy, lddy, x, ldx, dw, reg_coef, w, ws, ws_bytes, (hipStream_t)stream);
+    return run_wgrad<F32>(g, true, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, nullptr, (hipStream_t)stream);
 }
 
 /* ---- bf16-storage variants: x / dy / y / dx and the weight work copies are bf16, bias fp32, weight gradients fp32 ---- */
@@ -646,34 +737,21 @@ int unetrir_conv2d_transpose_fwd_colstat_bf16(const unetrir_conv_geom* g, const 
 
 int unetrir_conv2d_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy,
                               float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes, unetrir_stream_t stream) {
-    if (!geom_ok(g) || !x || !dy || !dw || (g->Cin & 7) || (g->Cout & 7) || !ldh_ok(ldx, g->Cin) || !ldh_ok(lddy, g->Cout) ||
-        (reg_coef != 0.f && !w))
-        return UNETRIR_EINVAL;
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_WGRAD), conv_flops(g), (hipStream_t)stream);
-    return conv_wgrad_bf16_impl(g, (const __bf16*)x, ldx, (const __bf16*)dy, lddy, dw, reg_coef, w, ws, ws_bytes, (hipStream_t)stream);
+    return run_wgrad<BF16>(g, false, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, nullptr, (hipStream_t)stream);
 }
-
-namespace {
-struct SinkScope {         // the weight-gradient launchers below this scope record their reduction in *d instead of launching it
-    explicit SinkScope(unetrir_reduce_desc* d) { d->part = nullptr; d->nsplit = 0; d->n = 0; d->out = nullptr; d->reg = 0.f; d->w = nullptr; set_reduce_sink(d); }
-    ~SinkScope() { set_reduce_sink(nullptr); }
-};
-}  // namespace
 
 int unetrir_conv2d_wgrad_partials_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy,
                                        float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes, unetrir_reduce_desc* desc,
                                        unetrir_stream_t stream) {
     if (!desc) return UNETRIR_EINVAL;
-    SinkScope sc(desc);
-    return unetrir_conv2d_wgrad_bf16(g, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, stream);
+    return run_wgrad<BF16>(g, false, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, desc, (hipStream_t)stream);
 }
 
 int unetrir_conv2d_transpose_wgrad_partials_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy,
                                                  int lddy, float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
                                                  unetrir_reduce_desc* desc, unetrir_stream_t stream) {
     if (!desc) return UNETRIR_EINVAL;
-    SinkScope sc(desc);
-    return unetrir_conv2d_transpose_wgrad_bf16(g, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, stream);
+    return run_wgrad<BF16>(g, true, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, desc, (hipStream_t)stream);
 }
 
 int unetrir_conv2d_transpose_fwd_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* wt,
@@ -708,12 +786,7 @@ int unetrir_conv2d_transpose_dgrad_bf16(const unetrir_conv_geom* g, const unetri
 int unetrir_conv2d_transpose_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy,
                                         int lddy, float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
                                         unetrir_stream_t stream) {
-    if (!geom_ok(g) || !x || !dy || !dw || (g->Cin & 7) || (g->Cout & 7) || !ldh_ok(lddy, g->Cout) ||
-        !ldh_ok(ldx, g->Cin) || (reg_coef != 0.f && !w))
-        return UNETRIR_EINVAL;
-    const unetrir_conv_geom c = adjoint_geom(g);
-    ProfScope ps(conv_family(g, UNETRIR_FAM_CONV_WGRAD), conv_flops(&c), (hipStream_t)stream);
-    return conv_wgrad_bf16_impl(&c, (const __bf16*)dy, lddy, (const __bf16*)x, ldx, dw, reg_coef, w, ws, ws_bytes, (hipStream_t)stream);
+    return run_wgrad<BF16>(g, true, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, nullptr, (hipStream_t)stream);
 }
 
 /* fp32 master weights [N][T][C] -> bf16 work copies: same orientation with the channel dimension padded to Cp, and

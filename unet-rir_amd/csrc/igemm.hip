@@ -385,11 +385,11 @@ template <int G>
 __device__ __forceinline__ void splitk_reduce_body(float4 (*red)[64], const unsigned block, const float* __restrict__ part, int nsplit, size_t n,
                                                    float* __restrict__ out, float reg, const float* __restrict__ w) {
     const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    if (grp >= G) return;                          // the batched kernel runs 8 waves whatever G is (a finished wave does not count at the barrier)
+    const bool busy = grp < G;                     // the batched kernel runs 8 waves whatever G is: the others only meet the barrier
     const size_t i4 = ((size_t)block * 64 + lane) * 4;
     const bool full = i4 + 3 < n;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (full) {
+    if (busy && full) {
         const float* p = part + i4;
         int k = grp;
         for (; k + 7 * G < nsplit; k += 8 * G) {
@@ -403,13 +403,13 @@ __device__ __forceinline__ void splitk_reduce_body(float4 (*red)[64], const unsi
             const float4 v = *reinterpret_cast<const float4*>(p + (size_t)k * n);
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
         }
-    } else if (i4 < n) {
+    } else if (busy && i4 < n) {
         float* sp = &s.x;
         for (int k = grp; k < nsplit; k += G)
             for (size_t i = i4; i < n; ++i) sp[i - i4] += part[(size_t)k * n + i];
     }
     if (G > 1) {
-        red[grp][lane] = s;
+        if (busy) red[grp][lane] = s;
         __syncthreads();
         if (grp != 0) return;
 #pragma unroll
@@ -418,7 +418,7 @@ __device__ __forceinline__ void splitk_reduce_body(float4 (*red)[64], const unsi
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
         }
     }
-    if (i4 >= n) return;
+    if (!busy || i4 >= n) return;
     if (full) {
         if (reg != 0.f) {
             const float4 v = *reinterpret_cast<const float4*>(w + i4);
@@ -557,14 +557,7 @@ int wgrad_plan(const IgemmGeom& g, int* nsplit, long long* chunks_per_split) {
     return 0;
 }
 
-int launch_igemm_wgrad(WgradArgs a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s, int bf16_operands) {
-    int nsplit; long long per;
-    wgrad_plan(a.g, &nsplit, &per);
-    const size_t nout = (size_t)a.g.N * a.g.wtaps * a.g.C;
-    const bool direct = (nsplit == 1 && reg == 0.f);
-    if (!direct && ws_bytes < (size_t)nsplit * nout * sizeof(float)) return UNETRIR_EINVAL;
-    a.part = direct ? dw : (float*)ws;
-    a.chunks_per_split = per;
+int launch_igemm_wgrad(const WgradArgs& a, int nsplit, hipStream_t s, int bf16_operands) {
     const int br = a.g.N > 64 ? 128 : 64;
     const unsigned tiles = (unsigned)(((a.g.N + br - 1) / br) * ((a.g.ntaps * a.g.C + WG_COLS - 1) / WG_COLS));
     if (bf16_operands) {      // a.x / a.dy point at bf16 tensors
@@ -572,12 +565,7 @@ int launch_igemm_wgrad(WgradArgs a, float* dw, float reg, const float* w, void* 
         else hipLaunchKernelGGL((igemm_wgrad_kernel<64, __bf16>), dim3(tiles, nsplit), dim3(256), 0, s, a);
     } else if (br == 128) hipLaunchKernelGGL(igemm_wgrad_kernel<128>, dim3(tiles, nsplit), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(igemm_wgrad_kernel<64>, dim3(tiles, nsplit), dim3(256), 0, s, a);
-    int err = (int)hipGetLastError();
-    if (err) return err;
-    if (!direct) {
-        err = launch_splitk_reduce((const float*)ws, nsplit, nout, dw, reg, w, s);
-    }
-    return err;
+    return (int)hipGetLastError();
 }
 
 // Few outputs, many slabs (the 1x1 and small 3x3 weight gradients of the residual graphs: 1 K .. 64 K floats from up to 512
@@ -652,15 +640,12 @@ __global__ __launch_bounds__(512) void splitk_reduce_batched_kernel(const Reduce
     }
 }
 
-// A weight-gradient entry point called with a descriptor to fill (unetrir_*_wgrad_partials_*) runs its implementation with this
-// pointer set: launch_splitk_reduce then records what it was asked to reduce instead of launching.  Thread-local: the ABI stays
-// re-entrant across host threads.
-thread_local unetrir_reduce_desc* t_reduce_sink = nullptr;
-void set_reduce_sink(unetrir_reduce_desc* d) { t_reduce_sink = d; }
-
-static inline bool reduce_is_wide(int nsplit, size_t n, const float* part, const float* out, const float* w) {
+// The form of one reduction: 0 = the wide kernel, else the narrow one with that many slab groups (8 / 4 / 2 / 1).  The single launch
+// and the batched one both take it from here: the same groups sum the same slabs in the same order - bit-identical.
+static int reduce_kind(int nsplit, size_t n, const float* part, const float* out, const float* w) {
     const size_t n4 = (n + 3) / 4;
-    return (n & 3) == 0 && nsplit >= 32 && (n4 + 63) / 64 < 128 && (((uintptr_t)part | (uintptr_t)out | (uintptr_t)w) & 15) == 0;
+    if ((n & 3) == 0 && nsplit >= 32 && (n4 + 63) / 64 < 128 && (((uintptr_t)part | (uintptr_t)out | (uintptr_t)w) & 15) == 0) return 0;
+    return nsplit >= 8 ? 8 : nsplit >= 4 ? 4 : nsplit >= 2 ? 2 : 1;
 }
 
 extern "C" int unetrir_splitk_reduce_batched(const unetrir_reduce_desc* desc, int n, unetrir_stream_t stream) {
@@ -684,13 +669,13 @@ extern "C" int unetrir_splitk_reduce_batched(const unetrir_reduce_desc* desc, in
         const unetrir_reduce_desc& d = desc[i];
         if (d.nsplit == 0) continue;                            // the weight gradient went straight into dw: nothing to reduce
         if (!d.part || !d.out || d.nsplit < 0 || d.n == 0 || (d.reg != 0.f && !d.w)) return UNETRIR_EINVAL;
-        const bool wide = reduce_is_wide(d.nsplit, d.n, d.part, d.out, d.w);
+        const int kind = reduce_kind(d.nsplit, d.n, d.part, d.out, d.w);
         const size_t n4 = (d.n + 3) / 4;
-        const size_t blocks = wide ? (n4 + 15) / 16 : (n4 + 63) / 64;
+        const size_t blocks = kind == 0 ? (n4 + 15) / 16 : (n4 + 63) / 64;
         if (blocks > 0x3fffffffu) return UNETRIR_EINVAL;
         if (a.n == REDUCE_BATCH || (size_t)a.first_block[a.n] + blocks > 0x7fffffffu) { const int e = flush(); if (e) return e; a.first_block[0] = 0; }
         a.d[a.n] = d;
-        a.kind[a.n] = wide ? 0 : (d.nsplit >= 8 ? 8 : d.nsplit >= 4 ? 4 : d.nsplit >= 2 ? 2 : 1);      // as launch_splitk_reduce picks them
+        a.kind[a.n] = (unsigned char)kind;
         a.first_block[a.n + 1] = a.first_block[a.n] + (unsigned)blocks;
         ++a.n;
     }
@@ -698,23 +683,16 @@ extern "C" int unetrir_splitk_reduce_batched(const unetrir_reduce_desc* desc, in
 }
 
 int launch_splitk_reduce(const float* part, int nsplit, size_t n, float* out, float reg, const float* w, hipStream_t s) {
-    if (t_reduce_sink) {          // deferred: the caller reduces later, together with others (unetrir_splitk_reduce_batched)
-        if (t_reduce_sink->nsplit != 0) return UNETRIR_EINVAL;          // one reduction per weight gradient
-        t_reduce_sink->part = part; t_reduce_sink->nsplit = nsplit; t_reduce_sink->n = n; t_reduce_sink->out = out;
-        t_reduce_sink->reg = reg; t_reduce_sink->w = w;
-        return 0;
-    }
     const size_t n4 = (n + 3) / 4;
-    // (round 3: taking larger outputs too - up to 4096 narrow workgroups - moves single launches by +-8 us and the step by nothing)
-    if (reduce_is_wide(nsplit, n, part, out, w)) {
-        hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)((n4 + 15) / 16)), dim3(512), 0, s, part, nsplit, n, out, reg, w);
-        return (int)hipGetLastError();
-    }
     const dim3 grid((unsigned)((n4 + 63) / 64));
-    if (nsplit >= 8) hipLaunchKernelGGL(splitk_reduce_kernel<8>, grid, dim3(512), 0, s, part, nsplit, n, out, reg, w);
-    else if (nsplit >= 4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, grid, dim3(256), 0, s, part, nsplit, n, out, reg, w);
-    else if (nsplit >= 2) hipLaunchKernelGGL(splitk_reduce_kernel<2>, grid, dim3(128), 0, s, part, nsplit, n, out, reg, w);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<1>, grid, dim3(64), 0, s, part, nsplit, n, out, reg, w);
+    // (round 3: taking larger outputs too - up to 4096 narrow workgroups - moves single launches by +-8 us and the step by nothing)
+    switch (reduce_kind(nsplit, n, part, out, w)) {
+        case 0: hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)((n4 + 15) / 16)), dim3(512), 0, s, part, nsplit, n, out, reg, w); break;
+        case 8: hipLaunchKernelGGL(splitk_reduce_kernel<8>, grid, dim3(512), 0, s, part, nsplit, n, out, reg, w); break;
+        case 4: hipLaunchKernelGGL(splitk_reduce_kernel<4>, grid, dim3(256), 0, s, part, nsplit, n, out, reg, w); break;
+        case 2: hipLaunchKernelGGL(splitk_reduce_kernel<2>, grid, dim3(128), 0, s, part, nsplit, n, out, reg, w); break;
+        default: hipLaunchKernelGGL(splitk_reduce_kernel<1>, grid, dim3(64), 0, s, part, nsplit, n, out, reg, w); break;
+    }
     return (int)hipGetLastError();
 }
 

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void igemm_fwd_bf16_kernel4(const IgemmArgsH4 
 // ------------------------------------------------------------------------------------------------
 // 3x3 weight gradient, bf16 operands, fp32 partial slabs (see wgrad3x3.hip for the patch scheme)
 // ------------------------------------------------------------------------------------------------
-#define TPW 8
+#define TPW WG_TPW
 
 // KS = 3: the 3x3 layers.  KS = 1: the 1x1 layers of the residual graphs (dl_models/res_ae.py:455-512) - the same patch scheme
 // with one tap and no halo (pad_t = pad_l = 0).
@@ -580,64 +580,19 @@ int launch_igemm_fwd_bf16_x4(const IgemmArgsH* a, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-void wgrad3x3_plan_tph(int TPH, int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx);
-// bf16 patch heights: one barrier pair and one global round trip are amortised over TPH*8 pixels of MFMA work
-#define TPH_S1 8
-#define TPH_S2 4
-
-int launch_wgrad3x3_bf16(Wgrad3ArgsH a, int stride, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (stride == 1) {       // patch rows reused from registers: LDS-DMA staged (wgrad3x3g.hip), else register staged (wgrad3x3r.hip)
-        int err = launch_wgrad3x3g_bf16(a, dw, reg, w, ws, ws_bytes, s);
-        if (err != WGRAD3X3R_NOT_TAKEN) return err;
-        err = launch_wgrad3x3r_bf16(a, dw, reg, w, ws, ws_bytes, s);
-        if (err != WGRAD3X3R_NOT_TAKEN) return err;
-    } else {                 // stride 2: LDS-DMA kernel with the column-de-interleaved x patch (wgrad3x3d.hip)
-        const int err = launch_wgrad3x3d_bf16(a, dw, reg, w, ws, ws_bytes, s);
-        if (err != WGRAD3X3R_NOT_TAKEN) return err;
-    }
-    int ns, per;
-    wgrad3x3_plan_tph(stride == 1 ? TPH_S1 : TPH_S2, a.B, a.OH, a.OW, a.N, a.C, &ns, &per, &a.npy, &a.npx);
-    const size_t nout = (size_t)a.N * 9 * a.C;
-    const bool direct = (ns == 1 && reg == 0.f);
-    if (!direct && ws_bytes < (size_t)ns * nout * sizeof(float)) return UNETRIR_EINVAL;
-    a.part = direct ? dw : (float*)ws;
-    a.patches_per_split = per;
+int launch_wgrad3x3_bf16(const Wgrad3ArgsH& a, int stride, int nslabs, hipStream_t s) {
     const unsigned tiles = (unsigned)(((a.N + 63) / 64) * ((a.C + 63) / 64));
-    if (stride == 1) hipLaunchKernelGGL((wgrad3x3_bf16_kernel<1, TPH_S1>), dim3(tiles, ns), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wgrad3x3_bf16_kernel<2, TPH_S2>), dim3(tiles, ns), dim3(256), 0, s, a);
-    int err = (int)hipGetLastError();
-    if (err || direct) return err;
-    return launch_splitk_reduce((const float*)ws, ns, nout, dw, reg, w, s);
+    if (stride == 1) hipLaunchKernelGGL((wgrad3x3_bf16_kernel<1, WG_BF16_TPH_S1>), dim3(tiles, nslabs), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((wgrad3x3_bf16_kernel<2, WG_BF16_TPH_S2>), dim3(tiles, nslabs), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
 }
 
-// 1x1 weight gradient (stride 1 or 2): 16 x 8 pixel patches (one tap of MFMA work per 16-pixel K step, so taller patches)
-#define TPH_1X1 16
-#define TPH_1X1_S2 8          // stride 2: the x patch is (2 TPH - 1) x 15 pixels
-size_t wgrad1x1_bf16_ws_bytes(int B, int OH, int OW, int N, int C) {
-    size_t m = 0;
-    for (int tph : {TPH_1X1, TPH_1X1_S2}) {
-        int ns, per, npy, npx;
-        wgrad3x3_plan_tph(tph, B, OH, OW, N, C, &ns, &per, &npy, &npx);
-        const size_t b = (size_t)ns * N * C * sizeof(float);
-        if (b > m) m = b;
-    }
-    return m;
-}
-
-int launch_wgrad1x1_bf16(Wgrad3ArgsH a, int stride, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    int ns, per;
-    wgrad3x3_plan_tph(stride == 1 ? TPH_1X1 : TPH_1X1_S2, a.B, a.OH, a.OW, a.N, a.C, &ns, &per, &a.npy, &a.npx);
-    const size_t nout = (size_t)a.N * a.C;
-    const bool direct = (ns == 1 && reg == 0.f);
-    if (!direct && ws_bytes < (size_t)ns * nout * sizeof(float)) return UNETRIR_EINVAL;
-    a.part = direct ? dw : (float*)ws;
-    a.patches_per_split = per;
+// 1x1 weight gradient (stride 1 or 2): the KS = 1 instance of the patch kernel
+int launch_wgrad1x1_bf16(const Wgrad3ArgsH& a, int stride, int nslabs, hipStream_t s) {
     const unsigned tiles = (unsigned)(((a.N + 63) / 64) * ((a.C + 63) / 64));
-    if (stride == 1) hipLaunchKernelGGL((wgrad3x3_bf16_kernel<1, TPH_1X1, 1, 1>), dim3(tiles, ns), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wgrad3x3_bf16_kernel<2, TPH_1X1_S2, 1, 1>), dim3(tiles, ns), dim3(256), 0, s, a);
-    const int err = (int)hipGetLastError();
-    if (err || direct) return err;
-    return launch_splitk_reduce((const float*)ws, ns, nout, dw, reg, w, s);
+    if (stride == 1) hipLaunchKernelGGL((wgrad3x3_bf16_kernel<1, WG_1X1_TPH_S1, 1, 1>), dim3(tiles, nslabs), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((wgrad3x3_bf16_kernel<2, WG_1X1_TPH_S2, 1, 1>), dim3(tiles, nslabs), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
 }
 
 int launch_cast_weight(const float* w, void* o, int N, int T, int C, int Cp, hipStream_t s) {

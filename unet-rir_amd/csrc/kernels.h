@@ -57,13 +57,25 @@ struct WgradArgs {
 };
 
 int launch_igemm_fwd(const IgemmArgs& a, hipStream_t s);
-int wgrad_plan(const IgemmGeom& g, int* nsplit, long long* chunks_per_split);
-int launch_igemm_wgrad(WgradArgs a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s, int bf16_operands = 0);
 int launch_transpose_weight(const float* w, float* wt, int N, int T, int C, hipStream_t s);
 int launch_splitk_reduce(const float* part, int nsplit, size_t n, float* out, float reg, const float* w, hipStream_t s);
-// While a sink is set (this host thread), launch_splitk_reduce records its arguments there instead of launching: the
-// *_wgrad_partials_* entry points (api.hip) run the ordinary weight-gradient launchers under it.
-void set_reduce_sink(unetrir_reduce_desc* d);
+
+// ---- weight gradients.  Every kernel below writes fp32 partial slabs [slab][N][taps][C] (grid.y = slab) that a fixed-order split-K
+// reduction sums - or, with one slab and no l2 term, dw itself.  Which kernel serves a layer, how it splits K and what becomes of the
+// slabs is decided in ONE place, plan_wgrad / run_wgrad (api.hip); the launchers only launch the partial-sum kernel into `part` with
+// the plan's numbers.
+// Patch shapes (output pixels, rows x columns) in which the patch-walking kernels walk K; plan_wgrad splits K into whole patches.
+#define WG_TPW 8                  // wgrad3x3_kernel (fp32) and wgrad3x3_bf16_kernel (bf16 3x3 and 1x1): 8 columns; rows:
+#define WG_F32_TPH_S1 4           //   fp32 3x3, stride 1 / 2
+#define WG_F32_TPH_S2 2
+#define WG_BF16_TPH_S1 8          //   bf16 3x3: one barrier pair and one global round trip are amortised over TPH*8 pixels of MFMA work
+#define WG_BF16_TPH_S2 4
+#define WG_1X1_TPH_S1 16          //   bf16 1x1: one tap of MFMA work per 16-pixel K step, so taller patches
+#define WG_1X1_TPH_S2 8           //     (stride 2: the x patch is (2 TPH - 1) x 15 pixels)
+#define WG_ROW_TPH 8              // wgrad3x3g and wgrad3x3r: 8 x 16
+#define WG_ROW_TPW 16
+int wgrad_plan(const IgemmGeom& g, int* nsplit, long long* chunks_per_split);       // the tap-table kernel's own split
+int launch_igemm_wgrad(const WgradArgs& a, int nsplit, hipStream_t s, int bf16_operands);
 
 // 3x3 weight gradient with a halo-staged x patch (wgrad3x3.hip)
 struct Wgrad3Args {
@@ -74,8 +86,7 @@ struct Wgrad3Args {
     float* part;                              // [nsplit][N][9][C]
     int patches_per_split, npy, npx;
 };
-size_t wgrad3x3_ws_bytes(int stride, int B, int OH, int OW, int N, int C);
-int launch_wgrad3x3(Wgrad3Args a, int stride, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_wgrad3x3(const Wgrad3Args& a, int stride, int nslabs, hipStream_t s);
 
 // ---- bf16-storage variants (igemm_bf16.hip): activations / weight work copies bf16, accumulate fp32 ----
 struct IgemmArgsH {
@@ -111,15 +122,17 @@ struct Wgrad3ArgsH {
 };
 int launch_igemm_fwd_bf16(const IgemmArgsH& a, hipStream_t s);
 int launch_igemm_fwd_bf16_x4(const IgemmArgsH* a, hipStream_t s);
-int launch_wgrad3x3_bf16(Wgrad3ArgsH a, int stride, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s);
-bool wgrad3x3d_applies(const Wgrad3ArgsH& a);       // stride 2, even sizes: LDS-DMA kernel with the de-interleaved x patch
-size_t wgrad3x3d_ws_bytes(int B, int OH, int OW, int N, int C);
-int launch_wgrad3x3d_bf16(Wgrad3ArgsH a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s);
-size_t wgrad1x1_bf16_ws_bytes(int B, int OH, int OW, int N, int C);
-int launch_wgrad1x1_bf16(Wgrad3ArgsH a, int stride, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s);
-#define WGRAD3X3R_NOT_TAKEN (-12345)
-int launch_wgrad3x3g_bf16(Wgrad3ArgsH a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_wgrad3x3r_bf16(Wgrad3ArgsH a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_wgrad3x3_bf16(const Wgrad3ArgsH& a, int stride, int nslabs, hipStream_t s);     // the generic patch kernel
+int launch_wgrad1x1_bf16(const Wgrad3ArgsH& a, int stride, int nslabs, hipStream_t s);
+// Shape rules of the bf16 3x3 weight-gradient kernels.  with_ld = false (the workspace query, which has no pixel strides): the limits
+// that depend on ldx / lddy are left out.
+bool wgrad3x3g_applies(const Wgrad3ArgsH& a, bool with_ld);        // stride 1: LDS-DMA kernel with register reuse of patch rows
+int launch_wgrad3x3g_bf16(Wgrad3ArgsH a, int ns, hipStream_t s);
+bool wgrad3x3r_applies(const Wgrad3ArgsH& a);                     // stride 1: register-staged twin of wgrad3x3g
+int launch_wgrad3x3r_bf16(const Wgrad3ArgsH& a, int nslabs, hipStream_t s);
+bool wgrad3x3d_applies(const Wgrad3ArgsH& a, bool with_ld);        // stride 2, even sizes: LDS-DMA kernel with the de-interleaved x patch
+void wgrad3x3d_plan(int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx);     // its own split
+int launch_wgrad3x3d_bf16(Wgrad3ArgsH a, int nslabs, hipStream_t s);
 int launch_cast_weight(const float* w, void* o, int N, int T, int C, int Cp, hipStream_t s);
 int launch_cast_weights_batched(const unetrir_cast_desc* desc_dev, int n_layers, hipStream_t s);
 int launch_transpose_cast_weight(const float* w, void* wt, int N, int T, int C, int Np, hipStream_t s);
@@ -139,7 +152,7 @@ struct Conv3Args {
                               // (img * tiles_y + ty) * tiles_x + tx)
 };
 // Which of the kernels below serves a launch - and that includes the kernel-selection switches they belong to - is decided in ONE
-// place, plan_conv (api.hip).  The *_applies predicates are shape rules only.
+// place, plan_conv (api.hip), as plan_wgrad decides it for the weight gradients above.  All *_applies predicates are shape rules only.
 int launch_conv3x3(const Conv3Args& a, int bf16, hipStream_t s);     // the generic patch-staged kernel (conv3x3.hip); no statistics
 long long conv3x3r_colstat_rows(const Conv3Args& a);
 int launch_conv3x3r_bf16(const Conv3Args& a, hipStream_t s);

@@ -13,7 +13,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#define TPW 8            // patch width (output pixels); patch height TPH_ is 4 (stride 1) or 2 (stride 2)
+#define TPW WG_TPW       // patch width (output pixels); patch height TPH_ is 4 (stride 1) or 2 (stride 2)
 #define W3_LD 68          // 64 channels + 4 pad (floats)
 
 template <int SI, int TPH>
@@ -119,50 +119,9 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_kernel(const Wgrad3Args a) {
     }
 }
 
-void wgrad3x3_plan_tph(int TPH, int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx);
-void wgrad3x3_plan(int stride, int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx) {
-    wgrad3x3_plan_tph(stride == 1 ? 4 : 2, B, OH, OW, N, C, nsplit, per_split, npy, npx);
-}
-
-void wgrad3x3_plan_tph(int TPH, int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx) {
-    *npy = (OH + TPH - 1) / TPH;
-    *npx = (OW + TPW - 1) / TPW;
-    const long long G = (long long)B * (*npy) * (*npx);
-    const long long tiles = (long long)((N + 63) / 64) * ((C + 63) / 64);
-    const long long target = 512;                        // split-K workgroups aimed for
-    long long want = (target + tiles - 1) / tiles;
-    long long maxs = (G + 3) / 4;                       // at least 4 patches per slice
-    if (maxs < 1) maxs = 1;
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    const long long per = (G + want - 1) / want;
-    *per_split = (int)per;
-    *nsplit = (int)((G + per - 1) / per);
-}
-
-size_t wgrad3x3_ws_bytes(int stride, int B, int OH, int OW, int N, int C) {
-    int ns, per, npy, npx;
-    wgrad3x3_plan(stride, B, OH, OW, N, C, &ns, &per, &npy, &npx);
-    size_t bytes = (size_t)ns * N * 9 * C * sizeof(float);
-    if (stride == 2) {                       // the bf16 LDS-DMA kernel (wgrad3x3d.hip) has its own split plan
-        const size_t d = wgrad3x3d_ws_bytes(B, OH, OW, N, C);
-        if (d > bytes) bytes = d;
-    }
-    return bytes;
-}
-
-int launch_wgrad3x3(Wgrad3Args a, int stride, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    int ns, per;
-    wgrad3x3_plan(stride, a.B, a.OH, a.OW, a.N, a.C, &ns, &per, &a.npy, &a.npx);
-    const size_t nout = (size_t)a.N * 9 * a.C;
-    const bool direct = (ns == 1 && reg == 0.f);
-    if (!direct && ws_bytes < (size_t)ns * nout * sizeof(float)) return UNETRIR_EINVAL;
-    a.part = direct ? dw : (float*)ws;
-    a.patches_per_split = per;
+int launch_wgrad3x3(const Wgrad3Args& a, int stride, int nslabs, hipStream_t s) {
     const unsigned tiles = (unsigned)(((a.N + 63) / 64) * ((a.C + 63) / 64));
-    if (stride == 1) hipLaunchKernelGGL((wgrad3x3_kernel<1, 4>), dim3(tiles, ns), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wgrad3x3_kernel<2, 2>), dim3(tiles, ns), dim3(256), 0, s, a);
-    int err = (int)hipGetLastError();
-    if (err || direct) return err;
-    return launch_splitk_reduce((const float*)ws, ns, nout, dw, reg, w, s);
+    if (stride == 1) hipLaunchKernelGGL((wgrad3x3_kernel<1, WG_F32_TPH_S1>), dim3(tiles, nslabs), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((wgrad3x3_kernel<2, WG_F32_TPH_S2>), dim3(tiles, nslabs), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
 }

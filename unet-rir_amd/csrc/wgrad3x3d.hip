@@ -220,8 +220,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3d_bf16_kernel(const Wgrad3Args
     }
 }
 
-namespace {
-void plan_d(int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx) {
+void wgrad3x3d_plan(int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx) {
     *npy = OH / DPH;
     *npx = OW / DPW;
     const long long G = (long long)B * (*npy) * (*npx);
@@ -236,35 +235,17 @@ void plan_d(int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, in
     *per_split = (int)per;
     *nsplit = (int)((G + per - 1) / per);
 }
-}  // namespace
 
-bool wgrad3x3d_applies(const Wgrad3ArgsH& a) {
+bool wgrad3x3d_applies(const Wgrad3ArgsH& a, bool with_ld) {
     const size_t x_bytes = (((size_t)a.IH * a.IW - 1) * a.ldx + a.C) * 2, d_bytes = (((size_t)a.OH * a.OW - 1) * a.lddy + a.N) * 2;
-    return unetrir_cfg().wgrad3x3d && a.pad_t == 0 && a.pad_l == 0 && a.IH == 2 * a.OH && a.IW == 2 * a.OW && a.OH % DPH == 0 &&
-           a.OW % DPW == 0 && (a.C & 7) == 0 && (a.N & 7) == 0 && x_bytes < 0x70000000u && d_bytes < 0x70000000u;
+    return a.pad_t == 0 && a.pad_l == 0 && a.IH == 2 * a.OH && a.IW == 2 * a.OW && a.OH % DPH == 0 && a.OW % DPW == 0 && (a.C & 7) == 0 &&
+           (a.N & 7) == 0 && (!with_ld || (x_bytes < 0x70000000u && d_bytes < 0x70000000u));
 }
 
-size_t wgrad3x3d_ws_bytes(int B, int OH, int OW, int N, int C) {
-    if (OH % DPH || OW % DPW) return 0;
-    int ns, per, npy, npx;
-    plan_d(B, OH, OW, N, C, &ns, &per, &npy, &npx);
-    return (size_t)ns * N * 9 * C * sizeof(float);
-}
-
-// stride-2 3x3 weight gradient; WGRAD3X3R_NOT_TAKEN when this kernel does not take the layer (the caller falls back)
-int launch_wgrad3x3d_bf16(Wgrad3ArgsH a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (!wgrad3x3d_applies(a)) return WGRAD3X3R_NOT_TAKEN;
-    int ns, per;
-    plan_d(a.B, a.OH, a.OW, a.N, a.C, &ns, &per, &a.npy, &a.npx);
-    const size_t nout = (size_t)a.N * 9 * a.C;
-    const bool direct = (ns == 1 && reg == 0.f);
-    if (!direct && ws_bytes < (size_t)ns * nout * sizeof(float)) return WGRAD3X3R_NOT_TAKEN;
-    a.part = direct ? dw : (float*)ws;
-    a.patches_per_split = per;
+// stride-2 3x3 weight gradient
+int launch_wgrad3x3d_bf16(Wgrad3ArgsH a, int nslabs, hipStream_t s) {
     const unsigned tiles = (unsigned)(((a.N + 127) / 128) * ((a.C + 63) / 64));
-    a.xcd_remap = (tiles > 1 && ns % 8 == 0) ? 1 : 0;
-    hipLaunchKernelGGL(wgrad3x3d_bf16_kernel, dim3(tiles, ns), dim3(512), 0, s, a);
-    const int err = (int)hipGetLastError();
-    if (err || direct) return err;
-    return launch_splitk_reduce((const float*)ws, ns, nout, dw, reg, w, s);
+    a.xcd_remap = (tiles > 1 && nslabs % 8 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(wgrad3x3d_bf16_kernel, dim3(tiles, nslabs), dim3(512), 0, s, a);
+    return (int)hipGetLastError();
 }

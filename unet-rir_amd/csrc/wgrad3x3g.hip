@@ -25,7 +25,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 #define LGKM0() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
 namespace {
-constexpr int WTPH = 8, WTPW = 16;
+constexpr int WTPH = WG_ROW_TPH, WTPW = WG_ROW_TPW;
 constexpr int WXH = WTPH + 2, WXW = WTPW + 2;          // 10 x 18 x-patch pixels
 constexpr int WX_INSTR = (WXH * WXW + 7) / 8;          // 23 wave-instructions of 8 pixels x 128 B
 constexpr int WD_INSTR = WTPH * WTPW / 8;              // 16
@@ -317,39 +317,19 @@ __global__ __launch_bounds__(256 * NH, NH == 1 ? 2 : 1) void wgrad3x3g_bf16_kern
     }
 }
 
-static void plan_g(int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx) {
-    const long long target = 512;                        // split-K workgroups aimed for
-    *npy = (OH + WTPH - 1) / WTPH;
-    *npx = (OW + WTPW - 1) / WTPW;
-    const long long G = (long long)B * (*npy) * (*npx);
-    const long long tiles = (long long)((N + 63) / 64) * ((C + 63) / 64);
-    long long want = (target + tiles - 1) / tiles;
-    long long maxs = (G + 3) / 4;
-    if (maxs < 1) maxs = 1;
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    const long long per = (G + want - 1) / want;
-    *per_split = (int)per;
-    *nsplit = (int)((G + per - 1) / per);
+// Heights that are not a multiple of the 8-row patch: the rows past the image are zero-filled DMAs (as the columns past OW); taken
+// while at least 60 % of the patch rows are real (the reference's 144 x 160 geometry: 36 and 18 rows).  One image of x and of dy
+// must lie within the 32-bit buffer offsets.
+bool wgrad3x3g_applies(const Wgrad3ArgsH& a, bool with_ld) {
+    const size_t x_bytes = (((size_t)a.IH * a.IW - 1) * a.ldx + a.C) * 2, d_bytes = (((size_t)a.OH * a.OW - 1) * a.lddy + a.N) * 2;
+    const int rows8 = (a.OH + 7) / 8 * 8;
+    return a.OH * 10 >= rows8 * 6 && (a.C & 7) == 0 && (a.N & 7) == 0 && (!with_ld || (x_bytes < 0x70000000u && d_bytes < 0x70000000u));
 }
 
-// stride-1 3x3 weight gradient; WGRAD3X3R_NOT_TAKEN when this kernel does not take the layer (the caller falls back)
-int launch_wgrad3x3g_bf16(Wgrad3ArgsH a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    const bool on = unetrir_cfg().wgrad3x3g != 0;
-    const size_t x_bytes = (((size_t)a.IH * a.IW - 1) * a.ldx + a.C) * 2, d_bytes = (((size_t)a.OH * a.OW - 1) * a.lddy + a.N) * 2;
-    // heights that are not a multiple of the 8-row patch: the rows past the image are zero-filled DMAs (as the columns past OW);
-    // taken while at least 60 % of the patch rows are real (the reference's 144 x 160 geometry: 36 and 18 rows)
-    const int rows8 = (a.OH + 7) / 8 * 8;
-    if (!on || a.OH * 10 < rows8 * 6 || x_bytes >= 0x70000000u || d_bytes >= 0x70000000u || (a.C & 7) || (a.N & 7)) return WGRAD3X3R_NOT_TAKEN;
-    int ns, per;
-    plan_g(a.B, a.OH, a.OW, a.N, a.C, &ns, &per, &a.npy, &a.npx);
-    const int nh = ns >= 2 ? 2 : 1;                       // two split-K quartets per workgroup share one partial slab
-    ns = (ns + nh - 1) / nh;                             // partial slabs = workgroups along the split dimension
-    const size_t nout = (size_t)a.N * 9 * a.C;
-    const bool direct = (ns == 1 && reg == 0.f);
-    if (!direct && ws_bytes < (size_t)ns * nout * sizeof(float)) return WGRAD3X3R_NOT_TAKEN;
-    a.part = direct ? dw : (float*)ws;
-    a.patches_per_split = per;
+// stride-1 3x3 weight gradient: ns partial slabs = workgroups along the split dimension, each with two split-K quartets that share
+// its slab unless one slice covers every patch (plan_wgrad counts the slabs so)
+int launch_wgrad3x3g_bf16(Wgrad3ArgsH a, int ns, hipStream_t s) {
+    const int nh = (long long)a.B * a.npy * a.npx > a.patches_per_split ? 2 : 1;
     const unsigned tiles = (unsigned)(((a.N + 63) / 64) * ((a.C + 63) / 64));
     a.xcd_remap = (tiles > 1 && ns % 8 == 0 && !UNETRIR_ABL(UNETRIR_ABL_HOST(), 512)) ? 1 : 0;
 #ifdef UNETRIR_ABLATIONS
@@ -362,7 +342,5 @@ int launch_wgrad3x3g_bf16(Wgrad3ArgsH a, float* dw, float reg, const float* w, v
 #endif
     if (nh == 2) hipLaunchKernelGGL(wgrad3x3g_bf16_kernel<2>, dim3(tiles, ns), dim3(512), 0, s, a, UNETRIR_ABL_HOST());
     else hipLaunchKernelGGL(wgrad3x3g_bf16_kernel<1>, dim3(tiles, ns), dim3(256), 0, s, a, UNETRIR_ABL_HOST());
-    const int err = (int)hipGetLastError();
-    if (err || direct) return err;
-    return launch_splitk_reduce((const float*)ws, ns, nout, dw, reg, w, s);
+    return (int)hipGetLastError();
 }

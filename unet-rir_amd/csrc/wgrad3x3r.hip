@@ -17,7 +17,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_r;
 
-#define RW_TPW 16
+#define RW_TPW WG_ROW_TPW
 #define RW_LD 96              // LDS pixel stride, elements (192 B)
 
 template <int TPH>
@@ -150,37 +150,12 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3r_bf16_kernel(const Wgrad3Args
     }
 }
 
-// split-K plan for TPH x 16 patches: about `target` workgroups, at least 4 patches per slice
-static void plan_r(int TPH, int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx) {
-    const long long target = 512;                        // split-K workgroups aimed for
-    *npy = (OH + TPH - 1) / TPH;
-    *npx = (OW + RW_TPW - 1) / RW_TPW;
-    const long long G = (long long)B * (*npy) * (*npx);
-    const long long tiles = (long long)((N + 63) / 64) * ((C + 63) / 64);
-    long long want = (target + tiles - 1) / tiles;
-    long long maxs = (G + 3) / 4;
-    if (maxs < 1) maxs = 1;
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    const long long per = (G + want - 1) / want;
-    *per_split = (int)per;
-    *nsplit = (int)((G + per - 1) / per);
-}
+// heights in whole 8-row patches
+bool wgrad3x3r_applies(const Wgrad3ArgsH& a) { return a.OH % WG_ROW_TPH == 0; }
 
-// stride-1 3x3 weight gradient; returns WGRAD3X3R_NOT_TAKEN when this kernel does not take the layer (the caller falls back)
-int launch_wgrad3x3r_bf16(Wgrad3ArgsH a, float* dw, float reg, const float* w, void* ws, size_t ws_bytes, hipStream_t s) {
-    const bool on = unetrir_cfg().wgrad3x3r != 0;
-    if (!on || a.OH % 8 != 0) return WGRAD3X3R_NOT_TAKEN;
-    int ns, per;
-    plan_r(8, a.B, a.OH, a.OW, a.N, a.C, &ns, &per, &a.npy, &a.npx);
-    const size_t nout = (size_t)a.N * 9 * a.C;
-    const bool direct = (ns == 1 && reg == 0.f);
-    if (!direct && ws_bytes < (size_t)ns * nout * sizeof(float)) return WGRAD3X3R_NOT_TAKEN;
-    a.part = direct ? dw : (float*)ws;
-    a.patches_per_split = per;
+// stride-1 3x3 weight gradient
+int launch_wgrad3x3r_bf16(const Wgrad3ArgsH& a, int nslabs, hipStream_t s) {
     const unsigned tiles = (unsigned)(((a.N + 63) / 64) * ((a.C + 63) / 64));
-    hipLaunchKernelGGL((wgrad3x3r_bf16_kernel<8>), dim3(tiles, ns), dim3(256), 0, s, a);
-    const int err = (int)hipGetLastError();
-    if (err || direct) return err;
-    return launch_splitk_reduce((const float*)ws, ns, nout, dw, reg, w, s);
+    hipLaunchKernelGGL((wgrad3x3r_bf16_kernel<WG_ROW_TPH>), dim3(tiles, nslabs), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
 }
