@@ -479,6 +479,26 @@ int unetrir_stft_features_f32(const float* wav, int B, int T, int n_fft, int win
 int unetrir_istft_features_f32(const float* feat, int B, int H, int W, int n_bins, int n_frames, int n_fft, int win_length,
                                int hop_length, int denormalize, float* wav, unetrir_stream_t stream);
 
+/* ---- scoring of generated impulse responses: the loss block of the evaluation loop (rir_generation.py:185-225) and its per-room
+ *      bookkeeping (:227-290, :311-357), on the device and without a read-back.
+ *
+ * unetrir_eval_metrics_f32: pred / target fp32 NCHW [B][2][H][W] (plane 0 magnitude, plane 1 phase, normalised, padding included),
+ * phase_ref nullable [B][2][H][W] = the network INPUT (diff_gen, :173-176, :190-193: the scored phase is pred + phase_ref, plane 1
+ * of each, summed in fp32), wav_pred / wav_true fp32 [B][T], nullable as a pair.  out fp64 [B][7]:
+ *   0 mean (target - pred)^2 over both planes, always the raw pred (:197)      1 the same over plane 0 (:195)
+ *   2 mean over plane 1 of 1 - cos(2 pi (target - p)) (:36-40, :196)            3 20 log10(|pred0 - target0| / |target0|) (:203-205)
+ *   4 mean (wav_true - wav_pred)^2 (:215)   5 the same over the first min(n50, T) samples (:218)
+ *   6 20 log10(|wav_pred - wav_true| / |wav_true|) (:221-223);   4-6 are NaN without waveforms.
+ * fp64 accumulation in a fixed order: the same bits in every run, and a sample's row does not depend on its batch.  A zero
+ * numerator gives -inf dB (the reference raises), a zero denominator +inf, both NaN.
+ *
+ * unetrir_eval_accumulate: folds out [B][7] into acc fp64 [(G+1)][8] (in/out; row 0 global, rows 1..G the groups; columns 0-6
+ * running sums of the figures - dB figures are summed as dB, :205-207, :316-317 - column 7 the sample count).  group int32 [B]:
+ * the room of each sample, 0..G-1; any other value counts in the global row only.  One workgroup, batch walked in index order. */
+int unetrir_eval_metrics_f32(const float* pred, const float* target, const float* phase_ref, int B, int H, int W,
+                             const float* wav_pred, const float* wav_true, int T, int n50, double* out, unetrir_stream_t stream);
+int unetrir_eval_accumulate(const double* out, const int* group, int B, int G, double* acc, unetrir_stream_t stream);
+
 /* ---- glue that would otherwise be framework kernels inside the step.
  * bn_inference_affine: BatchNormalization with training=False (rir_generation.py:165): scale = gamma * rsqrt(moving_var + eps),
  *   shift = beta - moving_mean * scale into affine[2*C] (gamma / beta NULL = 1 / 0), consumed by unetrir_bn_apply_*.

@@ -1,0 +1,95 @@
+"""Score a trained model on a test set, on the device, and write the reference's three report files
+(rir_generation.py:160-532 -> unet_rir_amd.Evaluator + write_report).
+
+    python scripts/evaluate.py --load SAVED_MODEL_DIR --data BATCH_DIR --out REPORT_DIR [--name unet] [--diff-gen]
+    python scripts/evaluate.py --checkpoint CKPT_DIR --filters 32 --kernels 3 --data BATCH_DIR --out REPORT_DIR
+    python scripts/evaluate.py --synthetic 8 --out REPORT_DIR            # no dataset, no checkpoint: random weights and data
+
+--load         a folder written by `UNet.save` / `ResAE.save` / `Autoencoder.save` (--arch picks the class)
+--checkpoint   a `CheckpointManager` directory; the latest checkpoint is restored into a U-Net built from --filters / --kernels
+--data         a directory of .npz files, one test batch each: spec_in, spec_out fp32 [B, H, W, 2] (or [B, 2, H, W]), emb int
+               [B, 2, 16], wav_true fp32 [B, T], room = B room names (or indices into evaluate.ROOMS)
+--synthetic N  N batches of `synthetic_batches`, which yields no waveforms: wav_true is the reconstruction of spec_out
+"""
+import argparse
+import glob
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import unet_rir_amd as U
+from unet_rir_amd.features import PostProcess
+
+
+def build_model(a, dev):
+    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder}[a.arch]
+    if a.load:
+        return cls.load(a.load, batch_size=a.batch, device=dev)
+    if a.arch != "unet":
+        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net; use --load for the autoencoders")
+    m = U.UNet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, kernels=a.kernels, batch_size=a.batch, device=dev,
+               dropout=False)
+    if a.checkpoint:
+        mgr = U.CheckpointManager(U.Trainer(m.engine, dropout=False), a.checkpoint)
+        if mgr.latest_checkpoint is None:
+            raise SystemExit(f"no checkpoint in {a.checkpoint}")
+        mgr.restore()
+        print("restored", mgr.latest_checkpoint)
+    return m
+
+
+def file_batches(folder, dev):
+    files = sorted(glob.glob(os.path.join(folder, "*.npz")))
+    if not files:
+        raise SystemExit(f"no .npz batches in {folder}")
+    for f in files:
+        with np.load(f) as z:
+            room = z["room"]
+            room = [str(r) for r in room] if room.dtype.kind in "US" else torch.from_numpy(room.astype(np.int32)).to(dev)
+            yield (torch.from_numpy(z["spec_in"]).float().to(dev), torch.from_numpy(z["emb"]).to(dev),
+                   torch.from_numpy(z["spec_out"]).float().to(dev), torch.from_numpy(z["wav_true"]).float().to(dev), room)
+
+
+def synthetic(a, dev):
+    post = PostProcess()
+    for k, (spec_in, emb, spec_out) in enumerate(U.synthetic_batches(a.synthetic, a.batch, a.height, a.width, dev)):
+        room = [U.evaluate.ROOMS[(k * a.batch + j) % len(U.evaluate.ROOMS)] for j in range(a.batch)]
+        yield spec_in, emb, spec_out, post.post_process(spec_out).clone(), room
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--load")
+    ap.add_argument("--checkpoint")
+    ap.add_argument("--arch", choices=("unet", "resae", "ae"), default="unet")
+    ap.add_argument("--filters", type=int, default=32)
+    ap.add_argument("--kernels", type=int, default=3)
+    ap.add_argument("--height", type=int, default=144)
+    ap.add_argument("--width", type=int, default=160)
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--data")
+    ap.add_argument("--synthetic", type=int, default=0)
+    ap.add_argument("--diff-gen", action="store_true")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--name", default="unet")
+    a = ap.parse_args()
+    if bool(a.data) == bool(a.synthetic):
+        raise SystemExit("give exactly one of --data and --synthetic")
+    if not torch.cuda.is_available():
+        raise SystemExit("evaluation runs on the GPU; there is none here")
+    dev = torch.device("cuda:0")
+    model = build_model(a, dev)
+    ev = U.Evaluator(model, diff_gen=a.diff_gen)
+    for batch in (file_batches(a.data, dev) if a.data else synthetic(a, dev)):
+        ev.update(*batch)
+    res = ev.result()
+    for p in U.write_report(res, a.out, a.name):
+        print("wrote", p)
+    print("samples", res["n"][0], " ".join(f"{m}={res[m][0]:.6g}" for m in U.evaluate.METRICS))
+
+
+if __name__ == "__main__":
+    main()

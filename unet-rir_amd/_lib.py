@@ -161,6 +161,9 @@ _SIGS = {
                                             c_f32p, C.c_int, C.c_int, c_stream]),
     "unetrir_istft_features_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, c_f32p, c_stream]),
+    "unetrir_eval_metrics_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int,
+                                           C.c_void_p, c_stream]),
+    "unetrir_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
     "unetrir_head6x6_dgrad_supported": (C.c_int, [C.c_int, C.c_int]),
     "unetrir_head6x6_dgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int,
                                              c_stream]),

@@ -845,6 +845,20 @@ int unetrir_stage_h2d(int n, const void* const* src, void* const* pinned, void* 
     return 0;
 }
 
+// ---- scoring of generated impulse responses (evalmetrics.hip): every argument is checked before the device is touched
+int unetrir_eval_metrics_f32(const float* pred, const float* target, const float* phase_ref, int B, int H, int W,
+                             const float* wav_pred, const float* wav_true, int T, int n50, double* out, unetrir_stream_t stream) {
+    if (!pred || !target || !out || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
+    if ((wav_pred == nullptr) != (wav_true == nullptr)) return UNETRIR_EINVAL;          // the waveforms come as a pair
+    if (wav_pred && (T <= 0 || n50 <= 0)) return UNETRIR_EINVAL;
+    return launch_eval_metrics(pred, target, phase_ref, B, H, W, wav_pred, wav_true, T, n50, out, (hipStream_t)stream);
+}
+
+int unetrir_eval_accumulate(const double* out, const int* group, int B, int G, double* acc, unetrir_stream_t stream) {
+    if (!out || !group || !acc || B <= 0 || G < 1 || G > (0x7fffffff >> 3) - 1) return UNETRIR_EINVAL;
+    return launch_eval_accumulate(out, group, B, G, acc, (hipStream_t)stream);
+}
+
 int unetrir_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_on = on != 0;

@@ -213,3 +213,8 @@ struct PwArgs {
 bool pw1x1_applies(const PwArgs& a);
 long long pw1x1_colstat_rows(const PwArgs& a);
 int launch_pw1x1_bf16(const PwArgs& a, hipStream_t s);   // H, W = coarse (input) grid; output 2H x 2W
+
+// scoring of generated impulse responses (evalmetrics.hip); arguments are validated by the entry points in api.hip
+int launch_eval_metrics(const float* pred, const float* target, const float* phase_ref, int B, int H, int W, const float* wav_pred,
+                        const float* wav_true, int T, int n50, double* out, hipStream_t s);
+int launch_eval_accumulate(const double* out, const int* group, int B, int G, double* acc, hipStream_t s);

@@ -116,7 +116,7 @@ class PostProcess:
         self.waveform = None
 
     def post_process(self, feature, vector=None, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH, hop_length=HOP_LENGTH,
-                     sr=SAMPLE_RATE, nhwc=None):
+                     sr=SAMPLE_RATE, nhwc=None, out=None):
         if not isinstance(feature, torch.Tensor) or not feature.is_cuda:
             raise ValueError("features must be CUDA tensors (there is no CPU path)")
         f = feature
@@ -128,7 +128,8 @@ class PostProcess:
         if nhwc:
             f = f.permute(0, 3, 1, 2)
         f = f.contiguous().float()
-        wav = torch.empty((f.shape[0], hop_length * (des_shape[1] - 1)), dtype=torch.float32, device=f.device)
+        wav = out if out is not None else torch.empty((f.shape[0], hop_length * (des_shape[1] - 1)), dtype=torch.float32,
+                                                      device=f.device)
         ops.istft_features(f, wav, des_shape[0], des_shape[1], n_fft, win_length, hop_length, denormalize=True)
         self.waveform = wav[0] if single else wav
         return self.waveform

@@ -501,6 +501,50 @@ def istft_features(feat, wav, n_bins, n_frames, n_fft=256, win_length=128, hop_l
                                                 int(denormalize), _p(wav), _stream()), "istft_features")
 
 
+def _f32c(t, shape, what, like):
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or t.device != like.device:
+        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on {like.device}")
+
+
+def eval_metrics(pred, target, out, wav_pred=None, wav_true=None, phase_ref=None, n50=2400):
+    """pred / target fp32 [B, 2, H, W] (+ phase_ref, the network input, for diff_gen; + the waveform pair fp32 [B, T]) -> out fp64
+    [B, 7]: the seven per-sample figures of rir_generation.py:185-225 in one launch (include/unetrir.h)."""
+    if not pred.is_cuda or pred.dim() != 4 or pred.shape[1] != 2:
+        raise ValueError("eval_metrics: pred must be a CUDA tensor [B, 2, H, W]")
+    B, _, H, W = pred.shape
+    _f32c(pred, pred.shape, "pred", pred)
+    _f32c(target, pred.shape, "target", pred)
+    if phase_ref is not None:
+        _f32c(phase_ref, pred.shape, "phase_ref", pred)
+    if (wav_pred is None) != (wav_true is None):
+        raise ValueError("eval_metrics: wav_pred and wav_true come as a pair")
+    T = 0
+    if wav_pred is not None:
+        if wav_pred.dim() != 2 or wav_pred.shape[0] != B:
+            raise ValueError("eval_metrics: waveforms must be [B, T]")
+        T = wav_pred.shape[1]
+        _f32c(wav_pred, (B, T), "wav_pred", pred)
+        _f32c(wav_true, (B, T), "wav_true", pred)
+    if out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (B, 7) or out.device != pred.device:
+        raise ValueError(f"eval_metrics: out must be a contiguous float64 [{B}, 7] tensor on {pred.device}")
+    check(_lib.lib().unetrir_eval_metrics_f32(_p(pred), _p(target), _p(phase_ref), B, H, W, _p(wav_pred), _p(wav_true), T, int(n50),
+                                              _p(out), _stream()), "eval_metrics")
+
+
+def eval_accumulate(out, group, acc):
+    """Fold out fp64 [B, 7] into the running sums acc fp64 [G + 1, 8] (row 0 global, rows 1..G the groups; column 7 the count);
+    group int32 [B], values outside 0..G-1 count in the global row only (rir_generation.py:227-290)."""
+    if not out.is_cuda or out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != 7 or not out.is_contiguous():
+        raise ValueError("eval_accumulate: out must be a contiguous float64 CUDA tensor [B, 7]")
+    B = out.shape[0]
+    if group.dtype != torch.int32 or tuple(group.shape) != (B,) or not group.is_contiguous() or group.device != out.device:
+        raise ValueError(f"eval_accumulate: group must be a contiguous int32 [{B}] tensor on {out.device}")
+    if acc.dtype != torch.float64 or acc.dim() != 2 or acc.shape[0] < 2 or acc.shape[1] != 8 or not acc.is_contiguous() or \
+            acc.device != out.device:
+        raise ValueError(f"eval_accumulate: acc must be a contiguous float64 [G + 1, 8] tensor on {out.device}")
+    check(_lib.lib().unetrir_eval_accumulate(_p(out), _p(group), B, acc.shape[0] - 1, _p(acc), _stream()), "eval_accumulate")
+
+
 def sigmoid_loss(logits: Act, target, alpha, inv_norm, pred, dlogits: Act, loss_out, ws: Workspace, phase_ref=None, phase_weight=None):
     """sigmoid head (dl_models/u_net.py:249) + compute_loss (main_training.py:203-231) + dL/dlogits.
     phase_ref: the network input [B,2,H,W] (the `diff_loss` switch, main_training.py:214-217); phase_weight: fp32 [W] column
