@@ -292,7 +292,11 @@ int unetrir_dropout_mask_dev_f32(float* mask, long long n, float p, unsigned lon
  *      statistics / weight gradients / master weights stay fp32.  Channel counts and pixel strides are multiples of 8
  *      (16-byte rows).  Same call sites as the _f32 entry points above.  The weight gradient has dedicated bf16 kernels
  *      for 3x3 and 1x1 layers; other kernel sizes (kernels = 6, the reference's constructor default) run on the tap-table
- *      weight-gradient kernel with bf16 operand loads (fp32 MFMA arithmetic); the Dense layers stay fp32. */
+ *      weight-gradient kernel with bf16 operand loads (fp32 MFMA arithmetic); the Dense layers stay fp32.
+ *      `addend` of the forward / data-gradient entry points (here and in the _packed and _colstat forms): the convolution result
+ *      (+ bias) is ROUNDED to bf16 first, the addend is added to that rounded value and the sum is rounded again -
+ *      y = bf16(bf16(conv + bias) + addend), what storing the convolution and adding afterwards would give, in every kernel;
+ *      addend may be the output itself (in-place accumulation). */
 int unetrir_conv2d_fwd_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* w,
                             const float* bias, const unetrir_bf16* addend, int ldadd, unetrir_bf16* y, int ldy,
                             unetrir_stream_t stream);

@@ -1,11 +1,17 @@
 """Parity of every HIP kernel (called through the C ABI) against the CPU oracle on seeded inputs.
-fp32 tolerances are stated per test; the oracle side runs in fp64."""
+fp32 tolerances are stated per test; the oracle side runs in fp64.
+
+The convolution tests take their inputs in two kinds (parameter `data`): "uniform" - uniform(-1, 1) values, compared within a
+tolerance - and "int" - the integer data set of tests/exact_data.py, for which the stored result is fully determined (fp32
+accumulation of integers below 2^24 is exact in any order), so EVERY element is compared for equality with the oracle, under
+every kernel-selection switch set that can route the layer to another kernel."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
+import exact_data as X
 from oracle import detrand, torch_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +21,8 @@ pytestmark = pytest.mark.gpu
 def U():
     import unet_rir_amd
     unet_rir_amd._lib.lib()
-    return unet_rir_amd
+    yield unet_rir_amd
+    print("\nexact comparisons of this process so far:", X.STATS)
 
 
 DEV = "cuda:0"
@@ -57,27 +64,69 @@ CONV_CASES = [
 ]
 
 
-def conv_data(case, dtype=torch.float64):
+def rand(name, shape, data, role="act", lo=-1, hi=1):
+    """fp64 test tensor of the given kind: uniform(lo, hi), or the integers exact_data draws for the tensor's role
+    ("act": activations and gradients, "kernel", "bias", "addend")."""
+    if data == "int":
+        return dict(act=X.acts, kernel=X.kernels, bias=X.biases, addend=X.addends)[role](name, shape)
+    return torch.tensor(detrand.uniform(name, tuple(shape), lo, hi, np.float64))
+
+
+def set_switches(ops, *switch_sets):
+    """All switches at their defaults (1) with the given sets on top, flipped with the device idle; the tile tickets of the
+    persistent kernels are cleared whenever dyn_tiles changes (include/unetrir.h: a stale ticket would skip tiles or wait)."""
+    torch.cuda.synchronize()
+    old = ops.get_config()
+    new = {n: 1 for n in old}
+    for sw in switch_sets:
+        new.update(sw)
+    ops.set_config(**new)
+    if new["dyn_tiles"] != old["dyn_tiles"]:
+        ops.reset_tile_tickets()
+
+
+def exact_act(got_nhwc, want_nchw, what, tile=(16, 32)):
+    """Every element of a device activation [B,H,W,C] against the expected NCHW tensor (fp64, host or device)."""
+    X.assert_exact(got_nhwc, want_nchw.permute(0, 2, 3, 1), what, tile=tile)
+
+
+def conv_data(case, dtype=torch.float64, data="uniform"):
     B, H, W, Ci, Co, k, s = case
+    if data == "int":
+        return (X.acts(f"x{case}", (B, Ci, H, W)).to(dtype), X.kernels(f"w{case}", (k, k, Ci, Co)).to(dtype),
+                X.biases(f"b{case}", (Co,)).to(dtype))
     x = torch.tensor(detrand.uniform(f"x{case}", (B, Ci, H, W), -1, 1, np.float64), dtype=dtype)
     w = torch.tensor(detrand.uniform(f"w{case}", (k, k, Ci, Co), -1, 1, np.float64), dtype=dtype)
     b = torch.tensor(detrand.uniform(f"b{case}", (Co,), -1, 1, np.float64), dtype=dtype)
     return x, w, b
 
 
-@pytest.mark.parametrize("case", CONV_CASES)
-def test_conv2d_fwd_dgrad_wgrad(U, case):
+def cmp32(exact, got, want, tol, what, nchw=False):
+    """fp32 outputs: within tol of the tensor's scale (uniform data), or equal in every element (integer data: the fp32 MFMA is an
+    fmaf chain and the split-K reductions are fp32 sums, all of integers below 2^24)."""
+    if not exact:
+        return close(got, want, tol, what)
+    X.assert_exact(got, want.permute(0, 2, 3, 1) if nchw else want, what, tile=(8, 32) if nchw else None)
+
+
+@X.parametrize_kinds("case", CONV_CASES)
+def test_conv2d_fwd_dgrad_wgrad(U, case, data):
     ops = U.ops
+    exact = data == "int"
     B, H, W, Ci, Co, k, s = case
-    x, w, b = conv_data(case)
+    x, w, b = conv_data(case, data=data)
     x.requires_grad_(True); w.requires_grad_(True)
     y = R.conv2d_same(x, w, b, s)
     Ho, Wo = y.shape[2], y.shape[3]
-    add = torch.tensor(detrand.uniform(f"a{case}", (B, Co, Ho, Wo), -1, 1, np.float64))
-    gy = torch.tensor(detrand.uniform(f"g{case}", (B, Co, Ho, Wo), -1, 1, np.float64))
+    add = rand(f"a{case}", (B, Co, Ho, Wo), data, "addend")
+    gy = rand(f"g{case}", (B, Co, Ho, Wo), data)
     (y * gy).sum().backward()
     K = max(Ci * k * k, 1)
     tol = 2e-6 * math.sqrt(K) + 1e-6
+    if exact:
+        X.check_exactness_conditions({"x": (x.detach(), False), "w": (w.detach(), False), "bias": (b, False), "addend": (add, False), "dy": (gy, False)},
+                                     X.conv_abs_bound(k * k * max(Ci, Co)), what=f"f32 {case}")
+        X.check_exactness_conditions({}, B * Ho * Wo * 9 + 1, quantum=0.5, what=f"f32 wgrad {case}")
 
     g = ops.geom(B, H, W, Ci, Co, k, s)
     xa = ops.Act(to_nhwc_buf(x.detach(), Ci + 8, 4, DEV), 4, Ci)          # offset view: concat-style input
@@ -87,7 +136,7 @@ def test_conv2d_fwd_dgrad_wgrad(U, case):
     adda = ops.Act(to_nhwc_buf(add, Co, 0, DEV))
     ops.conv2d_fwd(g, xa, w_ohwi, bias, ya, adda)
     torch.cuda.synchronize()
-    close(ya.dense().permute(0, 3, 1, 2), y.detach() + add, tol, "fwd")
+    cmp32(exact, ya.dense() if exact else ya.dense().permute(0, 3, 1, 2), y.detach() + add, tol, "fwd", nchw=exact)
     assert float(ya.base[..., Co:].min()) == 555.0      # pad channels untouched
 
     # dgrad
@@ -99,32 +148,38 @@ def test_conv2d_fwd_dgrad_wgrad(U, case):
     dxa = ops.Act(torch.full((B, H, W, Ci), 333.0, device=DEV))
     ops.conv2d_dgrad(g, gya, wt, dxa)
     torch.cuda.synchronize()
-    close(dxa.dense().permute(0, 3, 1, 2), x.grad, 2e-6 * math.sqrt(Co * k * k) + 1e-6, "dgrad")
+    cmp32(exact, dxa.dense() if exact else dxa.dense().permute(0, 3, 1, 2), x.grad, 2e-6 * math.sqrt(Co * k * k) + 1e-6, "dgrad", nchw=exact)
 
     # wgrad (+ l2 regulariser gradient 2*coef*w folded into the reduction)
     ws = ops.Workspace(DEV)
     dw = torch.full((Co, k, k, Ci), 111.0, device=DEV)
-    reg = 0.002
+    reg = X.REG if exact else 0.002
     ops.conv2d_wgrad(g, xa, gya, dw, ws, reg=reg, w=w_ohwi)
     torch.cuda.synchronize()
     exp = (w.grad + reg * w.detach()).permute(3, 0, 1, 2)
-    close(dw, exp, 2e-6 * math.sqrt(B * Ho * Wo) + 1e-6, "wgrad")
+    cmp32(exact, dw, exp, 2e-6 * math.sqrt(B * Ho * Wo) + 1e-6, "wgrad")
 
 
 CONVT_CASES = [(2, 6, 5, 16, 8, 3), (1, 4, 4, 64, 32, 3), (1, 5, 6, 8, 16, 6), (2, 3, 3, 128, 64, 3),
                (2, 12, 40, 48, 72, 3), (1, 16, 32, 64, 64, 3)]      # the last two take the fused parity-class kernel
 
 
-@pytest.mark.parametrize("case", CONVT_CASES)
-def test_conv2d_transpose(U, case):
+@X.parametrize_kinds("case", CONVT_CASES)
+def test_conv2d_transpose(U, case, data):
     ops = U.ops
+    exact = data == "int"
     B, H, W, Ci, Co, k = case
-    x = torch.tensor(detrand.uniform(f"tx{case}", (B, Ci, H, W), -1, 1, np.float64), requires_grad=True)
-    w = torch.tensor(detrand.uniform(f"tw{case}", (k, k, Co, Ci), -1, 1, np.float64), requires_grad=True)  # HWOI
-    b = torch.tensor(detrand.uniform(f"tb{case}", (Co,), -1, 1, np.float64))
+    x = rand(f"tx{case}", (B, Ci, H, W), data).requires_grad_(True)
+    w = rand(f"tw{case}", (k, k, Co, Ci), data, "kernel").requires_grad_(True)  # HWOI
+    b = rand(f"tb{case}", (Co,), data, "bias")
     y = R.conv2d_transpose_same(x, w, b, 2)
-    gy = torch.tensor(detrand.uniform(f"tg{case}", tuple(y.shape), -1, 1, np.float64))
+    gy = rand(f"tg{case}", tuple(y.shape), data)
     (y * gy).sum().backward()
+    reg = X.REG if exact else 0.002
+    if exact:
+        X.check_exactness_conditions({"x": (x.detach(), False), "w": (w.detach(), False), "bias": (b, False), "dy": (gy, False)},
+                                     X.conv_abs_bound(k * k * max(Ci, Co), has_addend=False), what=f"f32 convT {case}")
+        X.check_exactness_conditions({}, B * H * W * k * k + 1, quantum=0.5, what=f"f32 convT wgrad {case}")
 
     g = ops.geom(B, H, W, Ci, Co, k, 2)
     w_prim = w.detach().permute(3, 0, 1, 2).contiguous().float().to(DEV)       # [Ci][kh][kw][Co]
@@ -134,20 +189,20 @@ def test_conv2d_transpose(U, case):
     ya = ops.Act(torch.full((B, 2 * H, 2 * W, 2 * Co), 555.0, device=DEV), Co, Co)   # upper half of a concat buffer
     ops.conv2d_transpose_fwd(g, xa, wt, b.float().to(DEV), ya)
     torch.cuda.synchronize()
-    close(ya.dense().permute(0, 3, 1, 2), y.detach(), 2e-6 * math.sqrt(Ci * k * k) + 1e-6, "convT fwd")
+    cmp32(exact, ya.dense() if exact else ya.dense().permute(0, 3, 1, 2), y.detach(), 2e-6 * math.sqrt(Ci * k * k) + 1e-6, "convT fwd", nchw=exact)
     assert float(ya.base[..., :Co].min()) == 555.0
 
     gya = ops.Act(to_nhwc_buf(gy, 2 * Co, Co, DEV), Co, Co)
     dxa = ops.Act(torch.full((B, H, W, Ci), 333.0, device=DEV))
     ops.conv2d_transpose_dgrad(g, gya, w_prim, dxa)
     torch.cuda.synchronize()
-    close(dxa.dense().permute(0, 3, 1, 2), x.grad, 2e-6 * math.sqrt(Co * k * k) + 1e-6, "convT dgrad")
+    cmp32(exact, dxa.dense() if exact else dxa.dense().permute(0, 3, 1, 2), x.grad, 2e-6 * math.sqrt(Co * k * k) + 1e-6, "convT dgrad", nchw=exact)
 
     ws = ops.Workspace(DEV)
     dw = torch.full((Ci, k, k, Co), 111.0, device=DEV)
-    ops.conv2d_transpose_wgrad(g, xa, gya, dw, ws, reg=0.002, w=w_prim)
+    ops.conv2d_transpose_wgrad(g, xa, gya, dw, ws, reg=reg, w=w_prim)
     torch.cuda.synchronize()
-    close(dw, (w.grad + 0.002 * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * H * W) + 1e-6, "convT wgrad")
+    cmp32(exact, dw, (w.grad + reg * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * H * W) + 1e-6, "convT wgrad")
 
 
 @pytest.mark.parametrize("shape", [(2, 12, 10, 16), (3, 7, 5, 40), (1, 4, 4, 1024), (2, 33, 31, 8)])
@@ -271,23 +326,28 @@ def test_embedding_adam_misc(U):
     assert torch.equal(pa.base[..., :2].cpu(), nchw.permute(0, 2, 3, 1)) and float(pa.base[..., 2:].abs().max()) == 0
 
 
-@pytest.mark.parametrize("B,H,W,Cc", [(2, 20, 37, 16), (1, 32, 32, 64), (3, 16, 16, 32)])
-def test_head6x6_direct(U, B, H, W, Cc):
+@X.parametrize_kinds("B,H,W,Cc", [(2, 20, 37, 16), (1, 32, 32, 64), (3, 16, 16, 32)])
+def test_head6x6_direct(U, B, H, W, Cc, data):
     """The direct (non-MFMA) head kernels against the oracle: Conv2D(2,(6,6),'same') forward and weight gradient."""
     ops = U.ops
-    x = torch.tensor(detrand.uniform(f"hx{B,H,W,Cc}", (B, Cc, H, W), -1, 1, np.float64))
-    w = torch.tensor(detrand.uniform(f"hw{Cc}", (6, 6, Cc, 2), -1, 1, np.float64), requires_grad=True)
-    b = torch.tensor(detrand.uniform("hb", (2,), -1, 1, np.float64))
+    exact = data == "int"
+    x = rand(f"hx{B,H,W,Cc}", (B, Cc, H, W), data)
+    w = rand(f"hw{Cc}", (6, 6, Cc, 2), data, "kernel").requires_grad_(True)
+    b = rand("hb", (2,), data, "bias")
     y = R.conv2d_same(x, w, b, 1)
-    gy = torch.tensor(detrand.uniform(f"hg{B,H,W}", (B, 2, H, W), -1, 1, np.float64))
+    gy = rand(f"hg{B,H,W}", (B, 2, H, W), data)
     (y * gy).sum().backward()
+    if exact:
+        X.check_exactness_conditions({"x": (x, False), "w": (w.detach(), False), "bias": (b, False), "dy": (gy, False)},
+                                     max(X.conv_abs_bound(36 * Cc, has_addend=False), B * H * W * 9), what=f"f32 head {B, H, W, Cc}")
     xa = ops.Act(to_nhwc_buf(x, Cc + 4, 4, DEV), 4, Cc)
     w4 = torch.zeros((4, 6, 6, Cc), device=DEV); w4[:2] = w.detach().permute(3, 0, 1, 2).float().to(DEV)
     b4 = torch.zeros(4, device=DEV); b4[:2] = b.float().to(DEV)
     ya = ops.Act(torch.full((B, H, W, 4), 5.0, device=DEV))
     ops.head6x6_fwd(xa, w4, b4, ya)
     torch.cuda.synchronize()
-    close(ya.dense()[..., :2].permute(0, 3, 1, 2), y.detach(), 2e-6 * math.sqrt(36 * Cc) + 1e-6, "head fwd")
+    cmp32(exact, ya.dense()[..., :2] if exact else ya.dense()[..., :2].permute(0, 3, 1, 2), y.detach(), 2e-6 * math.sqrt(36 * Cc) + 1e-6, "head fwd",
+          nchw=exact)
     assert float(ya.dense()[..., 2:].abs().max()) == 0.0
     gya = ops.Act(to_nhwc_buf(gy, 4, 0, DEV), 0, 4)
     gya.base[..., 2:] = 0
@@ -295,7 +355,7 @@ def test_head6x6_direct(U, B, H, W, Cc):
     ws = ops.Workspace(DEV)
     ops.head6x6_wgrad(xa, gya, dw, ws)
     torch.cuda.synchronize()
-    close(dw[:2], w.grad.permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * H * W) + 1e-6, "head wgrad")
+    cmp32(exact, dw[:2], w.grad.permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * H * W) + 1e-6, "head wgrad")
     assert float(dw[2:].abs().max()) == 0.0
 
 
@@ -334,6 +394,7 @@ BF16_CONV_CASES = [
     (2, 21, 60, 64, 64, 3, 1), (3, 64, 96, 64, 64, 3, 1), (16, 24, 512, 64, 64, 3, 1), (32, 16, 512, 64, 64, 3, 1),
     # ... and its 32 -> 32 form (64-byte pixels, one K chunk): the same shapes, and the reference geometry's 144 x 160
     (2, 21, 60, 32, 32, 3, 1), (3, 64, 96, 32, 32, 3, 1), (16, 24, 512, 32, 32, 3, 1), (32, 16, 512, 32, 32, 3, 1), (4, 144, 160, 32, 32, 3, 1),
+    (20, 72, 80, 64, 192, 3, 1),                                      # >= 512 tiles: the persistent form (conv3x3p), ragged rows / columns / channel tiles
 ]
 
 
@@ -343,32 +404,85 @@ WGRAD_SETTINGS = [dict(wgrad3x3g=1, wgrad3x3r=1, wgrad3x3d=1), dict(wgrad3x3g=0,
                   dict(wgrad3x3g=0, wgrad3x3r=0, wgrad3x3d=1), dict(wgrad3x3g=1, wgrad3x3r=1, wgrad3x3d=0)]
 
 
-@pytest.mark.parametrize("case", BF16_CONV_CASES)
-def test_conv2d_bf16(U, case, monkeypatch):
-    ops = U.ops
+# The switch sets under which the forward and the data gradient of the two tests below run with the integer data, on top of the
+# defaults and against ONE expected tensor per case: the fall-through order of plan_conv (csrc/api.hip), so that every kernel that
+# can serve a layer meets the oracle on it, not only the one the defaults pick.
+CONV_SWITCH_SETS = [
+    {}, dict(conv3x3p=0), dict(conv3x3g=0), dict(conv3x3g=0, conv3x3s=0), dict(conv3x3g=0, conv3x3s=0, conv3x3h=0),
+    dict(conv3x3g=0, conv3x3s=0, conv3x3h=0, conv3x3r=0),                                   # the generic patch kernel
+    dict(conv3x3=0, conv3x3g_pair=0), dict(conv3x3=0, conv3x3g_pair=0, igemm2=0),           # tap-table kernels
+    dict(stem=0), dict(dyn_tiles=0), dict(conv3x3d=0), dict(upconv3x3q=0), dict(upconv3x3g=0),
+    dict(upconv3x3g=0, conv3x3=0),                                                          # four parity classes
+]
+CONVT_SWITCH_SETS = [{}, dict(upconv3x3q=0), dict(upconv3x3g=0), dict(upconv3x3g=0, conv3x3=0), dict(conv3x3d=0)]
+
+
+def switch_sets(data, table):
+    return table if data == "int" else [{}]
+
+
+def bf16_case_base(case):
+    """Narrow images take the paired-image tile of conv3x3g even at test sizes (by default it is gated on the workgroup count)."""
+    return dict(conv3x3g_pair=2) if case[2] <= 16 else {}
+
+
+def bf16_in_ld(case):
+    """(channel offset, pixel stride) of the forward input buffer of a BF16_CONV_CASES launch, and the data gradient's dy stride."""
     B, H, W, Ci, Co, k, s = case
-    if W <= 16:      # narrow images: take the paired-image tile of conv3x3g even at test sizes (it is gated on the workgroup count)
-        ops.set_config(conv3x3g_pair=2)
-    x, w, b = conv_data(case)
+    return 8, Ci + 8, -(-Co // 8) * 8
+
+
+@X.parametrize_kinds("case", BF16_CONV_CASES)
+def test_conv2d_bf16(U, case, data):
+    """Conv2D forward (bias, addend, strided output buffer), data gradient and weight gradient in bf16 storage.
+    data = "int": every stored element equals the oracle's (two roundings with an addend: exact_data.expected_bf16), under every
+    switch set of CONV_SWITCH_SETS; the data gradient has an addend too (a separate tensor; in place for the stride-2 layers,
+    as the engines accumulate the skip gradient), and the weight gradient (l2 coefficient 0.5) is exact in fp32."""
+    ops = U.ops
+    exact = data == "int"
+    B, H, W, Ci, Co, k, s = case
+    base = bf16_case_base(case)
+    set_switches(ops, base)
+    x, w, b = conv_data(case, data=data)
     x, w = q16(x), q16(w)
     x.requires_grad_(True); w.requires_grad_(True)
     y = R.conv2d_same(x, w, b, s)
     Ho, Wo = y.shape[2], y.shape[3]
-    add = q16(torch.tensor(detrand.uniform(f"a{case}", (B, Co, Ho, Wo), -1, 1, np.float64)))
-    gy = q16(torch.tensor(detrand.uniform(f"g{case}", (B, Co, Ho, Wo), -1, 1, np.float64)))
+    add = q16(rand(f"a{case}", (B, Co, Ho, Wo), data, "addend"))
+    gy = q16(rand(f"g{case}", (B, Co, Ho, Wo), data))
+    dadd = X.addends(f"da{case}", (B, Ci, H, W)) if exact else None
     (y * gy).sum().backward()
+    reg = X.REG if exact else 0.002
+    if exact:       # the conditions of the method, from the oracle's side, before any launch
+        xd, wd = x.detach(), w.detach()
+        ties = X.check_exactness_conditions({"x": (xd, True), "w": (wd, True), "bias": (b, False), "addend": (add, True)},
+                                            X.conv_abs_bound(k * k * Ci), y.detach(), add, what=f"fwd {case}")
+        ties_d = X.check_exactness_conditions({"dy": (gy, True), "addend": (dadd, True)}, X.conv_abs_bound(k * k * Co, has_bias=False),
+                                              x.grad, dadd, what=f"dgrad {case}")
+        X.check_exactness_conditions({"w": (wd, False)}, B * Ho * Wo * 9 + 1, quantum=0.5, what=f"wgrad {case}")
+        assert (ties > 0 or y.numel() < 4096) and (ties_d > 0 or x.numel() < 4096), (ties, ties_d)
+        X.note_ties(ties + ties_d)
+        want_y = X.expected_bf16(y.detach(), add).to(DEV)
+        want_dx = X.expected_bf16(x.grad, dadd).to(DEV)
 
     g = ops.geom(B, H, W, Ci, Co, k, s)
-    xa = ops.Act(to_nhwc_bf16(x.detach(), Ci + 8, 8, DEV), 8, Ci)
+    c0, ldx, Np = bf16_in_ld(case)
+    xa = ops.Act(to_nhwc_bf16(x.detach(), ldx, c0, DEV), c0, Ci)
     w32 = w.detach().permute(3, 0, 1, 2).contiguous().float().to(DEV)            # [Co][k][k][Ci] fp32 master
     wh = torch.empty((Co, k * k, Ci), dtype=torch.bfloat16, device=DEV)
     ops.cast_weight_bf16(w32, wh, Co, k * k, Ci, Ci)
-    ya = ops.Act(torch.full((B, Ho, Wo, Co + 8), 512.0, dtype=torch.bfloat16, device=DEV), 0, Co)
     adda = ops.Act(to_nhwc_bf16(add, Co, 0, DEV))
-    ops.conv2d_fwd(g, xa, wh, b.float().to(DEV), ya, adda)
-    torch.cuda.synchronize()
-    close(ya.dense().permute(0, 3, 1, 2), y.detach() + add, 1e-2, "bf16 fwd")
-    assert float(ya.base[..., Co:].float().min()) == 512.0
+    for sw in switch_sets(data, CONV_SWITCH_SETS):
+        set_switches(ops, base, sw)
+        ya = ops.Act(torch.full((B, Ho, Wo, Co + 8), 512.0, dtype=torch.bfloat16, device=DEV), 0, Co)
+        ops.conv2d_fwd(g, xa, wh, b.float().to(DEV), ya, adda)
+        torch.cuda.synchronize()
+        if exact:
+            exact_act(ya.dense(), want_y, f"bf16 fwd {case} {sw}")
+        else:
+            close(ya.dense().permute(0, 3, 1, 2), y.detach() + add, 1e-2, "bf16 fwd")
+        assert float(ya.base[..., Co:].float().min()) == 512.0 and float(ya.base[..., Co:].float().max()) == 512.0
+    set_switches(ops, base)
     ne = ops.conv3x3s2_packed_elems(Co, Ci) if (k == 3 and s == 2) else 0
     if ne:      # the packed kernel copy of the stride-2 forward kernel: same values in the same LDS positions -> the same bits out
         pk, pk2 = torch.zeros(ne, dtype=torch.bfloat16, device=DEV), torch.zeros(ne, dtype=torch.bfloat16, device=DEV)
@@ -381,43 +495,109 @@ def test_conv2d_bf16(U, case, monkeypatch):
         torch.cuda.synchronize()
         assert torch.equal(ya2.base, ya.base)
 
-    Np = -(-Co // 8) * 8
     wt = torch.zeros((Ci, k * k, Np), dtype=torch.bfloat16, device=DEV)
     ops.transpose_cast_weight_bf16(w32, wt, Co, k * k, Ci, Np)
     gya = ops.Act(to_nhwc_bf16(gy, Np, 0, DEV), 0, Np)
     if Np != Co:
         gya.base[..., Co:] = 0
     gd = ops.geom(B, H, W, Ci, Np, k, s)
-    dxa = ops.Act(torch.full((B, H, W, Ci), 256.0, dtype=torch.bfloat16, device=DEV))
-    ops.conv2d_dgrad(gd, gya, wt, dxa)
-    torch.cuda.synchronize()
-    close(dxa.dense().permute(0, 3, 1, 2), x.grad, 1e-2, "bf16 dgrad")
+    for sw in switch_sets(data, CONV_SWITCH_SETS):
+        set_switches(ops, base, sw)
+        dxa = ops.Act(torch.full((B, H, W, Ci), 256.0, dtype=torch.bfloat16, device=DEV))
+        if exact:
+            ops.conv2d_dgrad(gd, gya, wt, dxa, addend=ops.Act(to_nhwc_bf16(dadd, Ci, 0, DEV)))
+            torch.cuda.synchronize()
+            exact_act(dxa.dense(), want_dx, f"bf16 dgrad {case} {sw}")
+            if s == 2:      # accumulating in place behind an earlier writer (the skip gradient of the strided layers)
+                acc = ops.Act(to_nhwc_bf16(dadd, Ci, 0, DEV))
+                ops.conv2d_dgrad(gd, gya, wt, acc, addend=acc)
+                torch.cuda.synchronize()
+                exact_act(acc.dense(), want_dx, f"bf16 dgrad in place {case} {sw}")
+        else:
+            ops.conv2d_dgrad(gd, gya, wt, dxa)
+            torch.cuda.synchronize()
+            close(dxa.dense().permute(0, 3, 1, 2), x.grad, 1e-2, "bf16 dgrad")
+    set_switches(ops, base)
 
     if k == 3:
         gyw = ops.Act(to_nhwc_bf16(gy, Co, 0, DEV))
+        want_dw = (w.grad + reg * w.detach()).permute(3, 0, 1, 2)
         for sw in WGRAD_SETTINGS:
-            ops.set_config(**sw)
+            set_switches(ops, base, sw)
             ws = ops.Workspace(DEV)
             dw = torch.full((Co, k, k, Ci), 111.0, device=DEV)
-            ops.conv2d_wgrad(g, xa, gyw, dw, ws, reg=0.002, w=w32)
+            ops.conv2d_wgrad(g, xa, gyw, dw, ws, reg=reg, w=w32)
             torch.cuda.synchronize()
-            close(dw, (w.grad + 0.002 * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * Ho * Wo) + 1e-6, f"bf16 wgrad {sw}")
+            if exact:
+                X.assert_exact(dw, want_dw, f"bf16 wgrad {case} {sw}")
+            else:
+                close(dw, want_dw, 2e-6 * math.sqrt(B * Ho * Wo) + 1e-6, f"bf16 wgrad {sw}")
 
 
-@pytest.mark.parametrize("case", [(2, 6, 5, 16, 8, 3), (1, 4, 4, 64, 32, 3), (2, 3, 3, 128, 64, 3), (2, 12, 40, 48, 72, 3),
-                                  (1, 16, 32, 136, 64, 3),
-                                  (1, 16, 64, 96, 72, 3), (2, 20, 32, 32, 64, 3),    # LDS-DMA kernel (upconv3x3g): 3 chunks / ragged N, ragged rows
-                                  (2, 8, 32, 64, 32, 3), (1, 16, 32, 128, 48, 3),    # data gradient on conv3x3d (input in a concat buffer)
-                                  (2, 16, 16, 64, 32, 3)])                           # 16-wide adjoint: tap-table kernel
-def test_conv2d_transpose_bf16(U, case):
+# The first layer as the engines launch it: 8 stored input channels at their own pixel stride, no addend (test_stem_conv_bf16).
+STEM_CASES = [(2, 40, 70, 8, 64, 3, 1), (1, 32, 64, 8, 64, 3, 1), (3, 7, 33, 8, 64, 3, 1), (2, 20, 40, 8, 128, 3, 1)]
+
+K3_IDS = {"tap-table", "conv3x3r", "conv3x3g", "conv3x3g pair", "conv3x3h", "conv3x3s", "conv3x3p", "stem", "patch"}     # include/unetrir.h
+
+
+def test_the_switch_sets_reach_every_3x3_kernel(U):
+    """Which kernel serves each 3x3 stride-1 (case, switch set, direction) of the tables above - asked of the dispatch itself
+    (unetrir_conv3x3_kernel_id_bf16: a query, no launch) with the pixel strides the launches use: all nine kernels the header names
+    must occur, so the exact comparisons of test_conv2d_bf16 / test_stem_conv_bf16 cover every one of them."""
     ops = U.ops
+
+    class In:          # the query reads the pixel stride of the launch's input only
+        def __init__(self, ld):
+            self.ld = ld
+    seen = {}
+    for case in BF16_CONV_CASES + STEM_CASES:
+        B, H, W, Ci, Co, k, s = case
+        if k != 3 or s != 1:
+            continue
+        stem = case in STEM_CASES
+        c0, ldx, Np = (0, Ci, Co) if stem else bf16_in_ld(case)
+        for sw in CONV_SWITCH_SETS:
+            set_switches(ops, {} if stem else bf16_case_base(case), sw)
+            seen.setdefault(ops.conv3x3_kernel(ops.geom(B, H, W, Ci, Co, 3, 1), 0, In(ldx)), []).append((case, sw, "fwd"))
+            if not stem:
+                seen.setdefault(ops.conv3x3_kernel(ops.geom(B, H, W, Ci, Np, 3, 1), 1, In(Np)), []).append((case, sw, "dgrad"))
+    print("3x3 stride-1 kernels by (case, switch set, direction):", {n: len(v) for n, v in sorted(seen.items())})
+    assert set(seen) == K3_IDS, sorted(K3_IDS - set(seen))
+    # the stem kernel is reached by the layers that launch without an addend, as the stem does
+    assert any(c in STEM_CASES for c, _, _ in seen["stem"])
+
+
+CONVT_BF16_CASES = [(2, 6, 5, 16, 8, 3), (1, 4, 4, 64, 32, 3), (2, 3, 3, 128, 64, 3), (2, 12, 40, 48, 72, 3),
+                    (1, 16, 32, 136, 64, 3),
+                    (1, 16, 64, 96, 72, 3), (2, 20, 32, 32, 64, 3),    # LDS-DMA kernel (upconv3x3g): 3 chunks / ragged N, ragged rows
+                    (2, 8, 32, 64, 32, 3), (1, 16, 32, 128, 48, 3),    # data gradient on conv3x3d (input in a concat buffer)
+                    (2, 16, 16, 64, 32, 3),                            # 16-wide adjoint: tap-table kernel
+                    (8, 128, 128, 128, 64, 3)]                         # >= 1024 tiles: the persistent form (upconv3x3q)
+
+
+@X.parametrize_kinds("case", CONVT_BF16_CASES)
+def test_conv2d_transpose_bf16(U, case, data):
+    """Conv2DTranspose forward (bias, upper half of a concat buffer), data gradient (plain, and with the packed kernel copy where
+    one is defined) and weight gradient.  data = "int": exact, forward and data gradient under every set of CONVT_SWITCH_SETS."""
+    ops = U.ops
+    exact = data == "int"
     B, H, W, Ci, Co, k = case
-    x = q16(torch.tensor(detrand.uniform(f"tx{case}", (B, Ci, H, W), -1, 1, np.float64))).requires_grad_(True)
-    w = q16(torch.tensor(detrand.uniform(f"tw{case}", (k, k, Co, Ci), -1, 1, np.float64))).requires_grad_(True)
-    b = torch.tensor(detrand.uniform(f"tb{case}", (Co,), -1, 1, np.float64))
+    x = q16(rand(f"tx{case}", (B, Ci, H, W), data)).requires_grad_(True)
+    w = q16(rand(f"tw{case}", (k, k, Co, Ci), data, "kernel")).requires_grad_(True)
+    b = rand(f"tb{case}", (Co,), data, "bias")
     y = R.conv2d_transpose_same(x, w, b, 2)
-    gy = q16(torch.tensor(detrand.uniform(f"tg{case}", tuple(y.shape), -1, 1, np.float64)))
+    gy = q16(rand(f"tg{case}", tuple(y.shape), data))
     (y * gy).sum().backward()
+    reg = X.REG if exact else 0.002
+    if exact:
+        ties = X.check_exactness_conditions({"x": (x.detach(), True), "w": (w.detach(), True), "bias": (b, False)},
+                                            X.conv_abs_bound(k * k * Ci, has_addend=False), y.detach(), what=f"convT fwd {case}")
+        ties_d = X.check_exactness_conditions({"dy": (gy, True)}, X.conv_abs_bound(k * k * Co, has_bias=False, has_addend=False), x.grad,
+                                              what=f"convT dgrad {case}")
+        X.check_exactness_conditions({"w": (w.detach(), False)}, B * H * W * 9 + 1, quantum=0.5, what=f"convT wgrad {case}")
+        assert (ties > 0 or y.numel() < 4096) and (ties_d > 0 or x.numel() < 4096), (ties, ties_d)
+        X.note_ties(ties + ties_d)
+        want_y, want_dx = X.expected_bf16(y.detach()).to(DEV), X.expected_bf16(x.grad).to(DEV)
     g = ops.geom(B, H, W, Ci, Co, k, 2)
     w32 = w.detach().permute(3, 0, 1, 2).contiguous().float().to(DEV)            # primary [Ci][k][k][Co]
     wprim = torch.empty((Ci, k * k, Co), dtype=torch.bfloat16, device=DEV)
@@ -425,23 +605,43 @@ def test_conv2d_transpose_bf16(U, case):
     wt = torch.zeros((Co, k * k, Ci), dtype=torch.bfloat16, device=DEV)
     ops.transpose_cast_weight_bf16(w32, wt, Ci, k * k, Co, Ci)
     xa = ops.Act(to_nhwc_bf16(x.detach(), Ci, 0, DEV))
-    ya = ops.Act(torch.full((B, 2 * H, 2 * W, 2 * Co), 512.0, dtype=torch.bfloat16, device=DEV), Co, Co)
-    ops.conv2d_transpose_fwd(g, xa, wt, b.float().to(DEV), ya)
-    torch.cuda.synchronize()
-    close(ya.dense().permute(0, 3, 1, 2), y.detach(), 1e-2, "bf16 convT fwd")
-    assert float(ya.base[..., :Co].float().min()) == 512.0
     gya = ops.Act(to_nhwc_bf16(gy, 2 * Co, Co, DEV), Co, Co)
-    dxa = ops.Act(torch.full((B, H, W, Ci), 256.0, dtype=torch.bfloat16, device=DEV))
-    ops.conv2d_transpose_dgrad(g, gya, wprim, dxa)
-    torch.cuda.synchronize()
-    close(dxa.dense().permute(0, 3, 1, 2), x.grad, 1e-2, "bf16 convT dgrad")
+    ne = ops.conv3x3s2_packed_elems(Ci, Co)          # the data gradient is the stride-2 forward kernel on the adjoint geometry
+    pk = None
+    if exact and ne:
+        pk = torch.zeros(ne, dtype=torch.bfloat16, device=DEV)
+        ops.cast_weights_batched(ops.make_cast_table([(w32, torch.empty_like(wprim), torch.empty_like(wt), Ci, k * k, Co, Co, Ci, pk)], DEV))
+    for sw in switch_sets(data, CONVT_SWITCH_SETS):
+        set_switches(ops, sw)
+        ya = ops.Act(torch.full((B, 2 * H, 2 * W, 2 * Co), 512.0, dtype=torch.bfloat16, device=DEV), Co, Co)
+        ops.conv2d_transpose_fwd(g, xa, wt, b.float().to(DEV), ya)
+        dxa = ops.Act(torch.full((B, H, W, Ci), 256.0, dtype=torch.bfloat16, device=DEV))
+        ops.conv2d_transpose_dgrad(g, gya, wprim, dxa)
+        torch.cuda.synchronize()
+        assert float(ya.base[..., :Co].float().min()) == 512.0 and float(ya.base[..., :Co].float().max()) == 512.0
+        if exact:
+            exact_act(ya.dense(), want_y, f"bf16 convT fwd {case} {sw}", tile=(32, 64))
+            exact_act(dxa.dense(), want_dx, f"bf16 convT dgrad {case} {sw}")
+            if pk is not None:
+                dxp = ops.Act(torch.full((B, H, W, Ci), 256.0, dtype=torch.bfloat16, device=DEV))
+                ops.conv2d_transpose_dgrad(g, gya, wprim, dxp, w_packed=pk)
+                torch.cuda.synchronize()
+                exact_act(dxp.dense(), want_dx, f"bf16 convT dgrad, packed kernel copy {case} {sw}")
+        else:
+            close(ya.dense().permute(0, 3, 1, 2), y.detach(), 1e-2, "bf16 convT fwd")
+            close(dxa.dense().permute(0, 3, 1, 2), x.grad, 1e-2, "bf16 convT dgrad")
+    set_switches(ops)
+    want_dw = (w.grad + reg * w.detach()).permute(3, 0, 1, 2)
     for sw in WGRAD_SETTINGS:
-        ops.set_config(**sw)
+        set_switches(ops, sw)
         ws = ops.Workspace(DEV)
         dw = torch.full((Ci, k, k, Co), 111.0, device=DEV)
-        ops.conv2d_transpose_wgrad(g, xa, gya, dw, ws, reg=0.002, w=w32)
+        ops.conv2d_transpose_wgrad(g, xa, gya, dw, ws, reg=reg, w=w32)
         torch.cuda.synchronize()
-        close(dw, (w.grad + 0.002 * w.detach()).permute(3, 0, 1, 2), 2e-6 * math.sqrt(B * H * W) + 1e-6, f"bf16 convT wgrad {sw}")
+        if exact:
+            X.assert_exact(dw, want_dw, f"bf16 convT wgrad {case} {sw}")
+        else:
+            close(dw, want_dw, 2e-6 * math.sqrt(B * H * W) + 1e-6, f"bf16 convT wgrad {sw}")
 
 
 @pytest.mark.parametrize("shape", [(2, 12, 10, 16), (1, 4, 4, 1024), (2, 33, 31, 8)])
@@ -515,14 +715,18 @@ def test_batchnorm_passes_on_a_tensor_past_the_non_temporal_threshold(U):
     close(dxa.dense(), dx64, 1e-2, "dx")
 
 
-@pytest.mark.parametrize("B,H,W,Cc", [(2, 20, 37, 32), (1, 70, 200, 64), (1, 33, 256, 128), (1, 12, 300, 64), (2, 9, 20, 16),
+@X.parametrize_kinds("B,H,W,Cc", [(2, 20, 37, 32), (1, 70, 200, 64), (1, 33, 256, 128), (1, 12, 300, 64), (2, 9, 20, 16),
                                       (1, 19, 512, 128), (2, 35, 523, 64), (1, 7, 257, 32)])
-def test_head_and_loss_bf16(U, B, H, W, Cc):
+def test_head_and_loss_bf16(U, B, H, W, Cc, data):
     """Head forward / sigmoid+loss / head weight gradient on bf16 activations.  The matrix-core head (C in {32,64,128}; images
     wider than 256 pixels run in column blocks: 300, 512 = configs[3]'s width, 523 and 257 exercise the block seams) takes the
     kernel as bf16, so the oracle runs on the bf16-rounded kernel; C = 16 takes the direct kernels (fp32 kernel values: the
-    rounded kernel is exactly representable there too)."""
+    rounded kernel is exactly representable there too).
+    data = "int": the head forward (fp32 logits), its weight gradient and its data gradient from an integer dlogits tensor passed
+    directly, every element equal to the oracle's; the sigmoid / loss part runs on the uniform kind only."""
     ops = U.ops
+    if data == "int":
+        return _head_exact(ops, B, H, W, Cc)
     x = q16(torch.tensor(detrand.uniform("hx16", (B, Cc, H, W), -1, 1, np.float64)))
     w = q16(torch.tensor(detrand.uniform("hw16", (6, 6, Cc, 2), -1, 1, np.float64))).requires_grad_(True)
     b = torch.tensor(detrand.uniform("hb16", (2,), -1, 1, np.float64))
@@ -565,28 +769,80 @@ def test_head_and_loss_bf16(U, B, H, W, Cc):
         assert float(dxa.base[..., :8].float().min()) == 3.0 and float(dxa.base[..., :8].float().max()) == 3.0
 
 
-@pytest.mark.parametrize("B,K,N", [(32, 8192, 4096), (3, 520, 72), (4, 4096, 8192)])
-def test_dense_split_k(U, B, K, N):
+# The head's data gradient sums only 2 x 36 products per output: with gradients in {-1 .. 3} every result stays below 256, where all
+# integers are bf16 values, and the store would never round.  The integer dlogits of the head are therefore the data set's gradients
+# shifted by 40 ({39 .. 43}, bf16 values): results around 1 500, where bf16 keeps multiples of 8 and 4 mod 8 is an exact tie.
+HEAD_DLOGITS_SHIFT = 40
+
+
+def _head_exact(ops, B, H, W, Cc):
+    tag = f"head{B, H, W, Cc}"
+    x = X.acts(f"x{tag}", (B, Cc, H, W))
+    w = X.kernels(f"w{tag}", (6, 6, Cc, 2)).requires_grad_(True)
+    b = X.biases(f"b{tag}", (2,))
+    dlog = X.acts(f"d{tag}", (B, 2, H, W)) + HEAD_DLOGITS_SHIFT
+    x2 = x.clone().requires_grad_(True)
+    logits = R.conv2d_same(x2, w, b, 1)
+    (logits * dlog).sum().backward()
+    gmax = 3 + HEAD_DLOGITS_SHIFT
+    X.check_exactness_conditions({"x": (x, True), "w": (w.detach(), True), "bias": (b, False)}, X.conv_abs_bound(36 * Cc, has_addend=False),
+                                 what=f"{tag} fwd")
+    X.check_exactness_conditions({"dlogits": (dlog, True)}, B * H * W * 3 * gmax, what=f"{tag} wgrad")
+    ties = X.check_exactness_conditions({"dlogits": (dlog, True)}, 72 * 2 * gmax, x2.grad, what=f"{tag} dgrad")
+    xa = ops.Act(to_nhwc_bf16(x, Cc, 0, DEV))
+    w8 = torch.zeros((8, 6, 6, Cc), device=DEV); w8[:2] = w.detach().permute(3, 0, 1, 2).float().to(DEV)
+    b8 = torch.zeros(8, device=DEV); b8[:2] = b.float().to(DEV)
+    la = ops.Act(torch.full((B, H, W, 4), 5.0, device=DEV))
+    ops.head6x6_fwd(xa, w8, b8, la)
+    torch.cuda.synchronize()
+    exact_act(la.dense()[..., :2], logits.detach(), f"{tag} fwd")
+    assert float(la.dense()[..., 2:].abs().max()) == 0.0
+    dl = ops.Act(torch.zeros((B, H, W, 8), dtype=torch.bfloat16, device=DEV))
+    dl.base[..., :2] = dlog.permute(0, 2, 3, 1).to(torch.bfloat16).to(DEV)
+    dw = torch.zeros((8, 6, 6, Cc), device=DEV)
+    ws = ops.Workspace(DEV)
+    ops.head6x6_wgrad(xa, dl, dw, ws)
+    torch.cuda.synchronize()
+    X.assert_exact(dw[:2], w.grad.permute(3, 0, 1, 2), f"{tag} wgrad")
+    assert float(dw[2:].abs().max()) == 0.0
+    if ops.head6x6_dgrad_supported(W, Cc):
+        assert ties > 0 or x.numel() < 4096
+        X.note_ties(ties)
+        dxa = ops.Act(torch.full((B, H, W, Cc + 8), 3.0, dtype=torch.bfloat16, device=DEV), 8, Cc)
+        ops.head6x6_dgrad(dl, w8, dxa)
+        torch.cuda.synchronize()
+        exact_act(dxa.dense(), X.expected_bf16(x2.grad), f"{tag} dgrad", tile=(1, 64))
+        assert float(dxa.base[..., :8].float().min()) == 3.0 and float(dxa.base[..., :8].float().max()) == 3.0
+
+
+@X.parametrize_kinds("B,K,N", [(32, 8192, 4096), (3, 520, 72), (4, 4096, 8192)])
+def test_dense_split_k(U, B, K, N, data):
     """Dense on a small batch through the split-K entry point (dl_models/u_net.py:259) and its data gradient."""
     ops = U.ops
-    x = torch.tensor(detrand.uniform(f"dx{B,K}", (B, K), -1, 1))
-    w = torch.tensor(detrand.uniform(f"dw{K,N}", (N, K), -1, 1)) * 0.05
-    b = torch.tensor(detrand.uniform(f"db{N}", (N,), -1, 1))
+    exact = data == "int"
+    if exact:
+        x, w, b = X.acts(f"dx{B,K}", (B, K)).float(), X.kernels(f"dw{K,N}", (N, K)).float(), X.biases(f"db{N}", (N,)).float()
+        X.check_exactness_conditions({"x": (x.double(), False), "w": (w.double(), False), "bias": (b.double(), False)},
+                                     X.conv_abs_bound(max(K, N), has_addend=False), what=f"dense {B, K, N}")
+    else:
+        x = torch.tensor(detrand.uniform(f"dx{B,K}", (B, K), -1, 1))
+        w = torch.tensor(detrand.uniform(f"dw{K,N}", (N, K), -1, 1)) * 0.05
+        b = torch.tensor(detrand.uniform(f"db{N}", (N,), -1, 1))
     xa = ops.Act(x.view(B, 1, 1, K).to(DEV))
     ya = ops.Act(torch.full((B, 1, 1, N), 7.0, device=DEV))
     ws = ops.Workspace(DEV)
     ops.dense_fwd(xa, w.to(DEV), b.to(DEV), ya, ws)
     torch.cuda.synchronize()
-    close(ya.base.view(B, N), x.double() @ w.double().t() + b.double(), 2e-6 * math.sqrt(K) + 1e-6, "dense fwd")
+    cmp32(exact, ya.base.view(B, N), x.double() @ w.double().t() + b.double(), 2e-6 * math.sqrt(K) + 1e-6, "dense fwd")
     # data gradient from the kernel as stored (no transposed copy): dx = dy . w, rows beyond B untouched, ld > K honoured
-    dy = torch.tensor(detrand.uniform(f"ddy{B,N}", (B, N), -1, 1))
+    dy = X.acts(f"ddy{B,N}", (B, N)).float() if exact else torch.tensor(detrand.uniform(f"ddy{B,N}", (B, N), -1, 1))
     assert ops.dense_dgrad_supported(B, K, N) == (B <= 32 and K % 4 == 0)
     if ops.dense_dgrad_supported(B, K, N):
         ldx = K + 8
         dxa = ops.Act(torch.full((B, 1, 1, ldx), 7.0, device=DEV), 0, K)
         ops.dense_dgrad(ops.Act(dy.view(B, 1, 1, N).to(DEV)), w.to(DEV), dxa, ws)
         torch.cuda.synchronize()
-        close(dxa.base.view(B, ldx)[:, :K], dy.double() @ w.double(), 2e-6 * math.sqrt(N) + 1e-6, "dense dgrad")
+        cmp32(exact, dxa.base.view(B, ldx)[:, :K], dy.double() @ w.double(), 2e-6 * math.sqrt(N) + 1e-6, "dense dgrad")
         assert bool((dxa.base.view(B, ldx)[:, K:] == 7.0).all())
         again = ops.Act(torch.zeros((B, 1, 1, ldx), device=DEV), 0, K)
         ops.dense_dgrad(ops.Act(dy.view(B, 1, 1, N).to(DEV)), w.to(DEV), again, ws)
@@ -659,6 +915,38 @@ def test_conv_fused_column_statistics_bf16(U, case, monkeypatch):
     close(out, dxa.base.double().sum(dim=(0, 1, 2))[c0:], 2e-6, "bias gradient from colstat")
 
 
+class Draw:
+    """bf16 device tensors of one data kind for the tests that compare two kernels on one layer: "uniform" - uniform(-1, 1) * scale
+    from a seeded device generator; "int" - the integers of tests/exact_data.py for the tensor's role (the scale does not apply).
+    reseed() restarts the sequence, so that both kernels see the same tensors."""
+
+    def __init__(self, data, seed, tag):
+        self.data, self.seed, self.tag = data, seed, tag
+        self.gen = torch.Generator(device=DEV)
+        self.reseed()
+
+    def reseed(self):
+        self.gen.manual_seed(self.seed)
+        self.n = 0
+
+    def __call__(self, *sh, role="act", scale=1.0):
+        if self.data == "int":
+            self.n += 1
+            return rand(f"{self.tag}:{self.n}", sh, "int", role).to(torch.bfloat16).to(DEV)
+        t = ((torch.rand(sh, device=DEV, generator=self.gen) - 0.5) * 2).to(torch.bfloat16)
+        return t if scale == 1.0 else (t.float() * scale).to(torch.bfloat16)
+
+    def bias(self, n):
+        if self.data == "int":
+            self.n += 1
+            return X.biases(f"{self.tag}:{self.n}", (n,)).float().to(DEV)
+        return torch.rand(n, device=DEV, generator=self.gen) - 0.5
+
+
+def nchw64(t_nhwc):
+    return t_nhwc.double().cpu().permute(0, 3, 1, 2)
+
+
 @pytest.mark.parametrize("case", [(20, 72, 80, 64, 192), (32, 64, 64, 64, 256), (16, 128, 128, 96, 128)])
 def test_persistent_conv3x3p_equals_conv3x3g_bit_for_bit(U, case):
     """conv3x3p (persistent: continuous K loop across tiles, direct-store epilogue, per-workgroup statistics) against conv3x3g
@@ -713,21 +1001,22 @@ def test_persistent_conv3x3p_equals_conv3x3g_bit_for_bit(U, case):
     assert torch.equal(y3.base, res[1][6]) and torch.equal(cs3, cs4)
 
 
-@pytest.mark.parametrize("case", [(3, 72, 80, 128, 64), (2, 40, 50, 256, 64), (4, 64, 64, 96, 64)])
-def test_conv3x3g_64_channel_tiles_serve_the_n64_layers(U, case):
+@X.parametrize_kinds("case", [(3, 72, 80, 128, 64), (2, 40, 50, 256, 64), (4, 64, 64, 96, 64)])
+def test_conv3x3g_64_channel_tiles_serve_the_n64_layers(U, case, data):
     """N = 64 output channels with C > 64 (dec1.cb1a: 128 -> 64 behind the first skip concat, dl_models/u_net.py:309) run on
     conv3x3g's 64-channel-tile instantiation: forward (bias, addend, fused column statistics over its eight row groups) and the
     flip = 1 data gradient form, sizes that are not multiples of the 16 x 32 tile (the reference geometry's 72 x 80 among them),
-    against conv3x3h for the same layer (set_config(conv3x3g=0)) - different K order, so to bf16 rounding - and the routing itself."""
+    against conv3x3h for the same layer (set_config(conv3x3g=0)) - different K order, so to bf16 rounding - and the routing itself.
+    data = "int": both kernels' forward and data gradient equal the oracle's in every element of every image."""
     ops = U.ops
+    exact = data == "int"
     B, H, W, Ci, Co = case
-    gen = torch.Generator(device=DEV); gen.manual_seed(H * 100 + Ci)
-    rnd = lambda *sh: ((torch.rand(sh, device=DEV, generator=gen) - 0.5) * 2).to(torch.bfloat16)
+    rnd = Draw(data, H * 100 + Ci, f"n64{case}")
     g = ops.geom(B, H, W, Ci, Co, 3, 1)            # forward: C = Ci > 64, N = 64
     gd = ops.geom(B, H, W, Co, Ci, 3, 1)           # a layer whose DATA GRADIENT has C = Ci > 64, N = 64
-    x, add = ops.Act(rnd(B, H, W, Ci + 8), 0, Ci), ops.Act(rnd(B, H, W, Co))
-    w, wt = (rnd(Co, 9, Ci).float() * 0.1).to(torch.bfloat16), (rnd(Co, 9, Ci).float() * 0.1).to(torch.bfloat16)
-    bias = (torch.rand(Co, device=DEV, generator=gen) - 0.5)
+    x, add = ops.Act(rnd(B, H, W, Ci + 8), 0, Ci), ops.Act(rnd(B, H, W, Co, role="addend"))
+    w, wt = rnd(Co, 9, Ci, role="kernel", scale=0.1), rnd(Co, 9, Ci, role="kernel", scale=0.1)
+    bias = rnd.bias(Co)
     old = ops.get_config()
     res = {}
     try:
@@ -762,6 +1051,19 @@ def test_conv3x3g_64_channel_tiles_serve_the_n64_layers(U, case):
         add.base[:1].double().cpu().permute(0, 3, 1, 2)
     got = res[1][1][:1, ..., :Co].double().cpu().permute(0, 3, 1, 2)
     assert float((got - want).abs().max()) <= 1e-2 * float(want.abs().max())
+    if exact:
+        xo, addn = nchw64(x.base[..., :Ci]), nchw64(add.base)
+        conv = R.conv2d_same(xo, w_hwio, bias.double().cpu(), 1)
+        x0 = torch.zeros((B, Co, H, W), dtype=torch.float64, requires_grad=True)       # the layer Co -> Ci whose data gradient reads x as dy
+        (R.conv2d_same(x0, wt.double().cpu().view(Co, 3, 3, Ci).permute(1, 2, 0, 3), None, 1) * xo).sum().backward()
+        ties = X.check_exactness_conditions({"x": (xo, True), "w": (w.double().cpu(), True), "wt": (wt.double().cpu(), True), "addend": (addn, True),
+                                             "bias": (bias.double().cpu(), False)}, X.conv_abs_bound(9 * Ci), conv, addn, what=f"n64 {case}")
+        ties_d = X.count_ties(x0.grad)
+        assert ties > 0 and ties_d > 0
+        X.note_ties(ties + ties_d)
+        for on, name in ((1, "conv3x3g"), (0, "conv3x3h")):
+            exact_act(res[on][1][..., :Co], X.expected_bf16(conv, addn), f"{name} 64-channel layer fwd {case}")
+            exact_act(res[on][3], X.expected_bf16(x0.grad), f"{name} 64-channel layer dgrad {case}")
 
 
 @pytest.mark.parametrize("case", [(20, 40, 72, 128, 256), (32, 64, 32, 96, 256), (8, 128, 128, 128, 64)])
@@ -817,14 +1119,16 @@ def test_cast_weights_batched_bf16(U):
             assert float(tr2[i].float().min()) == 1.0      # NULL destination: untouched
 
 
-@pytest.mark.parametrize("case", [(2, 40, 70, 8, 64, 3, 1), (1, 32, 64, 8, 64, 3, 1), (3, 7, 33, 8, 64, 3, 1), (2, 20, 40, 8, 128, 3, 1)])
-def test_stem_conv_bf16(U, case):
+@X.parametrize_kinds("case", STEM_CASES)
+def test_stem_conv_bf16(U, case, data):
     """First layer (8 stored input channels -> 64, no addend): the direct-operand stem kernel (stem3x3.hip), ragged tiles,
     a strided output buffer, and agreement with the general kernel bit for bit (both accumulate the 72 products in fp32 MFMA
-    order per output; equality is not guaranteed in general, so compare against the oracle and bound the difference)."""
+    order per output; equality is not guaranteed in general, so compare against the oracle and bound the difference).
+    data = "int": every element equals the oracle's, on the stem kernel and on each kernel that takes the layer without it."""
     ops = U.ops
+    exact = data == "int"
     B, H, W, Ci, Co, k, s = case
-    x, w, b = conv_data(case)
+    x, w, b = conv_data(case, data=data)
     x, w = q16(x), q16(w)
     y = R.conv2d_same(x, w, b, s)
     g = ops.geom(B, H, W, Ci, Co, k, s)
@@ -832,36 +1136,50 @@ def test_stem_conv_bf16(U, case):
     w32 = w.permute(3, 0, 1, 2).contiguous().float().to(DEV)
     wh = torch.empty((Co, 9, Ci), dtype=torch.bfloat16, device=DEV)
     ops.cast_weight_bf16(w32, wh, Co, 9, Ci, Ci)
-    ya = ops.Act(torch.full((B, H, W, Co + 8), 512.0, dtype=torch.bfloat16, device=DEV), 0, Co)
-    ops.conv2d_fwd(g, xa, wh, b.float().to(DEV), ya)
-    torch.cuda.synchronize()
-    close(ya.dense().permute(0, 3, 1, 2), y, 1e-2, "stem fwd")
-    assert float(ya.base[..., Co:].float().min()) == 512.0 and float(ya.base[..., Co:].float().max()) == 512.0
-    again = ops.Act(torch.zeros((B, H, W, Co), dtype=torch.bfloat16, device=DEV))
-    ops.conv2d_fwd(g, xa, wh, b.float().to(DEV), again)
-    assert torch.equal(again.base, ya.base[..., :Co])
+    if exact:
+        ties = X.check_exactness_conditions({"x": (x, True), "w": (w, True), "bias": (b, False)}, X.conv_abs_bound(9 * Ci, has_addend=False), y,
+                                            what=f"stem {case}")
+        assert ties > 0 or y.numel() < 4096
+        X.note_ties(ties)
+        want = X.expected_bf16(y).to(DEV)
+    for sw in switch_sets(data, CONV_SWITCH_SETS):
+        set_switches(ops, sw)
+        ya = ops.Act(torch.full((B, H, W, Co + 8), 512.0, dtype=torch.bfloat16, device=DEV), 0, Co)
+        ops.conv2d_fwd(g, xa, wh, b.float().to(DEV), ya)
+        torch.cuda.synchronize()
+        if exact:
+            exact_act(ya.dense(), want, f"stem fwd {case} {sw}")
+        else:
+            close(ya.dense().permute(0, 3, 1, 2), y, 1e-2, "stem fwd")
+        assert float(ya.base[..., Co:].float().min()) == 512.0 and float(ya.base[..., Co:].float().max()) == 512.0
+        again = ops.Act(torch.zeros((B, H, W, Co), dtype=torch.bfloat16, device=DEV))
+        ops.conv2d_fwd(g, xa, wh, b.float().to(DEV), again)
+        torch.cuda.synchronize()
+        assert torch.equal(again.base, ya.base[..., :Co])
 
 
-@pytest.mark.parametrize("case", [(3, 9, 10, 32, 64), (2, 16, 24, 64, 32), (5, 7, 12, 128, 128), (2, 8, 8, 256, 256), (4, 12, 20, 8, 32),
+@X.parametrize_kinds("case", [(3, 9, 10, 32, 64), (2, 16, 24, 64, 32), (5, 7, 12, 128, 128), (2, 8, 8, 256, 256), (4, 12, 20, 8, 32),
                                   (2, 33, 17, 16, 96), (2, 10, 12, 48, 64), (2, 6, 10, 96, 32), (2, 5, 8, 64, 96)])
-def test_pw1x1_kernel_against_the_tap_table_kernel_and_the_oracle(U, case):
+def test_pw1x1_kernel_against_the_tap_table_kernel_and_the_oracle(U, case, data):
     """The register-streaming 1x1 kernel (pw1x1.hip) in every form the residual graphs launch it (dl_models/res_ae.py:310-371,
     :453-514): Conv2D forward at stride 1 and 2 (bias, fused column statistics, addend), its data gradients (stride 2: scatter to
     the even pixels, zeros - or the untouched in-place addend - elsewhere, odd sizes included), Conv2DTranspose forward at
     stride 1 and at stride 2 'valid' (bias in the three other pixels of every cell) and its data gradient.  Same arithmetic as the
     tap-table kernel (one fp32 MFMA chain over C, one rounding): identical bits; plus the oracle on the forward results.
     Channel counts the kernel has no instantiation for (48, 96 input channels of either direction) must be served by the tap-table
-    kernel, not refused."""
+    kernel, not refused.
+    data = "int": all six output tensors (y, y2, dx, dacc, yt, dxt) equal the oracle's in every element, the stride-2 fill pixels
+    included."""
     ops = U.ops
+    exact = data == "int"
     B, H, W, Ci, Co = case
-    gen = torch.Generator(device=DEV); gen.manual_seed(B * 100 + Ci)
-    rnd = lambda *sh: ((torch.rand(sh, device=DEV, generator=gen) - 0.5) * 2).to(torch.bfloat16)
+    rnd = Draw(data, B * 100 + Ci, f"pw{case}")
     old = ops.get_config()
     out = {}
     try:
         for on in (1, 0):
             ops.set_config(pw1x1=on)
-            gen.manual_seed(B * 100 + Ci)
+            rnd.reseed()
             res = []
             for s in (1, 2):
                 g = ops.geom(B, H, W, Ci, Co, 1, s)
@@ -869,9 +1187,9 @@ def test_pw1x1_kernel_against_the_tap_table_kernel_and_the_oracle(U, case):
                 x = ops.Act(rnd(B, H, W, Ci + 8), 0, Ci)
                 if Ci == 8:
                     x.base[..., 2:8] = 0
-                w, wt = (rnd(Co, 1, Ci).float() * 0.2).to(torch.bfloat16), (rnd(Ci, 1, Co).float() * 0.2).to(torch.bfloat16)
-                bias = torch.rand(Co, device=DEV, generator=gen) - 0.5
-                add = ops.Act(rnd(B, Ho, Wo, Co))
+                w, wt = rnd(Co, 1, Ci, role="kernel", scale=0.2), rnd(Ci, 1, Co, role="kernel", scale=0.2)
+                bias = rnd.bias(Co)
+                add = ops.Act(rnd(B, Ho, Wo, Co, role="addend"))
                 # Conv2D forward: plain, with addend, with column statistics
                 y = ops.Act(torch.full((B, Ho, Wo, Co + 8), 3.0, dtype=torch.bfloat16, device=DEV), 0, Co)
                 ops.conv2d_fwd(g, x, w, bias, y, addend=add)
@@ -884,12 +1202,12 @@ def test_pw1x1_kernel_against_the_tap_table_kernel_and_the_oracle(U, case):
                 gy = ops.Act(rnd(B, Ho, Wo, Co))
                 dx = ops.Act(torch.full((B, H, W, Ci), 5.0, dtype=torch.bfloat16, device=DEV))
                 ops.conv2d_dgrad(g, gy, wt, dx)
-                acc0 = rnd(B, H, W, Ci)
+                acc0 = rnd(B, H, W, Ci, role="addend")
                 dacc = ops.Act(acc0.clone())
                 ops.conv2d_dgrad(g, gy, wt, dacc, addend=dacc)
                 # Conv2DTranspose(Ci -> Co, 1x1, stride s) on the H x W grid: forward (+ statistics), data gradient
                 gt = ops.geom(B, H, W, Ci, Co, 1, s)
-                wtr, wprim = (rnd(Co, 1, Ci).float() * 0.2).to(torch.bfloat16), (rnd(Ci, 1, Co).float() * 0.2).to(torch.bfloat16)
+                wtr, wprim = rnd(Co, 1, Ci, role="kernel", scale=0.2), rnd(Ci, 1, Co, role="kernel", scale=0.2)
                 yt = ops.Act(torch.empty((B, H * s, W * s, Co), dtype=torch.bfloat16, device=DEV))
                 rows_t = ops.conv2d_transpose_colstat_rows(gt, x)
                 assert rows_t > 0
@@ -901,7 +1219,7 @@ def test_pw1x1_kernel_against_the_tap_table_kernel_and_the_oracle(U, case):
                 torch.cuda.synchronize()
                 res.append(dict(y=y.base.clone(), y2=y2.base.clone(), cs=cst.double().sum(0), dx=dx.base.clone(), dacc=dacc.base.clone(),
                                 acc0=acc0, yt=yt.base.clone(), cst=cst_t.double().sum(0), dxt=dxt.base.clone(), x=x, w=w, wtr=wtr,
-                                bias=bias, add=add.base.clone()))
+                                bias=bias, add=add.base.clone(), gy=gy.base, wt=wt, gyt=gyt.base, wprim=wprim))
             out[on] = res
     finally:
         ops.set_config(**old)
@@ -917,13 +1235,32 @@ def test_pw1x1_kernel_against_the_tap_table_kernel_and_the_oracle(U, case):
         s = s_i + 1
         xo = a["x"].base[..., :Ci].double().cpu().permute(0, 3, 1, 2)
         w_hwio = a["w"].double().cpu().view(Co, 1, 1, Ci).permute(1, 2, 3, 0)
-        want = R.conv2d_same(xo, w_hwio, a["bias"].double().cpu(), s) + a["add"].double().cpu().permute(0, 3, 1, 2)
+        conv = R.conv2d_same(xo, w_hwio, a["bias"].double().cpu(), s)
+        want = conv + a["add"].double().cpu().permute(0, 3, 1, 2)
         got = a["y"][..., :Co].double().cpu().permute(0, 3, 1, 2)
         assert float((got - want).abs().max()) <= 1e-2 * float(want.abs().max())
         k_hwoi = a["wtr"].double().cpu().view(Co, 1, 1, Ci).permute(1, 2, 0, 3)     # [kh,kw,O,I]
         want_t = R.conv2d_transpose_same(xo, k_hwoi, a["bias"].double().cpu(), s)
         got_t = a["yt"].double().cpu().permute(0, 3, 1, 2)
         assert float((got_t - want_t).abs().max()) <= 1e-2 * float(want_t.abs().max())
+        if exact:
+            # the data gradients: dx = adjoint of the convolution whose kernel is wt [Ci][1][Co] (an independent tensor), and the
+            # adjoint of the transposed convolution whose primary kernel is wprim [Ci][1][Co]
+            x0 = torch.zeros_like(xo).requires_grad_(True)
+            (R.conv2d_same(x0, a["wt"].double().cpu().view(Ci, 1, 1, Co).permute(1, 2, 0, 3), None, s) * nchw64(a["gy"])).sum().backward()
+            x1 = torch.zeros_like(xo).requires_grad_(True)
+            (R.conv2d_transpose_same(x1, a["wprim"].double().cpu().view(Ci, 1, 1, Co).permute(1, 2, 3, 0), torch.zeros(Co, dtype=torch.float64), s) *
+             nchw64(a["gyt"])).sum().backward()
+            addn, acc0 = nchw64(a["add"]), nchw64(a["acc0"])
+            inputs = {n: (a[n].double().cpu() if n not in ("x",) else xo, True) for n in ("x", "w", "wt", "wtr", "wprim", "gy", "gyt", "add", "acc0")}
+            inputs["bias"] = (a["bias"].double().cpu(), False)
+            ties = X.check_exactness_conditions(inputs, X.conv_abs_bound(max(Ci, Co)), conv, addn, what=f"pw1x1 {case} stride {s}")
+            ties += X.count_ties(conv) + X.count_ties(x0.grad) + X.count_ties(x0.grad, acc0) + X.count_ties(want_t) + X.count_ties(x1.grad)
+            assert ties > 0                  # over the six outputs; the sums of 8 .. 256 products alone stay among the exact bf16 integers
+            X.note_ties(ties)
+            for k, want_k in (("y", X.expected_bf16(conv, addn)), ("y2", X.expected_bf16(conv)), ("dx", X.expected_bf16(x0.grad)),
+                              ("dacc", X.expected_bf16(x0.grad, acc0)), ("yt", X.expected_bf16(want_t)), ("dxt", X.expected_bf16(x1.grad))):
+                exact_act(a[k][..., :want_k.shape[1]], want_k, f"pw1x1 {k} {case} stride {s}", tile=(1, 128))
 
 
 def test_sgd_and_nadam_steps_against_the_oracle(U):
@@ -964,33 +1301,35 @@ def test_sgd_and_nadam_steps_against_the_oracle(U):
         U.Trainer(eng, optimizer="lamb")
 
 
-@pytest.mark.parametrize("case", [(4, 36, 40, 128, 128, 3, 1), (3, 18, 20, 64, 96, 3, 1), (5, 9, 10, 256, 128, 3, 1), (2, 20, 24, 64, 128, 6, 1),
+@X.parametrize_kinds("case", [(4, 36, 40, 128, 128, 3, 1), (3, 18, 20, 64, 96, 3, 1), (5, 9, 10, 256, 128, 3, 1), (2, 20, 24, 64, 128, 6, 1),
                                   (3, 18, 20, 64, 64, 6, 2), (2, 9, 11, 32, 64, 3, 2), (2, 12, 16, 24, 40, 5, 1)])
-def test_small_problem_tap_table_kernel_equals_the_general_one(U, case):
+def test_small_problem_tap_table_kernel_equals_the_general_one(U, case, data):
     """igemm2 (64-pixel tiles, two K chunks in flight: the reference geometry's small levels, main_training.py:27; 6 x 6 kernels,
     dl_models/u_net.py:40-45) against the general tap-table kernel on the same layers: the same MFMA chain over the same K order,
     so identical bits - Conv2D forward (bias, addend, fused column statistics), data gradient, Conv2DTranspose forward and data
-    gradient (stride 2: the four parity classes in one grid), odd sizes, channel counts that are not multiples of 64."""
-    _tap_table_ab(U, case, "igemm2", {})
+    gradient (stride 2: the four parity classes in one grid), odd sizes, channel counts that are not multiples of 64.
+    data = "int": the five output tensors also equal the oracle's in every element (k = 5, k = 6 at stride 2 and the odd sizes meet
+    the oracle at kernel level here)."""
+    _tap_table_ab(U, case, "igemm2", {}, data)
 
 
-def _tap_table_ab(U, case, switch, fixed):
+def _tap_table_ab(U, case, switch, fixed, data="uniform"):
     ops = U.ops
+    exact = data == "int"
     B, H, W, Ci, Co, k, s = case
-    gen = torch.Generator(device=DEV); gen.manual_seed(H * 100 + Ci + k)
-    rnd = lambda *sh: ((torch.rand(sh, device=DEV, generator=gen) - 0.5) * 2).to(torch.bfloat16)
+    rnd = Draw(data, H * 100 + Ci + k, f"tt{case}")
     old = ops.get_config()
     out = {}
     try:
         for on in (1, 0):
             ops.set_config(**{switch: on}, conv3x3=0, conv3x3g_pair=0, conv3x3d=0, upconv3x3g=0, upconv3x3q=0, **fixed)     # everything on the tap-table path
-            gen.manual_seed(H * 100 + Ci + k)
+            rnd.reseed()
             g = ops.geom(B, H, W, Ci, Co, k, s)
             Ho, Wo = -(-H // s), -(-W // s)
             x = ops.Act(rnd(B, H, W, Ci + 8), 0, Ci)
-            w, wt = (rnd(Co, k * k, Ci).float() * 0.2).to(torch.bfloat16), (rnd(Ci, k * k, Co).float() * 0.2).to(torch.bfloat16)
-            bias = torch.rand(Co, device=DEV, generator=gen) - 0.5
-            add = ops.Act(rnd(B, Ho, Wo, Co))
+            w, wt = rnd(Co, k * k, Ci, role="kernel", scale=0.2), rnd(Ci, k * k, Co, role="kernel", scale=0.2)
+            bias = rnd.bias(Co)
+            add = ops.Act(rnd(B, Ho, Wo, Co, role="addend"))
             y = ops.Act(torch.full((B, Ho, Wo, Co + 8), 3.0, dtype=torch.bfloat16, device=DEV), 0, Co)
             ops.conv2d_fwd(g, x, w, bias, y, addend=add)
             rows = ops.conv2d_colstat_rows(g, 0, x)
@@ -1006,7 +1345,7 @@ def _tap_table_ab(U, case, switch, fixed):
             ops.conv2d_dgrad(g, gy, wt, dx)
             # the transposed layer Ci -> Co on the H x W grid
             gt = ops.geom(B, H, W, Ci, Co, k, s)
-            wtr, wprim = (rnd(Co, k * k, Ci).float() * 0.2).to(torch.bfloat16), (rnd(Ci, k * k, Co).float() * 0.2).to(torch.bfloat16)
+            wtr, wprim = rnd(Co, k * k, Ci, role="kernel", scale=0.2), rnd(Ci, k * k, Co, role="kernel", scale=0.2)
             yt = ops.Act(torch.empty((B, H * s, W * s, Co), dtype=torch.bfloat16, device=DEV))
             ops.conv2d_transpose_fwd(gt, x, wtr, bias, yt)
             gyt = ops.Act(rnd(B, H * s, W * s, Co))
@@ -1015,6 +1354,7 @@ def _tap_table_ab(U, case, switch, fixed):
             torch.cuda.synchronize()
             out[on] = dict(y=y.base.clone(), y2=y2.base.clone(), cs=None if cst is None else cst.double().sum(0), dx=dx.base.clone(),
                            yt=yt.base.clone(), dxt=dxt.base.clone(), rows=rows)
+            ins = dict(x=x.base[..., :Ci], w=w, wt=wt, wtr=wtr, wprim=wprim, gy=gy.base, gyt=gyt.base, add=add.base, bias=bias)
     finally:
         ops.set_config(**old)
     for kk in ("y", "y2", "dx", "yt", "dxt"):
@@ -1025,6 +1365,24 @@ def _tap_table_ab(U, case, switch, fixed):
         close(out[1]["cs"][:, 0], td.sum(dim=(0, 1, 2)), 2e-6, "colstat sum")
         close(out[1]["cs"][:, 1], (td * td).sum(dim=(0, 1, 2)), 2e-6, "colstat sum of squares")
         assert out[1]["rows"] >= out[0]["rows"]                   # 64-pixel tiles: at least as many rows as the 128-pixel kernel
+    if exact:
+        d = lambda t: t.double().cpu()
+        xo, addn, b64 = nchw64(ins["x"]), nchw64(ins["add"]), d(ins["bias"])
+        conv = R.conv2d_same(xo, d(ins["w"]).view(Co, k, k, Ci).permute(1, 2, 3, 0), b64, s)
+        x0 = torch.zeros_like(xo).requires_grad_(True)         # dx: the adjoint of the convolution whose kernel is wt [Ci][k * k][Co]
+        (R.conv2d_same(x0, d(ins["wt"]).view(Ci, k, k, Co).permute(1, 2, 0, 3), None, s) * nchw64(ins["gy"])).sum().backward()
+        conv_t = R.conv2d_transpose_same(xo, d(ins["wtr"]).view(Co, k, k, Ci).permute(1, 2, 0, 3), b64, s)
+        x1 = torch.zeros_like(xo).requires_grad_(True)         # dxt: the adjoint of the transposed layer whose primary kernel is wprim
+        (R.conv2d_transpose_same(x1, d(ins["wprim"]).view(Ci, k, k, Co).permute(1, 2, 3, 0), torch.zeros(Co, dtype=torch.float64), s) *
+         nchw64(ins["gyt"])).sum().backward()
+        inputs = {n: (d(t), n != "bias") for n, t in ins.items()}
+        ties = X.check_exactness_conditions(inputs, X.conv_abs_bound(k * k * max(Ci, Co)), conv, addn, what=f"tap-table {case}")
+        ties_rest = X.count_ties(conv) + X.count_ties(x0.grad) + X.count_ties(conv_t) + X.count_ties(x1.grad)
+        assert ties > 0 and ties_rest > 0
+        X.note_ties(ties + ties_rest)
+        for kk, want in (("y", X.expected_bf16(conv, addn)), ("y2", X.expected_bf16(conv)), ("dx", X.expected_bf16(x0.grad)),
+                         ("yt", X.expected_bf16(conv_t)), ("dxt", X.expected_bf16(x1.grad))):
+            exact_act(out[1][kk][..., :want.shape[1]], want, f"tap-table {kk} {case}", tile=(1, 64))
 
 
 def test_parked_split_k_reductions_equal_the_immediate_ones_bit_for_bit(U):

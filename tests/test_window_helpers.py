@@ -32,3 +32,20 @@ def test_conv_transpose_window_helper():
     T._convT_windows(y, x, k, b, "self")
     with pytest.raises(AssertionError):
         T._convT_windows(torch.roll(y, 1, 1), x, k, b, "shifted")
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+def test_conv_window_helper_on_integer_data(stride):
+    """data = "int": the helper accepts the oracle's bf16 rounding and nothing else - one element of a compared window off by its
+    last bf16 bit is rejected (the uniform kind's tolerance passes it), and the windows hold exact ties."""
+    import exact_data as X
+    x = X.acts("wx", (32, 96, 128, 40))
+    w, b = X.kernels("ww", (3, 3, 40, 8)), X.biases("wb", (8,))
+    y = X.expected_bf16(R.conv2d_same(x.permute(0, 3, 1, 2), w, b, stride)).permute(0, 2, 3, 1).contiguous()
+    T._conv_windows(y, x, w, b, stride, "self", data="int")
+    off = y.clone()
+    v = off[0, 3, 5, 2]
+    off[0, 3, 5, 2] = (v.float().view(torch.int32) + 0x10000).view(torch.float32).double()      # the next bf16 value
+    T._conv_windows(off, x, w, b, stride, "one bf16 step, uniform kind")
+    with pytest.raises(AssertionError):
+        T._conv_windows(off, x, w, b, stride, "one bf16 step", data="int")
