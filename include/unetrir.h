@@ -157,7 +157,9 @@ int unetrir_transpose_weight_f32(const float* w, float* wt, int N, int T, int C,
  *      scale = gamma*rsqrt(var+eps), shift = beta - mean*scale into `affine[2*C]`,
  *      mean and rstd into `saved[2*C]`, and updates the moving statistics
  *      (moving = momentum*moving + (1-momentum)*batch, unbiased variance) when non-NULL.
- *      ws >= unetrir_bn_ws_bytes(P, C). */
+ *      ws >= unetrir_bn_ws_bytes(P, C): ONE size per (P, C), sufficient for the fp32 and the bf16 form of every entry point
+ *      that refers to it (bn_stats, bn_bwd, bn_bwd_junction, colsum) - the larger of the two kernels' needs; no kernel writes
+ *      behind it. */
 size_t unetrir_bn_ws_bytes(long long P, int C);
 int unetrir_bn_stats_f32(const float* x, int ldx, long long P, int C, const float* gamma,
                          const float* beta, float eps, float momentum, float* moving_mean,

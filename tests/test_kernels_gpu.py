@@ -849,19 +849,22 @@ def test_dense_split_k(U, B, K, N, data):
         assert torch.equal(again.base[..., :K], dxa.base[..., :K])        # fixed-order reduction: bit-reproducible
 
 
-@pytest.mark.parametrize("case", [(2, 40, 70, 64, 160, 3, 1), (1, 33, 64, 96, 96, 3, 1), (2, 30, 64, 32, 64, 3, 1), (1, 16, 32, 16, 24, 3, 1),
-                                  (5, 16, 16, 96, 128, 3, 1), (4, 24, 12, 96, 160, 3, 1),
-                                  (2, 21, 60, 64, 64, 3, 1), (3, 64, 96, 64, 64, 3, 1), (16, 24, 512, 64, 64, 3, 1),
-                                  (2, 21, 60, 32, 32, 3, 1), (3, 64, 96, 32, 32, 3, 1), (16, 24, 512, 32, 32, 3, 1)])
-def test_conv_fused_column_statistics_bf16(U, case, monkeypatch):
+@X.parametrize_kinds("case", [(2, 40, 70, 64, 160, 3, 1), (1, 33, 64, 96, 96, 3, 1), (2, 30, 64, 32, 64, 3, 1), (1, 16, 32, 16, 24, 3, 1),
+                              (5, 16, 16, 96, 128, 3, 1), (4, 24, 12, 96, 160, 3, 1),
+                              (2, 21, 60, 64, 64, 3, 1), (3, 64, 96, 64, 64, 3, 1), (16, 24, 512, 64, 64, 3, 1),
+                              (2, 21, 60, 32, 32, 3, 1), (3, 64, 96, 32, 32, 3, 1), (16, 24, 512, 32, 32, 3, 1)])
+def test_conv_fused_column_statistics_bf16(U, case, data, monkeypatch):
     """Conv epilogue statistics (conv3x3g / conv3x3r<4,1>): the per-tile (sum, sum of squares) rows must add up to the
     statistics of the bf16 tensor the same launch stored, forward and data gradient, and BN statistics / bias gradients
-    derived from them must match the stand-alone kernels."""
+    derived from them must match the stand-alone kernels.
+    data = "int" (the forward table only): the stored outputs are integers and every per-tile sum is an integer below 2^24, exact
+    in fp32, so the first column summed over the rows EQUALS the integer column sum of the stored tensor; the sums of squares
+    exceed 2^24 and keep their tolerance."""
     ops = U.ops
     B, H, W, Ci, Co, k, s = case
     if W <= 16:
         ops.set_config(conv3x3g_pair=2)
-    x, w, b = conv_data(case)
+    x, w, b = conv_data(case, data=data)
     g = ops.geom(B, H, W, Ci, Co, k, s)
     xa = ops.Act(to_nhwc_bf16(q16(x), Ci, 0, DEV))
     wf = torch.empty((Co, 9, Ci), dtype=torch.bfloat16, device=DEV)
@@ -889,6 +892,11 @@ def test_conv_fused_column_statistics_bf16(U, case, monkeypatch):
     ops.conv2d_fwd_colstat(g, xa, wf, b.float().to(DEV), ya, cst2)
     torch.cuda.synchronize()
     assert torch.equal(cst, cst2)
+    if data == "int":
+        # largest |output| times 32 columns x H rows x 2 images: more pixels than any tile or strip segment of these kernels holds
+        assert torch.equal(yd, yd.round()) and X.conv_abs_bound(9 * Ci, has_addend=False) * 64 * H < X.EXACT_LIMIT
+        X.assert_exact(tot[:, 0], yd.sum(dim=(0, 1, 2)), f"colstat sums on integer data {case}")
+        return
     # BN statistics from the rows == the stand-alone kernel
     gamma = torch.rand(Co, device=DEV) + 0.5
     beta = torch.rand(Co, device=DEV) - 0.5

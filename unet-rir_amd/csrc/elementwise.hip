@@ -842,8 +842,15 @@ extern "C" {
 
 size_t unetrir_bn_ws_bytes(long long P, int C) {
     if (P <= 0 || C <= 0) return 0;
-    const ChanPlan pl = chan_plan(P, C);
-    size_t b = ((size_t)pl.nslab * C * 2) * sizeof(double) + (size_t)2 * C * sizeof(float);
+    // One size for both element types: the fp32 entry points plan with 4-channel vectors, the bf16 ones with 8, and past
+    // C = 1024 the two plans differ in the number of channel groups and therefore of slabs (C = 2048, P = 16384: 1024 against
+    // 2048).  The larger of the two covers whichever kernel runs (bf16 needs C % 8 == 0; chan_ok refuses it otherwise).
+    int nslab = chan_plan(P, C, VecOf<float>::N).nslab;
+    if (C % VecOf<__bf16>::N == 0) {
+        const int n8 = chan_plan(P, C, VecOf<__bf16>::N).nslab;
+        if (n8 > nslab) nslab = n8;
+    }
+    size_t b = ((size_t)nslab * C * 2) * sizeof(double) + (size_t)2 * C * sizeof(float);
     return b;
 }
 
