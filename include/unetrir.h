@@ -517,6 +517,45 @@ int unetrir_dropout_mask_f32(float* mask, long long n, float p, unsigned long lo
                              unetrir_stream_t stream);
 int unetrir_index_to_i32(const void* idx, int elem_bytes, long long n, int* out, unetrir_stream_t stream);
 
+/* ---- the variational autoencoder (dl_models/vae.py; main_training.py:142-152, :192-201, :257-265, :286-288): what it adds to the
+ *      Autoencoder's graph.  fp32; L (latent_space_dim) a multiple of 4; mu / log_var / z / dz / dmu / dlv are [B][L] matrices with
+ *      row strides ld_* >= L (multiples of 4), eps is dense [B][L].  Null pointers, B or L <= 0, L % 4 != 0 or a row stride
+ *      shorter than L return UNETRIR_EINVAL before the device is touched.
+ *
+ * unetrir_normal_f32: the draw of SamplingLayer.call (vae.py:38, tf.keras.backend.random_normal(shape=(batch, dim))) as a
+ *   counter-based generator - element i of draw (seed, step) is a fixed function of (seed, step, i), so a step is reproducible
+ *   and a shorter draw is a prefix of a longer one.  The exact recipe (uint64 arithmetic wraps; GOLD = 0x9E3779B97F4A7C15,
+ *   TAG = 0x4E4F524D414C3634; mix64 is the splitmix64 finaliser  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^ z >> 31):
+ *       key = mix64(mix64(seed * GOLD + step) ^ TAG)      the inner hash is the key of unetrir_dropout_mask_f32 for the same
+ *                                                         (seed, step): the noise key is a hash of it, never equal to it
+ *       r   = mix64(key + GOLD * (i + 1))                 one hash per output
+ *       u1  = ((r >> 40) + 1) / 2^24   in (0, 1]          top 24 bits
+ *       u2  = ((r >> 16) & 0xFFFFFF) / 2^24   in [0, 1)   the next 24 bits
+ *       out = sqrt(-2 ln u1) * cos(2 pi u2)               Box-Muller in fp32: sqrtf(-2.f * logf(u1)) * cospif(2 u2)
+ *   |out| <= sqrt(48 ln 2) = 5.77 (u1 = 2^-24).
+ * unetrir_normal_dev_f32: the same draw with draw number *step_base + step_offset read from device memory (step_base = state + 2
+ *   of unetrir_step_advance) - the contract of unetrir_dropout_mask_dev_f32: a captured step draws fresh noise on every replay.
+ * unetrir_vae_sample_kl_fwd_f32: z = mu + exp(0.5 log_var) eps (vae.py:34-39) and the KL term:
+ *   kl_out[1] = sum over all B * L elements of -0.5 (1 + log_var - mu^2 - exp(log_var))  (kl_loss_object, main_training.py:192-194;
+ *   the train_loss_kl / val_loss_kl metrics average it, :286-288), kl_out[0] = inv_global_batch * kl_out[1] (compute_kl_loss,
+ *   :196-201).  One workgroup, fp64 accumulation in a fixed order: two runs are bit-identical.  log_var is not clamped (the
+ *   reference does not).
+ * unetrir_vae_sample_kl_bwd_f32: d(loss)/d(mu), d(loss)/d(log_var) of the two Dense heads (vae.py:466-468) from dz = d(data term)/dz:
+ *   dmu = dz + inv_global_batch mu;  dlv = dz 0.5 exp(0.5 log_var) eps + inv_global_batch 0.5 (exp(log_var) - 1).  Writes (never
+ *   accumulates) both.
+ * unetrir_vae_loss_add_f32: loss_out[0] += kl_out[0] - `loss += compute_kl_loss(mean, log_var)` (main_training.py:264-265) onto the
+ *   scalar unetrir_sigmoid_loss_* wrote. */
+int unetrir_normal_f32(float* out, long long n, unsigned long long seed, unsigned long long step, unetrir_stream_t stream);
+int unetrir_normal_dev_f32(float* out, long long n, unsigned long long seed, const unsigned long long* step_base,
+                           unsigned long long step_offset, unetrir_stream_t stream);
+int unetrir_vae_sample_kl_fwd_f32(const float* mu, int ld_mu, const float* log_var, int ld_lv, const float* eps, int B, int L,
+                                  float inv_global_batch, float* z, int ld_z, float* kl_out, unetrir_stream_t stream);
+int unetrir_vae_sample_kl_bwd_f32(const float* mu, int ld_mu, const float* log_var, int ld_lv, const float* eps, const float* dz,
+                                  int ld_dz, int B, int L, float inv_global_batch, float* dmu, int ld_dmu, float* dlv, int ld_dlv,
+                                  unetrir_stream_t stream);
+int unetrir_vae_loss_add_f32(const float* kl_out, float* loss_out, unetrir_stream_t stream);
+
 /* ---- input staging for a host-fed train step (DataGenerator.__getitem__, datageneratorv2.py:64-102, hands over host arrays):
  *      for k < n: memcpy src[k] -> pinned[k] (page-locked staging owned by the caller), then an asynchronous host -> device copy
  *      pinned[k] -> dev[k] on `stream`.  One call per batch from the producer thread: the foreign call runs without the

@@ -5,8 +5,9 @@
     python scripts/evaluate.py --checkpoint CKPT_DIR --filters 32 --kernels 3 --data BATCH_DIR --out REPORT_DIR
     python scripts/evaluate.py --synthetic 8 --out REPORT_DIR            # no dataset, no checkpoint: random weights and data
 
---load         a folder written by `UNet.save` / `ResAE.save` / `Autoencoder.save` (--arch picks the class)
+--load         a folder written by `UNet.save` / `ResAE.save` / `Autoencoder.save` / `VAE.save` (--arch picks the class)
 --checkpoint   a `CheckpointManager` directory; the latest checkpoint is restored into a U-Net built from --filters / --kernels
+               (--arch vae: into the VAE of rir_generation.py:78-87, latent size --latent)
 --data         a directory of .npz files, one test batch each: spec_in, spec_out fp32 [B, H, W, 2] (or [B, 2, H, W]), emb int
                [B, 2, 16], wav_true fp32 [B, T], room = B room names (or indices into evaluate.ROOMS)
 --synthetic N  N batches of `synthetic_batches`, which yields no waveforms: wav_true is the reconstruction of spec_out
@@ -25,11 +26,22 @@ from unet_rir_amd.features import PostProcess
 
 
 def build_model(a, dev):
-    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder}[a.arch]
+    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder, "vae": U.VAE}[a.arch]
     if a.load:
         return cls.load(a.load, batch_size=a.batch, device=dev)
+    if a.arch == "vae":        # as rir_generation.py:78-87 builds it (latent 32 there, 64 in main_training.py:143-152: --latent)
+        m = U.VAE((a.height, a.width, 2), (2, 16), conv_filters=(64, 128, 256, 512), conv_kernels=(3, 3, 3, 3),
+                  conv_strides=(2, 2, 2, 2), latent_space_dim=a.latent, n_neurons=32 * 64, name=a.name, batch_size=a.batch, device=dev,
+                  dropout=False)
+        if a.checkpoint:
+            mgr = U.CheckpointManager(U.Trainer(m.engine, dropout=False), a.checkpoint)
+            if mgr.latest_checkpoint is None:
+                raise SystemExit(f"no checkpoint in {a.checkpoint}")
+            mgr.restore()
+            print("restored", mgr.latest_checkpoint)
+        return m
     if a.arch != "unet":
-        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net; use --load for the autoencoders")
+        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net or a VAE; use --load for the other autoencoders")
     m = U.UNet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, kernels=a.kernels, batch_size=a.batch, device=dev,
                dropout=False)
     if a.checkpoint:
@@ -64,7 +76,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--load")
     ap.add_argument("--checkpoint")
-    ap.add_argument("--arch", choices=("unet", "resae", "ae"), default="unet")
+    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae"), default="unet")
+    ap.add_argument("--latent", type=int, default=32, help="latent_space_dim of --arch vae built without --load")
     ap.add_argument("--filters", type=int, default=32)
     ap.add_argument("--kernels", type=int, default=3)
     ap.add_argument("--height", type=int, default=144)

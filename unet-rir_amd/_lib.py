@@ -193,6 +193,13 @@ _SIGS = {
     "unetrir_step_advance": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, c_stream]),
     "unetrir_adam_dev_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_longlong, c_f32p, c_stream]),
     "unetrir_dropout_mask_dev_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_float, C.c_ulonglong, C.c_void_p, C.c_ulonglong, c_stream]),
+    "unetrir_normal_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_ulonglong, c_stream]),
+    "unetrir_normal_dev_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_void_p, C.c_ulonglong, c_stream]),
+    "unetrir_vae_sample_kl_fwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_float, c_f32p, C.c_int,
+                                                c_f32p, c_stream]),
+    "unetrir_vae_sample_kl_bwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_vae_loss_add_f32": (C.c_int, [c_f32p, c_f32p, c_stream]),
     "unetrir_prof_enable": (C.c_int, [C.c_int]),
     "unetrir_prof_collect": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }

@@ -1232,13 +1232,7 @@ __global__ void bn_inference_affine_kernel(const float* __restrict__ gamma, cons
     affine[C + c] = (beta ? beta[c] : 0.f) - mm[c] * scale;
 }
 
-// counter-based generator: element i of draw (seed, step) is a fixed function of (seed, step, i) - splitmix64 finaliser
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
+// counter-based generator: element i of draw (seed, step) is a fixed function of (seed, step, i) - mix64 (kernels.h)
 __global__ void dropout_mask_kernel(float* __restrict__ mask, long long n, float p, float keep_scale, unsigned long long seed,
                                     unsigned long long step, const unsigned long long* __restrict__ step_dev) {
     if (step_dev) step += *step_dev;          // draw number from device memory (a captured HIP graph replays the same arguments)

@@ -214,6 +214,14 @@ bool pw1x1_applies(const PwArgs& a);
 long long pw1x1_colstat_rows(const PwArgs& a);
 int launch_pw1x1_bf16(const PwArgs& a, hipStream_t s);   // H, W = coarse (input) grid; output 2H x 2W
 
+// splitmix64 finaliser: the hash of the counter-based generators - dropout_mask_kernel (elementwise.hip) and normal_kernel (vae.hip,
+// which also holds the sampling / KL kernels of the variational autoencoder; their entry points are in include/unetrir.h)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
 // scoring of generated impulse responses (evalmetrics.hip); arguments are validated by the entry points in api.hip
 int launch_eval_metrics(const float* pred, const float* target, const float* phase_ref, int B, int H, int W, const float* wav_pred,
                         const float* wav_true, int T, int n50, double* out, hipStream_t s);

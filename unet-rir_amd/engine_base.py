@@ -78,6 +78,7 @@ class DeviceCounters:
     once into a HIP graph and replayed (trainer.Trainer(graph=True)).  The host mirrors (`adam_t`, `dropout_step`) are kept in
     step either way; checkpoints hold the host values."""
     n_dropout_draws = 1          # dropout masks drawn per step
+    n_noise_draws = 0            # draws of the same counter made in every forward pass, with or without Dropout (vae.VAEEngine: eps)
     # compute_loss switches (main_training.py:38-39, :214-222); set through trainer.Trainer(sigmoid_loss=, diff_loss=, beta=)
     loss_diff = False            # diff_loss: the phase target is phase_true - phase of the network input
     loss_phase_weight = None     # sigmoid_loss: fp32 [W] column weights of the phase term (device tensor)

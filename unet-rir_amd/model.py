@@ -5,6 +5,7 @@ whose forward and backward run on the HIP engines.
              hand-scheduled ``UNetEngine``, fp32 or bf16 storage, optional side-stream schedule; 1-3: ``UNetGraphEngine``)
   ``ResAE``  dl_models/res_ae.py:35-70 - the residual autoencoder, with ``.encoder`` / ``.decoder`` / ``.model``
   ``Autoencoder``  dl_models/autoencoder.py:34-62 - the plain conv / conv-transpose autoencoder, same surface
+  ``VAE``    dl_models/vae.py:41-77    - the variational autoencoder: ``.encoder`` returns (z, mean, log_var)
 
 Both keep the reference's call shape ``model.model([spec_in, emb], training=...)`` (NHWC, main_training.py:261),
 ``model.model.trainable_variables`` / ``.losses``, ``summary()``, ``save()`` / ``load()`` / ``load_weights()``,
@@ -39,6 +40,7 @@ from .ae import AutoencoderEngine
 from .engine import L2_COEF, UNetEngine
 from .resae import ResAEEngine
 from .unet_graph import UNetGraphEngine
+from .vae import VAEEngine
 
 
 class _ModelFunction(torch.autograd.Function):
@@ -485,3 +487,33 @@ class ResAE(_AEFamily):
                  name="ResAE", **kw):
         super().__init__(input_shape, inf_vector_shape, conv_filters, conv_kernels, conv_strides, latent_space_dim, n_neurons,
                          name, **kw)
+
+
+class VAE(_AEFamily):
+    """Variational autoencoder of the reference (dl_models/vae.py:41-77; main_training.py:142-152 builds it with filters
+    (64,128,256,512), kernels 3, strides 2, latent 64, n_neurons 2048).  Constructor arguments keep the reference's names and
+    order; ``batch_size``, ``device``, ``n_replicas``, ``dropout``, ``dtype``, ``overlap`` are additions.
+
+    ``model.encoder([spec, emb], training=...)`` returns ``(z, mean, log_var)`` and ``model.decoder(z)`` the prediction, as the
+    train step of main_training.py:257-259 calls them.  The sampling layer draws eps on every call, training or not (vae.py:34-39
+    has no ``training`` switch).  Training runs through ``Trainer.step`` / ``fit`` (the KL term and its gradient live in the engine's
+    fused kernels); autograd through the module is not available for this model, so ``forward`` needs ``torch.no_grad()``."""
+    ENGINE = VAEEngine
+
+    def __init__(self, input_shape, inf_vector_shape, conv_filters, conv_kernels, conv_strides, latent_space_dim, n_neurons,
+                 name="VAE", **kw):
+        self.reconstruction_loss_weight = 100000           # dl_models/vae.py:67 (used by the legacy combined loss only)
+        super().__init__(input_shape, inf_vector_shape, conv_filters, conv_kernels, conv_strides, latent_space_dim, n_neurons,
+                         name, **kw)
+
+    def forward(self, spec, emb, dropout_mask=None):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("VAE: the module's autograd bridge carries dL/dprediction only, not the KL term's gradient into "
+                                      "the mu / log_variance heads - train with Trainer.step / fit, call forward under torch.no_grad()")
+        return super().forward(spec, emb, dropout_mask)
+
+    def compile_and_fit(self, *args, **kwargs):
+        """dl_models/vae.py:98-140 compiles the legacy combined loss (reconstruction_loss_weight * MSE + KL per sample); that recipe
+        is not implemented, and fitting plain MSE under its name would be a different model."""
+        raise NotImplementedError("VAE.compile_and_fit (the legacy Keras recipe with its combined loss) is not implemented: "
+                                  "use Trainer / fit, the train step of main_training.py")

@@ -646,6 +646,41 @@ def step_advance(state, cfg, hyper, n_draws, advance_t=True):
     check(_lib.lib().unetrir_step_advance(_p(state), _p(cfg), _p(hyper), int(n_draws), int(bool(advance_t)), _stream()), "step_advance")
 
 
+# ---- variational autoencoder (dl_models/vae.py) -------------------------------------------------------
+
+def normal(out, seed, step):
+    """Standard-normal noise of SamplingLayer.call (dl_models/vae.py:38), draw number `step` of stream `seed` (the dropout masks'
+    draw counter; a key of its own)."""
+    check(_lib.lib().unetrir_normal_f32(_p(out), out.numel(), int(seed), int(step), _stream()), "normal")
+
+
+def normal_dev(out, seed, state, offset):
+    """normal() with draw number state[2] + offset read from device memory (state: the uint64 [3] of step_advance)."""
+    check(_lib.lib().unetrir_normal_dev_f32(_p(out), out.numel(), int(seed), C.c_void_p(state.data_ptr() + 16), int(offset), _stream()),
+          "normal_dev")
+
+
+def vae_sample_kl_fwd(mu: Act, log_var: Act, eps, inv_global_batch, z: Act, kl_out):
+    """z = mu + exp(0.5 log_var) eps (dl_models/vae.py:34-39) and the KL term (main_training.py:192-201): kl_out[1] the raw sum of
+    kl_loss_object over every element, kl_out[0] = kl_out[1] / global batch.  mu / log_var / z: [B,1,1,L] nodes; eps dense [B, L]."""
+    if eps.dtype != torch.float32 or not eps.is_contiguous() or eps.numel() != mu.B * mu.C:
+        raise ValueError(f"eps must be a contiguous float32 [{mu.B},{mu.C}] tensor")
+    check(_lib.lib().unetrir_vae_sample_kl_fwd_f32(_p(mu), mu.ld, _p(log_var), log_var.ld, _p(eps), mu.P, mu.C, float(inv_global_batch),
+                                                   _p(z), z.ld, _p(kl_out), _stream()), "vae_sample_kl_fwd")
+
+
+def vae_sample_kl_bwd(mu: Act, log_var: Act, eps, dz: Act, inv_global_batch, dmu: Act, dlv: Act):
+    """Backward of vae_sample_kl_fwd: dmu = dz + mu / gb, dlv = dz 0.5 exp(0.5 lv) eps + 0.5 (exp(lv) - 1) / gb (written, not added)."""
+    check(_lib.lib().unetrir_vae_sample_kl_bwd_f32(_p(mu), mu.ld, _p(log_var), log_var.ld, _p(eps), _p(dz), dz.ld, mu.P, mu.C,
+                                                   float(inv_global_batch), _p(dmu), dmu.ld, _p(dlv), dlv.ld, _stream()),
+          "vae_sample_kl_bwd")
+
+
+def vae_loss_add(kl_out, loss_out):
+    """loss += compute_kl_loss(mean, log_var) (main_training.py:264-265): loss_out[0] += kl_out[0] on the device."""
+    check(_lib.lib().unetrir_vae_loss_add_f32(_p(kl_out), _p(loss_out), _stream()), "vae_loss_add")
+
+
 def reset_tile_tickets():
     check(_lib.lib().unetrir_reset_tile_tickets(), "reset_tile_tickets")
 

@@ -247,7 +247,8 @@ class Trainer:
     def _step_body(self, spec_in, emb, spec_out, dropout_mask, with_reg):
         """The launches of one step (what a HIP graph captures)."""
         eng = self.engine
-        eng.begin_step(self._lr_now, n_draws=eng.n_dropout_draws if (dropout_mask is None and self.dropout) else 0)     # device counters only
+        # device counters only; an engine's own noise (VAE: eps of the sampling layer) is drawn whatever the Dropout setting
+        eng.begin_step(self._lr_now, n_draws=(eng.n_dropout_draws if (dropout_mask is None and self.dropout) else 0) + eng.n_noise_draws)
         if dropout_mask is None and self.dropout:
             dropout_mask = self._make_mask()
         gb = eng.B * self.world_size
@@ -322,7 +323,7 @@ class Trainer:
             self._graphs[with_reg] = g
         g.replay()
         eng.adam_t += 1                          # host mirrors of the device counters
-        eng._shared["dropout_step"] += eng.n_dropout_draws if self.dropout else 0
+        eng._shared["dropout_step"] += (eng.n_dropout_draws if self.dropout else 0) + eng.n_noise_draws
         eng.t_dirty = True
 
     def compute_loss(self, y_true, y_pred, lr=None):
@@ -454,11 +455,15 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         lr = lr_schedule(lr0, epoch, lr_exp_decay)
         tot = torch.zeros(4, dtype=torch.float64, device=eng.device)      # data loss, amplitude sum, phase sum, l2 terms
         nb = 0
+        has_kl = hasattr(eng, "kl_out")           # VAE: train_loss_kl / val_loss_kl (main_training.py:246-250, :286-288, :318-320)
+        ktot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_kl else None      # raw KL sums: training, validation
         eng.reg_loss()
         reg0 = eng.reg_out[0].double()           # l2 terms on the weights the first step of the epoch sees
         for spec_in, emb, spec_out in train_batches(epoch):
             trainer.step(spec_in, emb, spec_out, lr=lr)
             tot[:3] += eng.loss_out[:3].double()     # total data loss, amplitude term, phase term of this step (raw sums ~1e5: fp64)
+            if has_kl:
+                ktot[0] += eng.kl_out[1].double()
             nb += 1
         # the l2 terms drift over an epoch (Adam moves every weight by ~lr per step whatever the gradient's scale): the reported
         # mean takes the trapezoid of their value before the first and after the last step instead of nine reductions per step
@@ -468,16 +473,21 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         n = max(nb, 1)
         rec = {"epoch": epoch + 1, "lr": lr, "train_loss": float(tot[0] + tot[3]) / n,
                "train_amp": float(tot[1]) * per_elem / n, "train_phase": float(tot[2]) * per_elem / n}
+        if has_kl:         # tf.keras.metrics.Mean over every (b, l) element of kl_loss_object, across steps and replicas
+            per_kl = 1.0 / (eng.kl_elems * trainer.world_size)
+            rec["train_kl"] = float(reduce_(ktot[0:1].clone())[0]) * per_kl / n
         if val_batches is not None:
             vt = torch.zeros(3, dtype=torch.float64, device=eng.device)
             vb = 0
             saved_moving = None if val_updates_moving else {k: v.clone() for k, v in eng.moving.items()}
             for spec_in, emb, spec_out in val_batches(epoch):
                 eng.training = True
-                eng.begin_step(lr, n_draws=eng.n_dropout_draws if trainer.dropout else 0, forward_only=True)     # device counters only
+                eng.begin_step(lr, n_draws=(eng.n_dropout_draws if trainer.dropout else 0) + eng.n_noise_draws, forward_only=True)     # device counters only
                 mask = eng.make_dropout_mask() if trainer.dropout else None
                 eng.forward(spec_in, emb, dropout_mask=mask, target=spec_out, global_batch=eng.B * trainer.world_size, alpha=trainer.alpha)
                 vt += eng.loss_out[:3].double()
+                if has_kl:
+                    ktot[1] += eng.kl_out[1].double()
                 vb += 1
             if saved_moving is not None:
                 for k, v in saved_moving.items():
@@ -485,6 +495,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
             vt = reduce_(vt)
             m = max(vb, 1)
             rec.update(val_loss=float(vt[0]) / m, val_amp=float(vt[1]) * per_elem / m, val_phase=float(vt[2]) * per_elem / m)
+            if has_kl:
+                rec["val_kl"] = float(reduce_(ktot[1:2].clone())[0]) * per_kl / m
         if manager is not None and epoch % 2 == 0:
             rec["checkpoint"] = manager.save(epoch=epoch)
         history.append(rec)
