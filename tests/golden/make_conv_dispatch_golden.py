@@ -1,6 +1,7 @@
 """Generates tests/golden/conv_dispatch.json: which bf16 convolution kernel the library picks for every convolution layer of
 the benchmarked workloads, and how many rows of fused column statistics it reports, under the default kernel-selection switches,
-under each dispatch switch set to 0 on its own, and with conv3x3g_pair = 2.  Also tests/golden/wgrad_ws.json: the workspace the
+under each dispatch switch set to 0 on its own, and with conv3x3g_pair = 2; the same for the bf16 layers of main_training.py's
+Autoencoder and VAE at their own size, as the entry "ae_vae_reference_geometry" of the same file.  Also tests/golden/wgrad_ws.json: the workspace the
 library asks for every weight-gradient layer of the same workloads.
 
 The layers are collected from one train step of each workload on the simulated runtime (tests/sim_runtime.py) with the
@@ -15,6 +16,7 @@ geometry is asked of
     ws / ws_t              unetrir_conv2d_wgrad_ws_bytes / unetrir_conv2d_transpose_wgrad_ws_bytes
 
     python tests/golden/make_conv_dispatch_golden.py [libunetrir.so to ask instead of the in-tree build]
+    python tests/golden/make_conv_dispatch_golden.py --ae-vae-only     (re-records the "ae_vae_reference_geometry" entry alone)
 """
 import json
 import os
@@ -46,6 +48,12 @@ WORKLOADS = {
     "resae": lambda rt: U.ResAE((256, 256, 2), (2, 16), (32, 64, 128, 256), (3, 3, 3, 3), (2, 2, 2, 2), 32, 16 * 64, name="resae",
                                 batch_size=32, device="cpu", runtime=rt, dtype="bf16"),
 }
+# main_training.py's Autoencoder and VAE at their own size (144 x 160, batch 32, filters 64 ... 512, latent 64, n_neurons 2048): recorded
+# as an entry of its own, "ae_vae_reference_geometry", so that the lines recorded for the workloads above stay as they are
+AE_VAE_WORKLOADS = {
+    "ae": lambda rt: U.AutoencoderEngine(144, 160, 32, device="cpu", runtime=rt, dtype="bf16"),
+    "vae": lambda rt: U.VAEEngine(144, 160, 32, device="cpu", runtime=rt, dtype="bf16"),
+}
 CONV_CALLS = ("conv2d_fwd", "conv2d_fwd_colstat", "conv2d_dgrad", "conv2d_dgrad_colstat", "conv2d_transpose_fwd",
               "conv2d_transpose_fwd_colstat", "conv2d_transpose_dgrad")
 WGRAD_CALLS = ("conv2d_wgrad", "conv2d_transpose_wgrad")
@@ -53,33 +61,38 @@ WGRAD_CALLS = ("conv2d_wgrad", "conv2d_transpose_wgrad")
 KEEP = ("_elems", "_supported", "_rows", "_ws_bytes", "_table")
 
 
-def collect_layers():
+def collect_layers(workloads=None, bf16_only=False):
     """{(B, H, W, Cin, Cout, k, stride, ld)} over every convolution call of one train step of each workload, and
-    {(B, H, W, Cin, Cout, k, stride, ldx, lddy, transposed)} over every weight-gradient call."""
+    {(B, H, W, Cin, Cout, k, stride, ldx, lddy, transposed)} over every weight-gradient call.  bf16_only: leave out the calls on fp32
+    tensors (the Dense branch of the auto-encoders: its data gradient with an addend is a 1x1 convolution in fp32)."""
+    workloads = WORKLOADS if workloads is None else workloads
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import cpu_ops
+    import vae_cpu_ops
     from oracle import torch_ref as R
     from sim_runtime import SimRuntime
     seen, wseen = set(), set()
 
     def recorder(name):
         def rec(g, x, *a, **k):
-            seen.add((g.B, g.H, g.W, g.Cin, g.Cout, g.k, g.stride, x.ld))
+            if not bf16_only or x.sfx == "bf16":
+                seen.add((g.B, g.H, g.W, g.Cin, g.Cout, g.k, g.stride, x.ld))
         rec.__name__ = name
         return rec
 
     def wgrad_recorder(name):
         def rec(g, x, dy, *a, **k):
+            if bf16_only and x.sfx != "bf16":
+                return
             wseen.add((g.B, g.H, g.W, g.Cin, g.Cout, g.k, g.stride, x.ld, dy.ld, int(name == "conv2d_transpose_wgrad")))
         rec.__name__ = name
         return rec
 
-    for name, make in WORKLOADS.items():
+    for name, make in workloads.items():
         mp = pytest.MonkeyPatch()
         try:
             rt = SimRuntime()
-            impl = cpu_ops.install(mp, rt)
-            for c in dir(impl):
+            impl = vae_cpu_ops.install(mp, rt)          # tests/cpu_ops.py and the VAE's operators on top
+            for c in dir(impl) + dir(vae_cpu_ops.VaeCpuOps):
                 if not c.startswith("_") and c != "rt" and not c.endswith(KEEP):
                     mp.setattr(U.ops, c, recorder(c) if c in CONV_CALLS else wgrad_recorder(c) if c in WGRAD_CALLS else
                                (lambda *a, **k: None))
@@ -131,13 +144,28 @@ def query_ws(wlayers):
     return out
 
 
+def ae_vae_entry():
+    layers, _ = collect_layers(AE_VAE_WORKLOADS, bf16_only=True)
+    return {"layers": [list(x) for x in layers], "settings": query(layers)}
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--ae-vae-only"]:      # add or replace that entry alone: every other recorded line stays as it is
+        with open(OUT) as f:
+            doc = json.load(f)
+        doc["ae_vae_reference_geometry"] = ae_vae_entry()
+        with open(OUT, "w") as f:
+            json.dump(doc, f, separators=(",", ":"))
+            f.write("\n")
+        print(f"wrote {OUT}: {len(doc['ae_vae_reference_geometry']['layers'])} auto-encoder layers x {len(SETTINGS)} settings", file=sys.stderr)
+        sys.exit(0)
     if len(sys.argv) > 1:
         U._lib.use_library(os.path.abspath(sys.argv[1]))
     layers, wlayers = collect_layers()
     doc = {"fields": ["k3_fwd", "k3_dgrad", "rows_fwd", "rows_dgrad", "rows_t"],
            "layer_fields": ["B", "H", "W", "Cin", "Cout", "k", "stride", "ld"],
            "layers": [list(x) for x in layers], "settings": query(layers)}
+    doc["ae_vae_reference_geometry"] = ae_vae_entry()
     with open(OUT, "w") as f:
         json.dump(doc, f, separators=(",", ":"))
         f.write("\n")

@@ -51,6 +51,31 @@ def test_plan_reproduces_the_recorded_dispatch():
     assert {"tap-table", "conv3x3r", "conv3x3g", "conv3x3g pair", "conv3x3h", "conv3x3s", "conv3x3p", "stem"} <= seen
 
 
+def test_plan_reproduces_the_recorded_dispatch_of_the_autoencoder_and_vae_layers():
+    """The entry "ae_vae_reference_geometry": the bf16 layers of main_training.py's Autoencoder and VAE at their own size, collected
+    from the engines on the simulated runtime.  The recording is the geometry table of tests/ae_vae_cases.py and nothing else, and
+    the library still answers what was recorded: the stride-1 Conv2DTranspose on the paired tile with 16 rows of statistics, no
+    fused statistics on any 3x3 stride-2 layer."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ae_vae_cases as T
+    gen = _generator()
+    doc = json.load(open(os.path.join(GOLDEN, "conv_dispatch.json")))["ae_vae_reference_geometry"]
+    layers = [tuple(x) for x in doc["layers"]]
+    assert [list(x) for x in layers] == gen.ae_vae_entry()["layers"]          # what the engines launch today
+    table = {T.conv_geom(c, "bf16") for c in T.CONV_LAYERS} | {T.convt_geom(c, "bf16") for c in T.CONVT_LAYERS}
+    assert {l[:7] for l in layers} == table
+    assert [s for s, _ in gen.SETTINGS] == list(doc["settings"])
+    got = gen.query(layers)
+    bad = [(s, l, r, n) for s, recs in doc["settings"].items() for l, r, n in zip(layers, recs, got[s]) if r != n]
+    assert not bad, bad[:10]
+    for layer, rec in zip(layers, doc["settings"]["default"]):
+        if layer[6] == 1:
+            assert rec == ["conv3x3g pair", "conv3x3g pair", 16, 16, 16], (layer, rec)
+        else:
+            assert rec[2:] == [0, 0, 0], (layer, rec)
+
+
 def test_wgrad_workspace_query_keeps_the_recorded_values():
     doc = json.load(open(os.path.join(GOLDEN, "wgrad_ws.json")))
     layers = [tuple(x) for x in doc["layers"]]

@@ -95,3 +95,50 @@ def test_ints_covers_its_range_and_repeats():
     assert torch.equal(t, X.ints("range", (4000,), -1, 3))
     a = X.addends("add", (4000,))
     assert float(a.abs().max()) == 240.0 and torch.equal(a % 4, torch.zeros_like(a)) and torch.equal(X.bf16(a), a)
+
+
+def _emulate_dense(x, w, b, ks, drop_bias_when_one_slice=False, skip_slice=None):
+    """The small-batch Dense launcher (csrc/igemm.hip launch_dense_fwd) in fp32: ks == 1 - the kernel's epilogue adds the bias;
+    ks > 1 - one fp32 slab per K slice, then bias + the slabs in slab order."""
+    K = x.shape[1]
+    edges = [round(i * K / ks) for i in range(ks + 1)]
+    slabs = [x[:, a:e].float() @ w[:, a:e].float().t() for a, e in zip(edges[:-1], edges[1:])]
+    if ks == 1:
+        return (slabs[0] if drop_bias_when_one_slice else slabs[0] + b.float()).double()
+    y = b.float().expand_as(slabs[0]).clone()
+    for i, s_ in enumerate(slabs):
+        if i != skip_slice:
+            y = y + s_
+    return y.double()
+
+
+def _within_tolerance(got, want, K):
+    """The criterion of the uniform data kind for fp32 outputs (test_kernels_gpu.close with 2e-6 sqrt(K) + 1e-6)."""
+    return float((got - want).abs().max()) <= (2e-6 * K ** 0.5 + 1e-6) * float(want.abs().max())
+
+
+@pytest.mark.parametrize("K,N,ks,mutant", [(64, 46080, 1, dict(drop_bias_when_one_slice=True)), (48128, 64, 128, dict(skip_slice=127)),
+                                           (48128, 64, 128, dict(skip_slice=0))])
+def test_both_data_kinds_reject_a_dense_that_drops_the_bias_or_a_slice(K, N, ks, mutant):
+    """The Dense plans of the auto-encoders at main_training.py's size (tests/test_fullsize_ae_vae_gpu.py): one slice, where the bias is
+    the igemm epilogue's, and the cap of 128 slices.  The correct emulation passes both data kinds; a launcher that drops the bias
+    when ks == 1, or sums 127 of the 128 slabs, passes neither."""
+    from oracle import detrand
+    Bn = 32
+    for data in X.DATA_KINDS:
+        if data == "int":
+            x, w, b = X.acts(f"dx{K}", (Bn, K)), X.kernels(f"dw{K, N}", (N, K)), X.biases(f"db{N}", (N,))
+            X.check_exactness_conditions({"x": (x, False), "w": (w, False), "bias": (b, False)}, X.conv_abs_bound(K, has_addend=False), what="dense")
+        else:
+            x = torch.tensor(detrand.uniform(f"dx{K}", (Bn, K), -1, 1)).double()
+            w = (torch.tensor(detrand.uniform(f"dw{K, N}", (N, K), -1, 1)) * 0.05).double()
+            b = torch.tensor(detrand.uniform(f"db{N}", (N,), -1, 1)).double()
+        want = x @ w.t() + b
+        good, bad = _emulate_dense(x, w, b, ks), _emulate_dense(x, w, b, ks, **mutant)
+        if data == "int":
+            X.assert_exact(good, want, "dense")
+            with pytest.raises(AssertionError) as e:
+                X.assert_exact(bad, want, "mutant")
+            assert "elements differ" in str(e.value)
+        else:
+            assert _within_tolerance(good, want, K) and not _within_tolerance(bad, want, K)

@@ -160,20 +160,39 @@ def test_conv2d_fwd_dgrad_wgrad(U, case, data):
     cmp32(exact, dw, exp, 2e-6 * math.sqrt(B * Ho * Wo) + 1e-6, "wgrad")
 
 
-CONVT_CASES = [(2, 6, 5, 16, 8, 3), (1, 4, 4, 64, 32, 3), (1, 5, 6, 8, 16, 6), (2, 3, 3, 128, 64, 3),
-               (2, 12, 40, 48, 72, 3), (1, 16, 32, 64, 64, 3)]      # the last two take the fused parity-class kernel
+# B, H, W, Cin, Cout, k, stride
+CONVT_CASES = [(2, 6, 5, 16, 8, 3, 2), (1, 4, 4, 64, 32, 3, 2), (1, 5, 6, 8, 16, 6, 2), (2, 3, 3, 128, 64, 3, 2),
+               (2, 12, 40, 48, 72, 3, 2), (1, 16, 32, 64, 64, 3, 2),   # these two take the fused parity-class kernel
+               (2, 9, 10, 64, 64, 3, 1),                               # stride 1 (decoder_conv_transpose_layer_0 of the auto-encoders)
+               (2, 12, 20, 16, 4, 3, 2)]                               # the 2-channel output layer, stored in 4 channels
+# the cases whose stored output channels are zero padding behind this many real ones: padded kernel rows, bias and dy are zero
+CONVT_REAL_OUT = {(2, 12, 20, 16, 4, 3, 2): 2, (1, 6, 10, 64, 8, 3, 2): 2}
+
+
+def convt_inputs(case, data, q=lambda t: t):
+    """x, HWOI kernel, bias, the oracle's output and dy of a Conv2DTranspose case (q: the rounding of the storage type).  The stride-2
+    cases keep the tensor names they had before the stride became part of the case."""
+    B, H, W, Ci, Co, k, s = case
+    name = case[:6] if s == 2 and case not in CONVT_REAL_OUT else case
+    real = CONVT_REAL_OUT.get(case, Co)
+    x = q(rand(f"tx{name}", (B, Ci, H, W), data))
+    w = q(rand(f"tw{name}", (k, k, Co, Ci), data, "kernel"))  # HWOI
+    b = rand(f"tb{name}", (Co,), data, "bias")
+    w[:, :, real:] = 0
+    b[real:] = 0
+    x.requires_grad_(True); w.requires_grad_(True)
+    y = R.conv2d_transpose_same(x, w, b, s)
+    gy = q(rand(f"tg{name}", tuple(y.shape), data))
+    gy[:, real:] = 0
+    return x, w, b, y, gy
 
 
 @X.parametrize_kinds("case", CONVT_CASES)
 def test_conv2d_transpose(U, case, data):
     ops = U.ops
     exact = data == "int"
-    B, H, W, Ci, Co, k = case
-    x = rand(f"tx{case}", (B, Ci, H, W), data).requires_grad_(True)
-    w = rand(f"tw{case}", (k, k, Co, Ci), data, "kernel").requires_grad_(True)  # HWOI
-    b = rand(f"tb{case}", (Co,), data, "bias")
-    y = R.conv2d_transpose_same(x, w, b, 2)
-    gy = rand(f"tg{case}", tuple(y.shape), data)
+    B, H, W, Ci, Co, k, s = case
+    x, w, b, y, gy = convt_inputs(case, data)
     (y * gy).sum().backward()
     reg = X.REG if exact else 0.002
     if exact:
@@ -181,12 +200,12 @@ def test_conv2d_transpose(U, case, data):
                                      X.conv_abs_bound(k * k * max(Ci, Co), has_addend=False), what=f"f32 convT {case}")
         X.check_exactness_conditions({}, B * H * W * k * k + 1, quantum=0.5, what=f"f32 convT wgrad {case}")
 
-    g = ops.geom(B, H, W, Ci, Co, k, 2)
+    g = ops.geom(B, H, W, Ci, Co, k, s)
     w_prim = w.detach().permute(3, 0, 1, 2).contiguous().float().to(DEV)       # [Ci][kh][kw][Co]
     wt = torch.empty((Co, k * k, Ci), device=DEV)
     ops.transpose_weight(w_prim, wt, Ci, k * k, Co)
     xa = ops.Act(to_nhwc_buf(x.detach(), Ci, 0, DEV))
-    ya = ops.Act(torch.full((B, 2 * H, 2 * W, 2 * Co), 555.0, device=DEV), Co, Co)   # upper half of a concat buffer
+    ya = ops.Act(torch.full((B, s * H, s * W, 2 * Co), 555.0, device=DEV), Co, Co)   # upper half of a concat buffer
     ops.conv2d_transpose_fwd(g, xa, wt, b.float().to(DEV), ya)
     torch.cuda.synchronize()
     cmp32(exact, ya.dense() if exact else ya.dense().permute(0, 3, 1, 2), y.detach(), 2e-6 * math.sqrt(Ci * k * k) + 1e-6, "convT fwd", nchw=exact)
@@ -567,26 +586,26 @@ def test_the_switch_sets_reach_every_3x3_kernel(U):
     assert any(c in STEM_CASES for c, _, _ in seen["stem"])
 
 
-CONVT_BF16_CASES = [(2, 6, 5, 16, 8, 3), (1, 4, 4, 64, 32, 3), (2, 3, 3, 128, 64, 3), (2, 12, 40, 48, 72, 3),
-                    (1, 16, 32, 136, 64, 3),
-                    (1, 16, 64, 96, 72, 3), (2, 20, 32, 32, 64, 3),    # LDS-DMA kernel (upconv3x3g): 3 chunks / ragged N, ragged rows
-                    (2, 8, 32, 64, 32, 3), (1, 16, 32, 128, 48, 3),    # data gradient on conv3x3d (input in a concat buffer)
-                    (2, 16, 16, 64, 32, 3),                            # 16-wide adjoint: tap-table kernel
-                    (8, 128, 128, 128, 64, 3)]                         # >= 1024 tiles: the persistent form (upconv3x3q)
+# B, H, W, Cin, Cout, k, stride
+CONVT_BF16_CASES = [(2, 6, 5, 16, 8, 3, 2), (1, 4, 4, 64, 32, 3, 2), (2, 3, 3, 128, 64, 3, 2), (2, 12, 40, 48, 72, 3, 2),
+                    (1, 16, 32, 136, 64, 3, 2),
+                    (1, 16, 64, 96, 72, 3, 2), (2, 20, 32, 32, 64, 3, 2),    # LDS-DMA kernel (upconv3x3g): 3 chunks / ragged N, ragged rows
+                    (2, 8, 32, 64, 32, 3, 2), (1, 16, 32, 128, 48, 3, 2),    # data gradient on conv3x3d (input in a concat buffer)
+                    (2, 16, 16, 64, 32, 3, 2),                            # 16-wide adjoint: tap-table kernel
+                    (8, 128, 128, 128, 64, 3, 2),                         # >= 1024 tiles: the persistent form (upconv3x3q)
+                    (2, 9, 10, 64, 64, 3, 1), (3, 9, 10, 128, 96, 3, 1),  # stride 1 (decoder_conv_transpose_layer_0 of the auto-encoders)
+                    (1, 6, 10, 64, 8, 3, 2)]                           # the 2-channel output layer, stored in 8 channels (CONVT_REAL_OUT)
 
 
 @X.parametrize_kinds("case", CONVT_BF16_CASES)
 def test_conv2d_transpose_bf16(U, case, data):
     """Conv2DTranspose forward (bias, upper half of a concat buffer), data gradient (plain, and with the packed kernel copy where
-    one is defined) and weight gradient.  data = "int": exact, forward and data gradient under every set of CONVT_SWITCH_SETS."""
+    one is defined) and weight gradient.  data = "int": exact, forward and data gradient under every set of CONVT_SWITCH_SETS
+    (stride 1: of CONV_SWITCH_SETS)."""
     ops = U.ops
     exact = data == "int"
-    B, H, W, Ci, Co, k = case
-    x = q16(rand(f"tx{case}", (B, Ci, H, W), data)).requires_grad_(True)
-    w = q16(rand(f"tw{case}", (k, k, Co, Ci), data, "kernel")).requires_grad_(True)
-    b = rand(f"tb{case}", (Co,), data, "bias")
-    y = R.conv2d_transpose_same(x, w, b, 2)
-    gy = q16(rand(f"tg{case}", tuple(y.shape), data))
+    B, H, W, Ci, Co, k, s = case
+    x, w, b, y, gy = convt_inputs(case, data, q16)
     (y * gy).sum().backward()
     reg = X.REG if exact else 0.002
     if exact:
@@ -598,7 +617,7 @@ def test_conv2d_transpose_bf16(U, case, data):
         assert (ties > 0 or y.numel() < 4096) and (ties_d > 0 or x.numel() < 4096), (ties, ties_d)
         X.note_ties(ties + ties_d)
         want_y, want_dx = X.expected_bf16(y.detach()).to(DEV), X.expected_bf16(x.grad).to(DEV)
-    g = ops.geom(B, H, W, Ci, Co, k, 2)
+    g = ops.geom(B, H, W, Ci, Co, k, s)
     w32 = w.detach().permute(3, 0, 1, 2).contiguous().float().to(DEV)            # primary [Ci][k][k][Co]
     wprim = torch.empty((Ci, k * k, Co), dtype=torch.bfloat16, device=DEV)
     ops.cast_weight_bf16(w32, wprim, Ci, k * k, Co, Co)
@@ -606,14 +625,14 @@ def test_conv2d_transpose_bf16(U, case, data):
     ops.transpose_cast_weight_bf16(w32, wt, Ci, k * k, Co, Ci)
     xa = ops.Act(to_nhwc_bf16(x.detach(), Ci, 0, DEV))
     gya = ops.Act(to_nhwc_bf16(gy, 2 * Co, Co, DEV), Co, Co)
-    ne = ops.conv3x3s2_packed_elems(Ci, Co)          # the data gradient is the stride-2 forward kernel on the adjoint geometry
+    ne = ops.conv3x3s2_packed_elems(Ci, Co) if s == 2 else 0     # the data gradient is the stride-2 forward kernel on the adjoint geometry
     pk = None
     if exact and ne:
         pk = torch.zeros(ne, dtype=torch.bfloat16, device=DEV)
         ops.cast_weights_batched(ops.make_cast_table([(w32, torch.empty_like(wprim), torch.empty_like(wt), Ci, k * k, Co, Co, Ci, pk)], DEV))
-    for sw in switch_sets(data, CONVT_SWITCH_SETS):
+    for sw in switch_sets(data, CONVT_SWITCH_SETS if s == 2 else CONV_SWITCH_SETS):      # stride 1: a 3x3 convolution with flipped taps
         set_switches(ops, sw)
-        ya = ops.Act(torch.full((B, 2 * H, 2 * W, 2 * Co), 512.0, dtype=torch.bfloat16, device=DEV), Co, Co)
+        ya = ops.Act(torch.full((B, s * H, s * W, 2 * Co), 512.0, dtype=torch.bfloat16, device=DEV), Co, Co)
         ops.conv2d_transpose_fwd(g, xa, wt, b.float().to(DEV), ya)
         dxa = ops.Act(torch.full((B, H, W, Ci), 256.0, dtype=torch.bfloat16, device=DEV))
         ops.conv2d_transpose_dgrad(g, gya, wprim, dxa)
@@ -815,7 +834,7 @@ def _head_exact(ops, B, H, W, Cc):
         assert float(dxa.base[..., :8].float().min()) == 3.0 and float(dxa.base[..., :8].float().max()) == 3.0
 
 
-@X.parametrize_kinds("B,K,N", [(32, 8192, 4096), (3, 520, 72), (4, 4096, 8192)])
+@X.parametrize_kinds("B,K,N", [(32, 8192, 4096), (3, 520, 72), (4, 4096, 8192), (32, 64, 46080), (32, 48128, 64)])
 def test_dense_split_k(U, B, K, N, data):
     """Dense on a small batch through the split-K entry point (dl_models/u_net.py:259) and its data gradient."""
     ops = U.ops

@@ -383,6 +383,10 @@ BN_CASES = [
     (64, 132000, BF16, False), (64, 66000, F32, False),                  # row 3 at the capped grid: several passes, parameters in registers
     (1536, 16384, BF16, False), (2048, 16384, BF16, False), (4096, 8192, BF16, False),   # row 4 (and row 5: 1024 / 2048 slabs), bf16
     (1536, 16384, F32, False), (2048, 16384, F32, False), (4096, 8192, F32, False),      # row 4, fp32
+    # BatchNorm -> ReLU / LeakyReLU of the Autoencoder and the VAE at main_training.py's size (tests/ae_vae_cases.py BN_PAIRS): batch 32 of
+    # 72 x 80, 36 x 40, 18 x 20 and 9 x 10 pixels, both storage types
+    (64, 184320, BF16, False), (128, 46080, BF16, False), (256, 11520, BF16, False), (512, 2880, BF16, False),
+    (64, 184320, F32, False), (128, 46080, F32, False), (256, 11520, F32, False), (512, 2880, F32, False),
 ]
 
 
