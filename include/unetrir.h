@@ -563,6 +563,29 @@ int unetrir_vae_loss_add_f32(const float* kl_out, float* loss_out, unetrir_strea
 int unetrir_stage_h2d(int n, const void* const* src, void* const* pinned, void* const* dev, const size_t* bytes,
                       unetrir_stream_t stream);
 
+/* ---- a training batch out of the device-resident data set, in one launch: the two loops over `dataset.__getitem__` and the
+ *      three np.stack calls of DataGenerator.__getitem__ (datageneratorv2.py:64-102) as a gather.
+ *      bank fp32 [N][2][H][W] (row_elems = 2 H W: the padded features of every file), emb_bank int32 [N][emb_len], wav_bank
+ *      nullable fp32 [N][wav_len] (the decoded waveforms), room_bank nullable int32 [N]; idx_in / idx_out int32 [B] IN DEVICE
+ *      MEMORY: the sample numbers of the input and of the target position of each pair.
+ *        spec_in[b] = bank[idx_in[b]]   spec_out[b] = bank[idx_out[b]]   contiguous NCHW fp32 [B][2][H][W], the engine's boundary
+ *        emb[b][0] = emb_bank[idx_in[b]]   emb[b][1] = emb_bank[idx_out[b]]          int32 [B][2][emb_len] (:91)
+ *        wav_true[b] = wav_bank[idx_out[b]]   room[b] = room_bank[idx_out[b]]        nullable; the target position (what the
+ *                                                                                    evaluation scores, rir_generation.py:160-293)
+ *      A streaming copy: 16 bytes per lane when row_elems % 4 == 0 and bank / spec_in / spec_out are 16-byte aligned (wav_len and
+ *      the waveform pointers likewise, independently), 4 bytes per lane otherwise - the only entry point that takes unaligned
+ *      buffers.  Nothing outside the outputs is written.
+ *      THE INDICES ARE TRUSTED: the kernel reads row idx of every bank without a range check (N is only validated as a
+ *      geometry argument).  The generator produces its index table on the host, checks it against N there, once per epoch,
+ *      and uploads it; a caller of this entry point owes the same check.
+ *      UNETRIR_EINVAL before the device is touched: a null required pointer (bank, emb_bank, idx_in, idx_out, spec_in, spec_out,
+ *      emb), B, N, row_elems or emb_len <= 0, wav_true without wav_bank or the reverse (or wav_len <= 0 with them), room without
+ *      room_bank, more than 2^31 - 1 workgroups of 16 KB ((2 ceil(row_elems / 4096) + ceil(wav_len / 4096)) B). */
+int unetrir_gather_batch_f32(const float* bank, long long N, long long row_elems, const int32_t* emb_bank, int emb_len,
+                             const float* wav_bank, long long wav_len, const int32_t* room_bank, const int32_t* idx_in,
+                             const int32_t* idx_out, int B, float* spec_in, float* spec_out, int32_t* emb, float* wav_true,
+                             int32_t* room, unetrir_stream_t stream);
+
 /* ---- profiling hooks used by bench.py: when enabled every conv launch is bracketed by HIP
  *      events on its own stream; collect() synchronises those events and returns, per kernel
  *      family, launch count, total milliseconds and total algorithmic FLOPs.  Process-global

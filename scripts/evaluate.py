@@ -3,6 +3,7 @@
 
     python scripts/evaluate.py --load SAVED_MODEL_DIR --data BATCH_DIR --out REPORT_DIR [--name unet] [--diff-gen]
     python scripts/evaluate.py --checkpoint CKPT_DIR --filters 32 --kernels 3 --data BATCH_DIR --out REPORT_DIR
+    python scripts/evaluate.py --checkpoint CKPT_DIR --dataset DIR NAME [--rooms ...] [--arrays ...] --out REPORT_DIR
     python scripts/evaluate.py --synthetic 8 --out REPORT_DIR            # no dataset, no checkpoint: random weights and data
 
 --load         a folder written by `UNet.save` / `ResAE.save` / `Autoencoder.save` / `VAE.save` (--arch picks the class)
@@ -10,6 +11,8 @@
                (--arch vae: into the VAE of rir_generation.py:78-87, latent size --latent)
 --data         a directory of .npz files, one test batch each: spec_in, spec_out fp32 [B, H, W, 2] (or [B, 2, H, W]), emb int
                [B, 2, 16], wav_true fp32 [B, T], room = B room names (or indices into evaluate.ROOMS)
+--dataset      the impulse-response tree DIR/NAME/Room/ZoneX/...Array/*.wav itself: the test partition of `unet_rir_amd.Dataset`
+               with characteristics=True, shuffle=False, as rir_generation.py:67-70 (--rooms / --arrays filter it, default all)
 --synthetic N  N batches of `synthetic_batches`, which yields no waveforms: wav_true is the reconstruction of spec_out
 """
 import argparse
@@ -65,6 +68,16 @@ def file_batches(folder, dev):
                    torch.from_numpy(z["spec_out"]).float().to(dev), torch.from_numpy(z["wav_true"]).float().to(dev), room)
 
 
+def dataset_batches(a, dev):
+    ds = U.Dataset(a.dataset[0], a.dataset[1], normalization=True, room_characteristics=True, room=a.rooms, array=a.arrays,
+                   device=dev, keep_waveforms=True, input_shape=(a.height, a.width))
+    gen = U.DataGenerator(ds, batch_size=a.batch, partition="test", shuffle=False, characteristics=True)
+    if len(gen) == 0:
+        raise SystemExit(f"the test partition ({len(gen.index_in)} pairs) holds less than one batch of {a.batch}")
+    for spec_in, emb, spec_out, (room, wav_true) in gen:
+        yield spec_in, emb, spec_out, wav_true, room
+
+
 def synthetic(a, dev):
     post = PostProcess()
     for k, (spec_in, emb, spec_out) in enumerate(U.synthetic_batches(a.synthetic, a.batch, a.height, a.width, dev)):
@@ -84,19 +97,22 @@ def main():
     ap.add_argument("--width", type=int, default=160)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--data")
+    ap.add_argument("--dataset", nargs=2, metavar=("DIR", "NAME"))
+    ap.add_argument("--rooms", nargs="+", default=None, help="with --dataset: room names (default: all five)")
+    ap.add_argument("--arrays", nargs="+", default=None, help="with --dataset: array names (default: both)")
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--diff-gen", action="store_true")
     ap.add_argument("--out", required=True)
     ap.add_argument("--name", default="unet")
     a = ap.parse_args()
-    if bool(a.data) == bool(a.synthetic):
-        raise SystemExit("give exactly one of --data and --synthetic")
+    if bool(a.data) + bool(a.synthetic) + bool(a.dataset) != 1:
+        raise SystemExit("give exactly one of --data, --dataset and --synthetic")
     if not torch.cuda.is_available():
         raise SystemExit("evaluation runs on the GPU; there is none here")
     dev = torch.device("cuda:0")
     model = build_model(a, dev)
     ev = U.Evaluator(model, diff_gen=a.diff_gen)
-    for batch in (file_batches(a.data, dev) if a.data else synthetic(a, dev)):
+    for batch in (file_batches(a.data, dev) if a.data else dataset_batches(a, dev) if a.dataset else synthetic(a, dev)):
         ev.update(*batch)
     res = ev.result()
     for p in U.write_report(res, a.out, a.name):

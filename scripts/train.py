@@ -1,0 +1,92 @@
+"""Train on the impulse-response tree, the flow of main_training.py: data set -> generators -> model by --name -> Trainer
+(optimizer, loss switches, learning rate) -> CheckpointManager -> fit.  One process, one GPU.
+
+    python scripts/train.py --dataset ../datasets room_impulse --rooms LargeMeetingRoom --name unet --out ../results/unet
+
+The defaults are main_training.py's (:27-47): target size (144, 160, 2), LargeMeetingRoom, both arrays, debug data set, U-Net,
+alpha 0.9, no sigmoid / diff loss, 500 epochs, lr 5e-7 with the exponential decay from epoch 80, batch 16, Adam.  A run continues
+from the latest checkpoint in --out when there is one (checkpoints are written every second epoch, :363-364).  The features of
+the whole data set live on the device (unet_rir_amd.Dataset); a batch is one kernel launch.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import unet_rir_amd as U
+
+
+def build_model(a, dev):
+    """main_training.py:119-161, constructor arguments included."""
+    shape, common = (a.height, a.width, 2), dict(batch_size=a.batch, device=dev, dtype=a.dtype)
+    if a.name == "ae":
+        return U.Autoencoder(shape, (2, 16), conv_filters=(64, 128, 256, 512), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
+                             latent_space_dim=64, n_neurons=32 * 64, name=a.name, **common)
+    if a.name == "resae":
+        return U.ResAE(shape, (2, 16), conv_filters=(32, 64, 128, 256), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
+                       latent_space_dim=32, n_neurons=16 * 64, name=a.name, **common)
+    if a.name == "vae":
+        return U.VAE(shape, (2, 16), conv_filters=(64, 128, 256, 512), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
+                     latent_space_dim=64, n_neurons=32 * 64, name=a.name, **common)
+    return U.UNet(shape, (2, 16), mode=0, number_filters_0=a.filters, kernels=a.kernels, name="U-Net", **common)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dataset", nargs=2, metavar=("DIR", "NAME"), required=True, help="the tree is DIR/NAME/Room/ZoneX/...Array/*.wav")
+    ap.add_argument("--rooms", nargs="+", default=["LargeMeetingRoom"], help="room names, or All")
+    ap.add_argument("--arrays", nargs="+", default=["PlanarMicrophoneArray", "CircularMicrophoneArray"])
+    ap.add_argument("--no-debug", action="store_true", help="load the whole tree (main_training.py runs with debug = True)")
+    ap.add_argument("--extract", action="store_true", help="unpack the zone archives first")
+    ap.add_argument("--name", choices=("ae", "resae", "vae", "unet"), default="unet")
+    ap.add_argument("--filters", type=int, default=32, help="number_filters_0 of the U-Net")
+    ap.add_argument("--kernels", type=int, default=3)
+    ap.add_argument("--height", type=int, default=144)
+    ap.add_argument("--width", type=int, default=160)
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--alpha", type=float, default=0.9)
+    ap.add_argument("--sigmoid-loss", action="store_true")
+    ap.add_argument("--diff-loss", action="store_true")
+    ap.add_argument("--beta", type=float, default=0.5)
+    ap.add_argument("--epochs", type=int, default=500)
+    ap.add_argument("--lr", type=float, default=5e-7)
+    ap.add_argument("--no-lr-decay", action="store_true")
+    ap.add_argument("--decay-from", type=int, default=80)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--optimizer", default="adam", help="adam, nadam or sgd")
+    ap.add_argument("--out", required=True, help="checkpoint directory (main_training.py: ../results/<name>)")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("training runs on the GPU; there is none here")
+    dev = torch.device("cuda:0")
+
+    dataset = U.Dataset(a.dataset[0], a.dataset[1], normalization=True, debugging=not a.no_debug, extract=a.extract,
+                        room=["All"] if a.rooms == ["All"] else a.rooms, array=a.arrays, device=dev, input_shape=(a.height, a.width))
+    # shuffle=True as main_training.py:78-79 passes it - and, as there, without effect: nothing calls on_epoch_end() (fit does
+    # not either), so every epoch visits the batches in the order the seeded shuffle of the constructor gave them
+    train = U.DataGenerator(dataset, batch_size=a.batch, partition="train", shuffle=True)
+    val = U.DataGenerator(dataset, batch_size=a.batch, partition="val", shuffle=True)
+    print(f"{len(dataset)} files, {len(dataset.index_in)} pairs: {len(train)} training and {len(val)} validation batches of {a.batch}")
+    if len(train) == 0:
+        raise SystemExit("the training partition holds less than one batch")
+
+    model = build_model(a, dev)
+    trainer = U.Trainer(model, lr=a.lr, alpha=a.alpha, sigmoid_loss=a.sigmoid_loss, diff_loss=a.diff_loss, beta=a.beta,
+                        optimizer=a.optimizer)
+    manager = U.CheckpointManager(trainer, a.out, max_to_keep=2)
+    start = 0
+    if manager.latest_checkpoint is not None:
+        epoch = manager.restore()
+        start = 0 if epoch is None else epoch + 1
+        print("restored", manager.latest_checkpoint, "- continuing with epoch", start + 1)
+    history = U.fit(trainer, train.batches, a.epochs, val.batches if len(val) else None, manager=manager, lr0=a.lr,
+                    lr_exp_decay=(not a.no_lr_decay, a.decay_from), start_epoch=start)
+    with open(os.path.join(a.out, "history.json"), "w") as f:
+        json.dump(history, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

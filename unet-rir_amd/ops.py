@@ -545,6 +545,63 @@ def eval_accumulate(out, group, acc):
     check(_lib.lib().unetrir_eval_accumulate(_p(out), _p(group), B, acc.shape[0] - 1, _p(acc), _stream()), "eval_accumulate")
 
 
+# ---- batches out of the device-resident data set ------------------------------------------------------
+
+def _bank(t, dtype, what, like=None, rows=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"gather_batch: {what} must be a contiguous {dtype} CUDA tensor")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"gather_batch: {what} lives on {t.device}, the bank on {like.device}")
+    if rows is not None and (t.dim() < 1 or t.shape[0] != rows):
+        raise ValueError(f"gather_batch: {what} must have {rows} rows")
+
+
+def gather_batch(bank, emb_bank, idx_in, idx_out, spec_in, spec_out, emb, wav_bank=None, room_bank=None, wav_true=None, room=None):
+    """One launch of DataGenerator.__getitem__ (datageneratorv2.py:64-102): rows `idx_in` / `idx_out` (int32 [B], on the device)
+    of bank fp32 [N, 2, H, W] -> spec_in / spec_out [B, 2, H, W]; of emb_bank int32 [N, L] -> emb [B, 2, L]; rows `idx_out` of
+    wav_bank fp32 [N, T] / room_bank int32 [N] -> wav_true [B, T] / room [B] when asked for.  The indices are NOT range-checked
+    here (include/unetrir.h): whoever builds them checks them against N on the host."""
+    _bank(bank, torch.float32, "bank")
+    if bank.dim() < 2:
+        raise ValueError("gather_batch: bank must be [N, ...]")
+    N, B = bank.shape[0], idx_in.numel()
+    _bank(emb_bank, torch.int32, "emb_bank", bank, N)
+    if emb_bank.dim() != 2:
+        raise ValueError("gather_batch: emb_bank must be [N, L]")
+    _bank(idx_in, torch.int32, "idx_in", bank)
+    _bank(idx_out, torch.int32, "idx_out", bank, B)
+    if idx_in.dim() != 1:
+        raise ValueError("gather_batch: idx_in / idx_out must be [B]")
+    for t, what in ((spec_in, "spec_in"), (spec_out, "spec_out")):
+        _bank(t, torch.float32, what, bank)
+        if tuple(t.shape) != (B,) + tuple(bank.shape[1:]):
+            raise ValueError(f"gather_batch: {what} must be {(B,) + tuple(bank.shape[1:])}")
+    _bank(emb, torch.int32, "emb", bank)
+    if tuple(emb.shape) != (B, 2, emb_bank.shape[1]):
+        raise ValueError(f"gather_batch: emb must be {(B, 2, emb_bank.shape[1])}")
+    T = 0
+    if (wav_true is None) != (wav_bank is None):
+        raise ValueError("gather_batch: wav_true and wav_bank come as a pair")
+    if wav_bank is not None:
+        _bank(wav_bank, torch.float32, "wav_bank", bank, N)
+        _bank(wav_true, torch.float32, "wav_true", bank, B)
+        if wav_bank.dim() != 2 or tuple(wav_true.shape) != (B, wav_bank.shape[1]):
+            raise ValueError("gather_batch: wav_bank [N, T], wav_true [B, T]")
+        T = wav_bank.shape[1]
+    if room is not None:
+        if room_bank is None:
+            raise ValueError("gather_batch: room needs room_bank")
+        _bank(room_bank, torch.int32, "room_bank", bank, N)
+        _bank(room, torch.int32, "room", bank, B)
+        if room_bank.dim() != 1 or room.dim() != 1:
+            raise ValueError("gather_batch: room_bank [N], room [B]")
+    else:
+        room_bank = None
+    check(_lib.lib().unetrir_gather_batch_f32(_p(bank), N, bank[0].numel(), _p(emb_bank), emb_bank.shape[1], _p(wav_bank), T,
+                                              _p(room_bank), _p(idx_in), _p(idx_out), B, _p(spec_in), _p(spec_out), _p(emb),
+                                              _p(wav_true), _p(room), _stream()), "gather_batch")
+
+
 def sigmoid_loss(logits: Act, target, alpha, inv_norm, pred, dlogits: Act, loss_out, ws: Workspace, phase_ref=None, phase_weight=None):
     """sigmoid head (dl_models/u_net.py:249) + compute_loss (main_training.py:203-231) + dL/dlogits.
     phase_ref: the network input [B,2,H,W] (the `diff_loss` switch, main_training.py:214-217); phase_weight: fp32 [W] column
