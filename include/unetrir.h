@@ -586,6 +586,38 @@ int unetrir_gather_batch_f32(const float* bank, long long N, long long row_elems
                              const int32_t* idx_out, int B, float* spec_in, float* spec_out, int32_t* emb, float* wav_true,
                              int32_t* room, unetrir_stream_t stream);
 
+/* ---- Griffin-Lim reconstruction from the magnitude alone: PostProcess.griffinlim (postprocess.py:47-50, :130-131,
+ *      librosa.griffinlim(S, hop_length, win_length)), the `algorithm='gl'` branch of rir_generation.py:62, :137, :424 - a whole
+ *      batch in one call.  PARITY UNPINNED like the feature transforms above: librosa 0.9.x's loop at its defaults,
+ *          S = magnitude plane of feat [B][2][H][W], first n_bins x n_frames block, denormalised (denormalize) and NOT clamped;
+ *          angles = exp(2 pi i u);  rebuilt = 0;
+ *          n_iter times:  tprev = rebuilt;  rebuilt = stft(istft(S angles));
+ *                         angles = rebuilt - momentum / (1 + momentum) tprev;  angles /= |angles| + 1e-16;
+ *          wav [B][hop_length (n_frames - 1)] = istft(S angles),
+ *      stft / istft being exactly the centred Hann pair of unetrir_stft_features_f32 / unetrir_istft_features_f32 (pad_mode 0 =
+ *      'reflect', 1 = 'constant').  librosa holds `angles` in complex64; here every state (angles, rebuilt, tprev, the
+ *      intermediate frames - all in ws) and all arithmetic are fp64, and the only fp32 values are feat, init_phase and the one
+ *      rounding of wav.  n_iter = 0 gives istft(S angles0).
+ *      momentum is read as the shortest decimal that rounds to the float given (0.99f means librosa's double 0.99, not
+ *      0.9900000095...: the difference reaches the waveform at ~1e-7 of its peak after 32 iterations).
+ *      u: init_phase fp32 [B][n_bins][n_frames] in turns, [0, 1) - angles0 = (cospi(2u), sinpi(2u)) in fp64 - or, when it is
+ *      NULL, draw (seed, draw) of unetrir_uniform_f32 over that shape.
+ *      2 n_iter + 3 launches on `stream` whatever B is; no allocation, no memset, no host synchronisation (capturable in a HIP
+ *      graph); fixed summation orders and no atomics: two runs are bit-identical.
+ *      UNETRIR_EINVAL before the device is touched: the geometry rules of unetrir_istft_features_f32, n_iter < 0, a negative or non-finite momentum,
+ *      pad_mode outside {0, 1}, a null feat / wav / ws, ws_bytes < unetrir_griffinlim_ws_bytes (0 for an invalid geometry).
+ *
+ * unetrir_uniform_f32: the `rng.rand` of librosa.griffinlim's init='random' as the uniform sibling of unetrir_normal_f32 -
+ *   element i of draw (seed, step) is a fixed function of (seed, step, i), a shorter draw is a prefix of a longer one.  Same GOLD
+ *   and mix64 as there; TAG = 0x554E4946524D3634:
+ *       key = mix64(mix64(seed * GOLD + step) ^ TAG);   r = mix64(key + GOLD * (i + 1));   out = (r >> 40) / 2^24   in [0, 1). */
+size_t unetrir_griffinlim_ws_bytes(int B, int n_bins, int n_frames, int n_fft);
+int unetrir_griffinlim_f32(const float* feat, int B, int H, int W, int n_bins, int n_frames, int n_fft, int win_length,
+                           int hop_length, int pad_mode, int denormalize, int n_iter, float momentum, const float* init_phase,
+                           unsigned long long seed, unsigned long long draw, float* wav, void* ws, size_t ws_bytes,
+                           unetrir_stream_t stream);
+int unetrir_uniform_f32(float* out, long long n, unsigned long long seed, unsigned long long step, unetrir_stream_t stream);
+
 /* ---- profiling hooks used by bench.py: when enabled every conv launch is bracketed by HIP
  *      events on its own stream; collect() synchronises those events and returns, per kernel
  *      family, launch count, total milliseconds and total algorithmic FLOPs.  Process-global

@@ -14,6 +14,8 @@
 --dataset      the impulse-response tree DIR/NAME/Room/ZoneX/...Array/*.wav itself: the test partition of `unet_rir_amd.Dataset`
                with characteristics=True, shuffle=False, as rir_generation.py:67-70 (--rooms / --arrays filter it, default all)
 --synthetic N  N batches of `synthetic_batches`, which yields no waveforms: wav_true is the reconstruction of spec_out
+--algorithm    ph (default): reconstruct from the predicted phase; gl: Griffin-Lim from the predicted magnitude
+               (rir_generation.py:62, :137; --gl-iters, --gl-momentum, --gl-seed)
 """
 import argparse
 import glob
@@ -102,6 +104,10 @@ def main():
     ap.add_argument("--arrays", nargs="+", default=None, help="with --dataset: array names (default: both)")
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--diff-gen", action="store_true")
+    ap.add_argument("--algorithm", choices=("ph", "gl"), default="ph")
+    ap.add_argument("--gl-iters", type=int, default=32)
+    ap.add_argument("--gl-momentum", type=float, default=0.99)
+    ap.add_argument("--gl-seed", type=int, default=0)
     ap.add_argument("--out", required=True)
     ap.add_argument("--name", default="unet")
     a = ap.parse_args()
@@ -111,7 +117,8 @@ def main():
         raise SystemExit("evaluation runs on the GPU; there is none here")
     dev = torch.device("cuda:0")
     model = build_model(a, dev)
-    ev = U.Evaluator(model, diff_gen=a.diff_gen)
+    ev = U.Evaluator(model, diff_gen=a.diff_gen, algorithm=a.algorithm, gl_iters=a.gl_iters, gl_momentum=a.gl_momentum,
+                     gl_seed=a.gl_seed)
     for batch in (file_batches(a.data, dev) if a.data else dataset_batches(a, dev) if a.dataset else synthetic(a, dev)):
         ev.update(*batch)
     res = ev.result()

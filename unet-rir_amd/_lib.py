@@ -202,6 +202,11 @@ _SIGS = {
     "unetrir_vae_loss_add_f32": (C.c_int, [c_f32p, c_f32p, c_stream]),
     "unetrir_gather_batch_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, c_f32p, C.c_longlong, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int, c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, c_stream]),
+    "unetrir_griffinlim_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "unetrir_griffinlim_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_float, c_f32p, C.c_ulonglong, C.c_ulonglong, c_f32p, C.c_void_p,
+                                         C.c_size_t, c_stream]),
+    "unetrir_uniform_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_ulonglong, c_stream]),
     "unetrir_prof_enable": (C.c_int, [C.c_int]),
     "unetrir_prof_collect": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }

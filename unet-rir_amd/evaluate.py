@@ -14,8 +14,9 @@ that live on the device (`ops.eval_accumulate`), and `Evaluator.result()` is the
 
 Spectrograms are accepted NHWC `[B, H, W, 2]` as the reference's generator yields them or NCHW `[B, 2, H, W]` as the engine
 produces them (the rule of `PostProcess.post_process`); waveforms are fp32 `[B, T]`.  There is no CPU path: tensors live on
-the GPU or the calls raise `ValueError`.  Only the predicted-phase reconstruction is scored (Griffin-Lim is outside the
-device path, features.py).
+the GPU or the calls raise `ValueError`.  `algorithm` selects the reconstruction that is scored, as the reference's argument of
+that name does (rir_generation.py:62, :137): 'ph' from the predicted phase (`features.PostProcess`), 'gl' by Griffin-Lim from
+the predicted magnitude alone (`features.GriffinLim`).
 """
 import csv
 import os
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .features import HOP_LENGTH, N_FFT, STFT_SHAPE, WIN_LENGTH, PostProcess
+from .features import HOP_LENGTH, N_FFT, STFT_SHAPE, WIN_LENGTH, GriffinLim, PostProcess
 
 ROOMS = ("HemiAnechoicRoom", "LargeMeetingRoom", "MediumMeetingRoom", "ShoeBoxRoom", "SmallMeetingRoom")
 METRICS = ("mse_spec", "mse_amp", "phase", "mis_amp", "mse_wav", "mse_wav50", "mis_wav")
@@ -83,19 +84,24 @@ class Evaluator:
     `Autoencoder` of this package).  `diff_gen` (:173-176, :190-193): the phase that is scored and reconstructed is
     `pred[..., 1] + spec_in[..., 1]` while `mse_spec` keeps the raw prediction.  `room` of a batch is a sequence of names out
     of `rooms` or an integer tensor of indices into it, on the device; anything else counts in the global figures only.
+    `algorithm` 'gl' (:176-178 with algorithm='gl'): the waveform comes from `GriffinLim(gl_iters, gl_momentum, seed=gl_seed)` on
+    the predicted magnitude; the phase plane - and `diff_gen`'s sum - still feed the phase figure but not the waveform.
 
     Between construction and `result()` nothing waits for the device.  The running sums, the [B, 7] figures, the waveform
     buffer and the layout staging buffers are allocated for the first batch and reused while the batch size holds.  Stage
     times come from HIP events recorded on the stream and are read in `result()`."""
 
     def __init__(self, model, diff_gen=False, rooms=ROOMS, n50=2400, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH,
-                 hop_length=HOP_LENGTH):
+                 hop_length=HOP_LENGTH, algorithm="ph", gl_iters=32, gl_momentum=0.99, gl_seed=0):
         self.model, self.diff_gen, self.rooms, self.n50 = model, bool(diff_gen), tuple(rooms), int(n50)
         if not self.rooms:
             raise ValueError("at least one room")
+        if algorithm not in ("ph", "gl"):
+            raise ValueError("algorithm must be 'ph' or 'gl'")
+        self.algorithm = algorithm
         self.des_shape, self.n_fft, self.win_length, self.hop_length = tuple(des_shape), n_fft, win_length, hop_length
         self._index = {r: i for i, r in enumerate(self.rooms)}
-        self._post = PostProcess(algorithm="ph")
+        self._post = PostProcess(algorithm="ph") if algorithm == "ph" else GriffinLim(gl_iters, gl_momentum, seed=gl_seed)
         self._acc = None
         self._buf = {}              # name -> kept device buffer
         self._pinned = []           # [pinned int32 buffer, event of the last copy out of it]
@@ -155,7 +161,8 @@ class Evaluator:
             pred = _nchw(self.model.model([x.permute(0, 2, 3, 1), emb], training=False), "prediction", nhwc=True)
         ev[1].record()
         feat = self._stage("pred", pred)
-        if self.diff_gen:                   # :174-175: magnitude as predicted, phase = predicted + input phase (fp32, as there)
+        if self.diff_gen and self.algorithm == "ph":    # :174-175: magnitude as predicted, phase = predicted + input phase (fp32, as
+                                                        # there); Griffin-Lim reads the magnitude alone
             xs = self._stage("spec_in", x)
             s = self._kept("diff", feat.shape, torch.float32, feat.device)
             s[:, 0].copy_(feat[:, 0])

@@ -10,13 +10,15 @@ the reference's names, constructor arguments and call shapes:
     Normalizer().normalize / .denormalize                                                        preprocess.py:21-41
     TensorPadder(desired_shape)                                                                  preprocess.py:60-113
     PreProcess(...)(waveforms)  = mean removal + extract + normalize + pad, fused               dataset.py:146-176
-    PostProcess().post_process(feature, ...) -> waveform (un_pad + denormalize + istft, fused)   postprocess.py:51-73
+    PostProcess().post_process(feature, ...) -> waveform (un_pad + denormalize + istft, fused)   postprocess.py:51-73 'ph'
+    GriffinLim().post_process(feature, ...)  -> waveform (un_pad + denormalize + griffinlim)     postprocess.py:47-50, :130-131 'gl'
 
 Layouts: waveforms fp32 `[B, T]` (or `[T]`), features fp32 NCHW `[B, 2, H, W]` (plane 0 amplitude, plane 1 phase; row =
 frequency bin, column = frame) - the engine's boundary, so a `PreProcess` output feeds `Trainer.step` / `UNet.forward`
-directly; `PostProcess.post_process` also accepts the reference's NHWC `[H, W, 2]` / `[B, H, W, 2]` features.  File decoding
-and writing (`librosa.load`, `scipy.io.wavfile.write`, `np.save`) and the Griffin-Lim branch stay on the host side of the
-boundary and are not reimplemented.  There is no CPU path: tensors must live on the GPU and the calls raise otherwise.
+directly; `PostProcess.post_process` and `GriffinLim.post_process` also accept the reference's NHWC `[H, W, 2]` /
+`[B, H, W, 2]` features.  The Griffin-Lim branch (`algorithm='gl'`) is the whole iteration for a batch in one library call
+(csrc/griffinlim.hip).  File decoding and writing (`librosa.load`, `scipy.io.wavfile.write`, `np.save`) stay on the host side
+of the boundary and are not reimplemented.  There is no CPU path: tensors must live on the GPU and the calls raise otherwise.
 """
 import torch
 
@@ -105,31 +107,79 @@ class PreProcess:
         return out
 
 
+def _feature_nchw(feature, nhwc):
+    """The layout rules of PostProcess.post_process: [H, W, 2], [B, H, W, 2] or [B, 2, H, W] -> (contiguous fp32 [B, 2, H, W],
+    whether a single feature came in)."""
+    if not isinstance(feature, torch.Tensor) or not feature.is_cuda:
+        raise ValueError("features must be CUDA tensors (there is no CPU path)")
+    f = feature
+    single = f.dim() == 3
+    if single:
+        f = f.unsqueeze(0)
+    if nhwc is None:                               # the reference hands over [H, W, 2]; the engine produces [B, 2, H, W]
+        nhwc = f.shape[-1] == 2 and f.shape[1] != 2
+    if nhwc:
+        f = f.permute(0, 3, 1, 2)
+    return f.contiguous().float(), single
+
+
 class PostProcess:
-    """postprocess.py:21-73 without the file writes: post_process(feature) -> waveform(s).  Only the 'ph' (predicted phase)
-    algorithm is provided; 'gl' (librosa.griffinlim) is outside the boundary."""
+    """postprocess.py:21-73 without the file writes: post_process(feature) -> waveform(s).  This class is the 'ph' (predicted
+    phase) algorithm; 'gl' (librosa.griffinlim) is `GriffinLim` below, which has arguments of its own (iterations, momentum,
+    seed) and keeps a workspace."""
 
     def __init__(self, folder=None, algorithm=None):
         if algorithm == "gl":
-            raise NotImplementedError("Griffin-Lim reconstruction is not part of the device path")
+            raise NotImplementedError("PostProcess reconstructs from the predicted phase; Griffin-Lim is features.GriffinLim")
         self.algorithm = "ph"
         self.waveform = None
 
     def post_process(self, feature, vector=None, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH, hop_length=HOP_LENGTH,
                      sr=SAMPLE_RATE, nhwc=None, out=None):
-        if not isinstance(feature, torch.Tensor) or not feature.is_cuda:
-            raise ValueError("features must be CUDA tensors (there is no CPU path)")
-        f = feature
-        single = f.dim() == 3
-        if single:
-            f = f.unsqueeze(0)
-        if nhwc is None:                               # the reference hands over [H, W, 2]; the engine produces [B, 2, H, W]
-            nhwc = f.shape[-1] == 2 and f.shape[1] != 2
-        if nhwc:
-            f = f.permute(0, 3, 1, 2)
-        f = f.contiguous().float()
+        f, single = _feature_nchw(feature, nhwc)
         wav = out if out is not None else torch.empty((f.shape[0], hop_length * (des_shape[1] - 1)), dtype=torch.float32,
                                                       device=f.device)
         ops.istft_features(f, wav, des_shape[0], des_shape[1], n_fft, win_length, hop_length, denormalize=True)
+        self.waveform = wav[0] if single else wav
+        return self.waveform
+
+
+class GriffinLim:
+    """PostProcess with algorithm='gl' (postprocess.py:47-50, :130-131): post_process(feature) -> waveform(s) from the magnitude
+    plane alone, librosa.griffinlim at librosa 0.9.x defaults (PARITY UNPINNED, see csrc/griffinlim.hip) for the whole batch in
+    one call of the library, in fp64 with one rounding to fp32.
+
+    The random initial phases are draw number `draws` of stream `seed` (ops.uniform); the counter advances by one per call, so
+    successive calls get fresh phases and a rebuilt object with the same seed repeats them.  `init_phase` (fp32
+    [B, n_bins, n_frames] or [n_bins, n_frames], turns in [0, 1)) replaces the draw and leaves the counter alone.  The fp64
+    workspace is kept while the shape holds."""
+
+    def __init__(self, n_iter=32, momentum=0.99, pad_mode="reflect", seed=0):
+        if n_iter < 0 or momentum < 0:
+            raise ValueError("n_iter and momentum must not be negative")
+        if pad_mode not in ops.PAD_MODES:
+            raise ValueError(f"pad_mode must be one of {sorted(ops.PAD_MODES)}")
+        self.n_iter, self.momentum, self.pad_mode, self.seed = int(n_iter), float(momentum), pad_mode, int(seed)
+        self.algorithm = "gl"
+        self.waveform = None
+        self.draws = 0
+        self._ws = None
+
+    def post_process(self, feature, vector=None, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH, hop_length=HOP_LENGTH,
+                     sr=SAMPLE_RATE, nhwc=None, out=None, init_phase=None):
+        f, single = _feature_nchw(feature, nhwc)
+        wav = out if out is not None else torch.empty((f.shape[0], hop_length * (des_shape[1] - 1)), dtype=torch.float32,
+                                                      device=f.device)
+        if init_phase is not None:
+            if not isinstance(init_phase, torch.Tensor) or not init_phase.is_cuda:
+                raise ValueError("init_phase must be a CUDA tensor (there is no CPU path)")
+            init_phase = (init_phase.unsqueeze(0) if init_phase.dim() == 2 else init_phase).contiguous().float()
+        if self._ws is None or self._ws.device != f.device:
+            self._ws = ops.Workspace(f.device)
+        ops.griffinlim(f, wav, des_shape[0], des_shape[1], n_fft, win_length, hop_length, self._ws, pad_mode=self.pad_mode,
+                       denormalize=True, n_iter=self.n_iter, momentum=self.momentum, init_phase=init_phase, seed=self.seed,
+                       draw=self.draws)
+        if init_phase is None:
+            self.draws += 1
         self.waveform = wav[0] if single else wav
         return self.waveform

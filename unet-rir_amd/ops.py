@@ -501,6 +501,40 @@ def istft_features(feat, wav, n_bins, n_frames, n_fft=256, win_length=128, hop_l
                                                 int(denormalize), _p(wav), _stream()), "istft_features")
 
 
+def griffinlim_ws_bytes(B, n_bins, n_frames, n_fft):
+    """Bytes of fp64 state `griffinlim` keeps in its workspace (0: a geometry the kernels do not take)."""
+    return int(_lib.lib().unetrir_griffinlim_ws_bytes(int(B), int(n_bins), int(n_frames), int(n_fft)))
+
+
+def griffinlim(feat, wav, n_bins, n_frames, n_fft, win_length, hop_length, ws: Workspace, pad_mode="reflect", denormalize=True,
+               n_iter=32, momentum=0.99, init_phase=None, seed=0, draw=0):
+    """feat fp32 [B, 2, H, W] (plane 0, the magnitude, alone is read) -> wav fp32 [B, hop (n_frames - 1)]: un_pad +
+    Normalizer.denormalize + librosa.griffinlim (postprocess.py:47-50, :69-71, :130-131) for the whole batch, fp64 inside.
+    init_phase fp32 [B, n_bins, n_frames] in turns, or None: draw (seed, draw) of `uniform` over that shape."""
+    if feat.dtype != torch.float32 or wav.dtype != torch.float32 or not feat.is_contiguous() or not wav.is_contiguous():
+        raise ValueError("griffinlim takes contiguous fp32 tensors")
+    if feat.dim() != 4 or feat.shape[1] != 2 or wav.dim() != 2 or wav.shape[0] != feat.shape[0] or \
+            wav.shape[1] != hop_length * (n_frames - 1):
+        raise ValueError("griffinlim: feat [B, 2, H, W], wav [B, hop_length * (n_frames - 1)]")
+    if pad_mode not in PAD_MODES:
+        raise ValueError(f"pad_mode must be one of {sorted(PAD_MODES)}")
+    B, _, H, W = feat.shape
+    if init_phase is not None:
+        _f32c(init_phase, (B, n_bins, n_frames), "init_phase", feat)
+    need = griffinlim_ws_bytes(B, n_bins, n_frames, n_fft)
+    if need:
+        ws.reserve(need)
+    check(_lib.lib().unetrir_griffinlim_f32(_p(feat), B, H, W, n_bins, n_frames, n_fft, win_length, hop_length, PAD_MODES[pad_mode],
+                                            int(denormalize), int(n_iter), float(momentum), _p(init_phase), int(seed), int(draw),
+                                            _p(wav), ws.ptr, ws.nbytes, _stream()), "griffinlim")
+
+
+def uniform(out, seed, step):
+    """Uniform [0, 1) numbers (the random initial phases of librosa.griffinlim, in turns), draw number `step` of stream `seed`
+    (a key of its own beside the dropout masks' and the normal draw's)."""
+    check(_lib.lib().unetrir_uniform_f32(_p(out), out.numel(), int(seed), int(step), _stream()), "uniform")
+
+
 def _f32c(t, shape, what, like):
     if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or t.device != like.device:
         raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on {like.device}")
