@@ -60,10 +60,10 @@ def serving_kernel(L, ConvGeom, name, cin, cout, h, k, s, tr, what):
         if kid == "stem":
             return "stem3x3_bf16_kernel"
         if kid == "conv3x3g pair":
-            return "conv3x3g_bf16_kernel<2, true"
+            return "conv3x3g_bf16_kernel<true"
         if kid == "conv3x3g":
             n_out = cin if what == "dgrad" else cout
-            return "conv3x3g_bf16_kernel<2, false, 64>" if n_out <= 64 else "conv3x3g_bf16_kernel<2, false, 128>"
+            return "conv3x3g_bf16_kernel<false, 64>" if n_out <= 64 else "conv3x3g_bf16_kernel<false, 128>"
         if kid == "conv3x3h":
             return "conv3x3h_bf16_kernel"
         if kid == "conv3x3r":

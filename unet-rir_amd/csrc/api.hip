@@ -76,9 +76,9 @@ extern "C" int unetrir_abl_hog(int n, long long cycles, int lds, void* sink, voi
 }
 #endif
 
-// ---- per-stream ticket slots (kernels.h): a static device array, one slot per (device, stream) in use: the tile tickets of the
-//      persistent convolution kernels (64 group counters + 1 count of finished workgroups).  Zero between launches: every kernel
-//      that uses a slot leaves it cleared.
+// ---- per-stream ticket slots: a static device array, one slot per (device, stream) in use, for the tile tickets of the
+//      persistent convolution kernels (tile_tickets.h has the layout of a slot and the protocol).  Zero between launches: every
+//      kernel that uses a slot leaves it cleared.
 __device__ unsigned g_sched_slots[128][80];
 // A __device__ symbol has one instance PER DEVICE: the table below is keyed by the device that is current at the launch (the
 // reference's own process shape is one process driving several GPUs, main_training.py:56), and a slot by (device, stream).

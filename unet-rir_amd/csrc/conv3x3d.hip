@@ -28,16 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MMA(accv, wfrag, pfrag) \
-    accv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wfrag), __builtin_bit_cast(bf16x8, pfrag), accv, 0, 0, 0)
+#include "lds_dma.h"
+#include "tile_tickets.h"
 
 namespace {
 constexpr int DTR = 8, DTC = 32, DNB = 128;     // output tile: rows, columns, channels
@@ -52,7 +44,6 @@ constexpr int DBIAS = 2 * (DP_BYTES + DW_BYTES);            // 147456
 constexpr int DMAXN = 4064;                      // output channels whose bias fits beside the rings (and 16 bytes of tile tickets)
 constexpr int DSCHED = DBIAS + DMAXN * 4;       // tile tickets handed from thread 0 to the workgroup
 constexpr int DSMEM = DSCHED + 16;              // 163728
-constexpr uint32_t OOB = 0xF0000000u;
 static_assert(DP_INSTR + DW_INSTR == 72, "nine DMA instructions per wave and step");
 
 struct Job { int img, oy0, ox0, n0, redge; uint32_t pbase, wbase; };
@@ -75,8 +66,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
 
     // ---- jobs of this workgroup: XCD x (= blockIdx & 7 under round-robin dispatch) owns a contiguous range of the job list
-    //      which job of its XCD's range a workgroup takes next is decided at run time by tickets (kernels.h, sched_slot; conv3x3p.hip
-    //      has the why); grids that are not a multiple of 8 (fewer jobs than CUs) keep the fixed assignment
+    //      which job of its XCD's range a workgroup takes next is decided at run time by tickets (tile_tickets.h); grids that are
+    //      not a multiple of 8 (fewer jobs than CUs) keep the fixed assignment
     int job0, cnt, kstep, kfirst;                     // range start, jobs in the range; fixed assignment: kfirst, kfirst + kstep, ...
     unsigned* ctr = nullptr;
     if ((gridDim.x & 7) == 0) {
@@ -101,22 +92,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
     {
         float* bl = reinterpret_cast<float*>(smem + DBIAS);
         for (int n = tid; n < a.N; n += 512) bl[n] = a.bias ? a.bias[n] : 0.f;
-        if (tid == 0) {                               // the first two tickets (one round trip)
-            unsigned* tk = reinterpret_cast<unsigned*>(smem + DSCHED);
-            if (ctr) { const unsigned t = __hip_atomic_fetch_add(ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tk[0] = t; tk[1] = t + 1; }
-            else { tk[0] = (unsigned)kfirst; tk[1] = (unsigned)(kfirst + kstep); kstat = 2; }
-        }
+        if (tid == 0) { TICKETS_FIRST_TWO(ctr, smem + DSCHED, (unsigned)kfirst, (unsigned)(kfirst + kstep)); if (!ctr) kstat = 2; }
     }
     __syncthreads();
     const unsigned tk0 = reinterpret_cast<const unsigned*>(smem + DSCHED)[0], tk1 = reinterpret_cast<const unsigned*>(smem + DSCHED)[1];
-    // the last workgroup to leave clears the launch's counters (every workgroup has drawn its last - failing - ticket by then)
-    auto leave = [&]() {
-        if (sched && (gridDim.x & 7) == 0 && tid == 0) {
-            const unsigned d = __hip_atomic_fetch_add(sched + 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (d == gridDim.x - 1)
-                for (int i = 0; i < 65; ++i) __hip_atomic_store(sched + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
+    auto leave = [&]() { if (sched && (gridDim.x & 7) == 0 && tid == 0) TICKETS_LEAVE(sched); };
     if (tk0 >= (unsigned)cnt) { leave(); return; }
     const uint32_t sched_a = lds0 + DSCHED;
 
@@ -154,8 +134,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
     // packed copy (a.wpk): piece k of (channel tile nt, chunk ch) is the 1 KB at ((nt * nch + ch) * 36 + k) * 1024 - contiguous
     const bool packed = a.wpk != nullptr;
     const __amdgpu_buffer_rsrc_t rs_w = packed
-        ? __builtin_amdgcn_make_buffer_rsrc((void*)a.wpk, (short)0, (int)((size_t)ntN * 128 * 9 * C * 2), 0x00020000)
-        : __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, (int)((size_t)a.N * 9 * C * 2), 0x00020000);
+        ? raw_rsrc(a.wpk, (int)((size_t)ntN * 128 * 9 * C * 2))
+        : raw_rsrc(a.w, (int)((size_t)a.N * 9 * C * 2));
     if (packed) {
 #pragma unroll
         for (int j = 4; j < 9; ++j) {
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
     struct Src { __amdgpu_buffer_rsrc_t rs; uint32_t pb, wb; int redge, n0, on; };
     auto step_src = [&](const Job& q, int ch, int on) {
         Src r;
-        r.rs = __builtin_amdgcn_make_buffer_rsrc((void*)(in + q.img * img_elems), (short)0, in_rec, 0x00020000);
+        r.rs = raw_rsrc(in + q.img * img_elems, in_rec);
         r.pb = q.pbase + ch * 32; r.wb = q.wbase + (packed ? ch * 36 * 1024 : ch * 32); r.redge = q.redge; r.n0 = q.n0; r.on = on;
         return r;
     };
@@ -247,11 +227,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
             //      after: thread 0 draws it at the start of this job's LAST step (returning atomic as inline asm: the compiler's own
             //      sequence waits vmcnt(0) on the spot) and waits for it at the end of that step, leaving the step's 9 DMA pieces in flight.
             if (ch == 0 && pending) {
-                unsigned v;
-                asm volatile("ds_read_b32 %0, %1 offset:8" : "=v"(v) : "v"(sched_a));
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned tk = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+                unsigned tk;
+                TICKETS_RECEIVE(tk, sched_a);
                 have_next = tk < (unsigned)cnt;
                 if (have_next) nxt = job_params(job_of(tk));
                 drawing = have_next;
@@ -259,10 +236,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
             }
             unsigned tk_mine = 0xFFFFFFFFu;
             const bool draw = drawing && ch + 1 == nch;
-            if (draw && tid == 0) {
-                if (ctr) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(tk_mine) : "v"((uint64_t)(uintptr_t)ctr), "v"(1u) : "memory");
-                else tk_mine = (unsigned)(kfirst + (kstat++) * kstep);
-            }
+            if (draw && tid == 0) TICKETS_DRAW(tk_mine, ctr, (uint64_t)(uintptr_t)ctr, (unsigned)(kfirst + (kstat++) * kstep));
             const bool same = ch + 1 < nch;
             const Src nx = step_src(same ? cur : nxt, same ? ch + 1 : 0, same || have_next);
             const int nb_ = par ^ 1;
@@ -310,7 +284,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3d_bf16_kernel(const Conv3Args a
             if (draw && tid < 64) {                    // wave 0: the ticket is older than the step's 9 DMA pieces
                 if (tid == 0) {
                     asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-                    asm volatile("ds_write_b32 %0, %1 offset:8" :: "v"(sched_a), "v"(tk_mine) : "memory");
+                    TICKETS_HAND_OVER(sched_a, tk_mine);
                 }
             }
             par ^= 1;

@@ -19,21 +19,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
-
-// The epilogue staging tile is private to a wave: LDS operations of one wave execute in issue order, so its reads see its
-// own earlier writes without a workgroup barrier; this only stops the compiler from moving LDS accesses across the point.
-#define WAVE_LDS_FENCE() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MMA(accv, wfrag, pfrag) \
-    accv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wfrag), __builtin_bit_cast(bf16x8, pfrag), accv, 0, 0, 0)
+#include "conv3x3_tile.h"
 
 namespace {
 constexpr int HPC = 34;                        // patch columns
@@ -64,9 +50,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3h_bf16_kernel(const Conv3Args a
     const int C = a.C;
     const int nch = C / 32;
     const int ldw = 9 * C;
-
-    constexpr uint32_t OOB = 0xF0000000u;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)w, (short)0, (int)((size_t)a.N * ldw * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = raw_rsrc(w, (int)((size_t)a.N * ldw * 2));
     const int slot = lane & 1, sub = lane >> 1;
     // patch half: 5 instructions per wave, instruction i covers patch pixels 32 i .. 32 i + 31 of tile t
     auto tile_origin = [&](int t, int& img, int& y0, int& x0) {
@@ -86,8 +70,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3h_bf16_kernel(const Conv3Args a
         }
     };
     auto image_rsrc = [&](int img) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(in + (size_t)img * a.H * a.W * a.ldi), (short)0,
-                                                 (int)((((size_t)a.H * a.W - 1) * a.ldi + C) * 2), 0x00020000);
+        return raw_rsrc(in + (size_t)img * a.H * a.W * a.ldi, (int)((((size_t)a.H * a.W - 1) * a.ldi + C) * 2));
     };
     // weight tile: 6 instructions of 32 rows; wave w issues instruction w and min(w + 4, 5) (5 twice: uniform DMA counts)
     uint32_t wp[2];
@@ -242,14 +225,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3h_bf16_kernel(const Conv3Args a
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
                 const int n = 32 * j + 8 * qd + 4 * hi;
-                float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (a.bias && n + 3 < a.N) bv = *reinterpret_cast<const float4*>(a.bias + n);
-                else if (a.bias) { float* bp = &bv.x; for (int e = 0; e < 4; ++e) if (n + e < a.N) bp[e] = a.bias[n + e]; }
+                STAGE_BIAS4(bv, n);
                 const f32x16& c = acc[i][j];
-                bf16x4 o;
-                o[0] = (__bf16)(c[4 * qd + 0] + bv.x); o[1] = (__bf16)(c[4 * qd + 1] + bv.y);
-                o[2] = (__bf16)(c[4 * qd + 2] + bv.z); o[3] = (__bf16)(c[4 * qd + 3] + bv.w);
-                *reinterpret_cast<bf16x4*>(stage + l31 * HSROW + n * 2) = o;
+                STAGE4(stage + l31 * HSROW + n * 2, c[4 * qd + 0], c[4 * qd + 1], c[4 * qd + 2], c[4 * qd + 3], bv);
             }
         }
         WAVE_LDS_FENCE();
@@ -259,45 +237,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3h_bf16_kernel(const Conv3Args a
             const int p = ps * 8 + pl;
             const int x = x0 + p;
             if (y >= a.H || x >= a.W || nq >= a.N) continue;
-            uint4 v = *reinterpret_cast<const uint4*>(stage + p * HSROW + cq * 16);
-            const size_t pix = ((size_t)img * a.H + y) * a.W + x;
-            if (addend) {
-                const bf16x8 ad = *reinterpret_cast<const bf16x8*>(addend + pix * a.ldadd + nq);
-                bf16x8 vv = __builtin_bit_cast(bf16x8, v);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) vv[e] = (__bf16)((float)vv[e] + (float)ad[e]);
-                v = __builtin_bit_cast(uint4, vv);
-            }
-            if (a.colstat) {
-                const bf16x8 sv = __builtin_bit_cast(bf16x8, v);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = (float)sv[e]; cs_s[e] += f; cs_q[e] += f * f; }
-            }
-            *reinterpret_cast<uint4*>(out + pix * a.ldo + nq) = v;
+            DRAIN8(stage + p * HSROW + cq * 16, ((size_t)img * a.H + y) * a.W + x, nq);
         }
     }
-    if (a.colstat) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-#pragma unroll
-            for (int off = 8; off < 64; off <<= 1) { cs_s[e] += __shfl_xor(cs_s[e], off); cs_q[e] += __shfl_xor(cs_q[e], off); }
-        }
-        float* red = reinterpret_cast<float*>(smem + 2 * HP_BYTES + 2 * HW_BYTES);       // [4 wm][64 ch][2] in ring slot 2
-        if (lane < 8) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                red[(wm * 64 + lane * 8 + e) * 2 + 0] = cs_s[e];
-                red[(wm * 64 + lane * 8 + e) * 2 + 1] = cs_q[e];
-            }
-        }
-        __syncthreads();
-        if (tid < 128) {
-            const int ch = tid >> 1, st = tid & 1;
-            const float t = ((red[(0 * 64 + ch) * 2 + st] + red[(1 * 64 + ch) * 2 + st]) + red[(2 * 64 + ch) * 2 + st]) +
-                            red[(3 * 64 + ch) * 2 + st];
-            if (ch < a.N) a.colstat[((size_t)tile * a.N + ch) * 2 + st] = t;
-        }
-    }
+    if (a.colstat)                                    // [4 wm][64 ch][2] floats in ring slot 2
+        COLSTAT_FOLD(4, 64, smem + 2 * HP_BYTES + 2 * HW_BYTES, wm, 0, (size_t)tile, 0);
     if (!has_next) break;
     tile = next; img = img_n; y0 = y0_n; x0 = x0_n; rs_in = rs_nx;
 #pragma unroll

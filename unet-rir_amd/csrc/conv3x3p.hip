@@ -15,35 +15,17 @@
 //   * tiles are dealt to the XCDs in contiguous ranges and inside an XCD round-robin, channel tile fastest: the workgroups
 //     that read the same patch run at the same time on one XCD, and a workgroup keeps ONE channel tile for all its tiles
 //     (its kernel tiles stay hot in L2, and its fused column statistics add up per lane).
-// K loop, LDS images, swizzles, ring and waits are those of conv3x3g.hip (16x16x32 body); see there.  Fused column
+// LDS images, swizzles, ring and waits are those of conv3x3g.hip; the K step and the DMA source tables are the same code
+// (conv3x3_tile.h).  Fused column
 // statistics: one row per pixel tile, as conv3x3g writes them (which workgroup serves a tile varies from run to run; the rows do not).
 // Requires C % 32 == 0, N / 128 tiles in {1, 2, 4, 8}, at least 512 tiles; otherwise conv3x3g.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MMA16(accv, wfrag, pfrag) \
-    accv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfrag), __builtin_bit_cast(bf16x8, pfrag), accv, 0, 0, 0)
+#include "conv3x3_tile.h"
+#include "tile_tickets.h"
 
 namespace {
-// sum over the 16 lanes of a DPP row, every lane gets the total: the xor-butterfly order (1, 2, 4, 8) on single vector
-// instructions (quad permutes, then the mirrored half / whole row: after two steps the lanes of a quad hold the same value)
-template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row_sum16(float v) {
-    v = dpp_add<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);     // row_half_mirror
-    return dpp_add<0x140>(v);  // row_mirror
-}
 constexpr int PPC = 34;                     // patch columns
 constexpr int PTR = 16;                     // tile rows
 constexpr int PNPX = (PTR + 2) * PPC;       // 612 patch pixels
@@ -58,9 +40,14 @@ constexpr int PRED_BYTES = 4 * 128 * 2 * 4;
 constexpr int PBIAS = PRED + 2 * PRED_BYTES;           // bias of the workgroup's 128 channels
 constexpr int PSCHED = PBIAS + 128 * 4;                // tile tickets handed from thread 0 to the workgroup
 constexpr int PSMEM = PSCHED + 16;                     // 158224
-constexpr uint32_t OOB = 0xF0000000u;
 
 struct Tile { int img, y0, x0, n0, pix; };
+
+// kernel tile: LDS row (dy * 128 + nl); within the 64 channels of a wave column (nl >> 6) the 16-row MFMA tile t = (nl >> 4) & 3,
+// row r = nl & 15 holds channel 32 (t >> 1) + 8 (r >> 2) + 4 (t & 1) + (r & 3): a lane then owns 8 consecutive channels
+#define PERM_T(nl) (((nl) >> 4) & 3)
+#define PERM_R(nl) ((nl) & 15)
+#define PERM_CHANNEL(nl) (((nl) & 64) + 32 * (PERM_T(nl) >> 1) + 8 * (PERM_R(nl) >> 2) + 4 * (PERM_T(nl) & 1) + (PERM_R(nl) & 3))
 }  // namespace
 
 #ifdef UNETRIR_ABLATIONS
@@ -92,18 +79,19 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
     // tiles; its 32 workgroups take jobs slot, slot + 32, ...: ntN divides 32, so a workgroup keeps channel tile slot % ntN.
     //
     // WHICH pixel tile of its XCD range a workgroup takes next is decided at run time: the 32 / ntN workgroups of a group (XCD,
-    // channel tile) draw tickets from one counter (kernels.h, SchedSlot).  With a fixed assignment a workgroup that cannot be placed
-    // at once - a CU held by another kernel: a collective beside the backward pass, a weight-gradient kernel of the side
-    // stream - leaves its tiles for a second round after everybody else has finished (measured with 32 of 256 CUs held:
-    // 1.6x the launch time; the per-tile kernel: 1.0-1.26x).  With tickets the workgroups that do run share all tiles.
+    // channel tile) draw tickets from one counter (tile_tickets.h has the protocol and the why; the per-tile kernel loses
+    // 1.0-1.26x where a fixed assignment loses 1.6x).
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int nt = slot % ntN, n0 = nt * PBN;
     const int pt0 = xcd * per_xcd, cnt = max(0, min(pix_tiles, (xcd + 1) * per_xcd) - pt0);
     unsigned* ctr = sched ? sched + xcd * 8 + nt : nullptr;
-    int kstat = 0;                                        // sched == nullptr: the fixed assignment q, q + 32 / ntN, ...
-    auto take = [&]() -> unsigned {                       // thread 0 only
+    int kstat = 0;                                        // sched == nullptr: the fixed assignment q, q + 32 / ntN, ... (thread 0)
+#define FIXED_TICKET() ((unsigned)(slot / ntN + (kstat++) * (32 / ntN)))
+    // one ticket the plain way, thread 0 at start-up.  (Only its fixed branch is ever reached - the first two tickets with a counter
+    // come from one atomic - but without the other one the compiler lays out the code in front of the loop differently.)
+    auto take = [&]() -> unsigned {
         if (ctr) return __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return (unsigned)(slot / ntN + (kstat++) * (32 / ntN));
+        return FIXED_TICKET();
     };
     auto tile_of = [&](unsigned ticket) {
         Tile t;
@@ -122,27 +110,18 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
     for (int j = 0; j < 5; ++j) {
         int i = wave + 8 * j;
         if (i > PP_INSTR - 1) i = PP_INSTR - 1;          // the last waves repeat the final instruction (uniform DMA counts)
-        const int p = 16 * i + sub;
-        const int pr = p / PPC, pc = p - pr * PPC;
-        const int gs = slot4 ^ ((pc & 4) >> 1);
+        PATCH_LANE(i, sub, PPC, p, pr, pc);
+        const int gs = DMA_GRANULE(slot4, pc);
         prc[j] = (p < PNPX ? pr : 0xFFFF) | (pc << 16);
         prel[j] = (uint32_t)(((pr * a.W + pc) * a.ldi + gs * 8) * 2);
     }
-    // kernel tile: LDS row (dy * 128 + nl); within the 64 channels of a wave column (nl >> 6) the 16-row MFMA tile t = (nl >> 4) & 3,
-    // row r = nl & 15 holds channel 32 (t >> 1) + 8 (r >> 2) + 4 (t & 1) + (r & 3): a lane then owns 8 consecutive channels
     uint32_t wp[3];
     const int dxs = ((a.flip & 1) ? -C : C) * 2;         // kernel-tap step per dx, bytes
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        const int row = 16 * (wave + 8 * j) + sub;
-        const int dy = row >> 7, nl = row & 127;
-        const int gs = slot4 ^ ((nl & 4) >> 1);
-        const int t = (nl >> 4) & 3, r = nl & 15;
-        const int n = n0 + (nl & 64) + 32 * (t >> 1) + 8 * (r >> 2) + 4 * (t & 1) + (r & 3);
-        const int tap0 = (a.flip & 1) ? 8 - 3 * dy : 3 * dy;
-        wp[j] = n < a.N ? (uint32_t)((n * ldw + tap0 * C + gs * 8) * 2) : OOB;
+        KERNEL_LANE(wp[j], wave + 8 * j, sub, slot4, PBN, PERM_CHANNEL(nl));
     }
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, (int)((size_t)a.N * ldw * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = raw_rsrc(a.w, (int)((size_t)a.N * ldw * 2));
     const int in_rec = (int)((((size_t)a.H * a.W - 1) * a.ldi + C) * 2);
     const size_t img_elems = (size_t)a.H * a.W * a.ldi;
 
@@ -171,7 +150,7 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lptr_t)(dst + (wave + 8 * j) * 1024), 16, wp[j] + off, 0, 0, 0);
     };
     auto image_rsrc = [&](int img) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(in + img * img_elems), (short)0, in_rec, 0x00020000);
+        return raw_rsrc(in + img * img_elems, in_rec);
     };
 
     __bf16* __restrict__ out = (__bf16*)a.out;
@@ -180,11 +159,7 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
     // to it tile after tile: deterministic without atomics across lanes) and the bias of the workgroup's 128 channels
     {
         float* red = reinterpret_cast<float*>(smem + PRED);
-        if (tid == 0) {                                   // the first two tickets
-            unsigned* tk = reinterpret_cast<unsigned*>(smem + PSCHED);
-            if (ctr) { const unsigned t = __hip_atomic_fetch_add(ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tk[0] = t; tk[1] = t + 1; }   // one round trip
-            else { tk[0] = take(); tk[1] = take(); }
-        }
+        if (tid == 0) TICKETS_FIRST_TWO(ctr, smem + PSCHED, take(), take());
         (void)red;
         if (tid < 128) reinterpret_cast<float*>(smem + PBIAS)[tid] = (a.bias && n0 + tid < a.N) ? a.bias[n0 + tid] : 0.f;
     }
@@ -253,11 +228,8 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
                     //      barrier of this tile's first step)
                     if (ch == 0 && dx == 1 && cs_pending >= 0) { flush_row(cs_pending, cs_par ^ 1); cs_pending = -1; }
                     if (ch == 0 && dx == 1 && pending) {
-                        unsigned v;
-                        asm volatile("ds_read_b32 %0, %1 offset:8" : "=v"(v) : "v"(sched_a));
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_sched_barrier(0);
-                        const unsigned tk = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+                        unsigned tk;
+                        TICKETS_RECEIVE(tk, sched_a);
                         have_next = tk < (unsigned)cnt;
                         if (have_next) { nxt = tile_of(tk); rs_nxt = image_rsrc(nxt.img); }
                         pending = false;
@@ -271,34 +243,8 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
                     }
                     const uint32_t ba = lds0 + 2 * PP_BYTES + dx * PW_BYTES + (wn * 64 + l15) * 64 + ((lq << 4) ^ ((l15 & 4) << 3));
                     const uint32_t aa = lds0 + pbuf * PP_BYTES + (4 * wm * PPC + l15 + dx) * 64 + ((lq << 4) ^ (((l15 + dx) & 4) << 3));
-                    u32x4 wf[3][4], pf[6][2];
-#define RDW(dy) DSR128(wf[dy][0], ba, dy * 8192 + 0); DSR128(wf[dy][1], ba, dy * 8192 + 1024); \
-                DSR128(wf[dy][2], ba, dy * 8192 + 2048); DSR128(wf[dy][3], ba, dy * 8192 + 3072)
-#define RDP(r) DSR128(pf[r][0], aa, r * PRP + 0); DSR128(pf[r][1], aa, r * PRP + 1024)
-#define ROWS16(r)                                                                              \
-    _Pragma("unroll") for (int dy = 0; dy < 3; ++dy) {                                         \
-        if (r - dy < 0 || r - dy > 3) continue;                                                \
-        _Pragma("unroll") for (int h = 0; h < 2; ++h)                                          \
-            _Pragma("unroll") for (int t = 0; t < 4; ++t) MMA16(acc[r - dy][h][t], wf[dy][t], pf[r][h]); \
-    }
-                    if (!UNETRIR_ABL(abl, 4)) {
-                    RDW(0); RDP(0); RDW(1); RDP(1); RDW(2); RDP(2);          // 18 reads in flight
-                    __builtin_amdgcn_s_setprio(1);
-                    LGKM_WAIT(12); ROWS16(0);
-                    RDP(3);
-                    LGKM_WAIT(8); ROWS16(1);
-                    RDP(4);
-                    LGKM_WAIT(4); ROWS16(2);
-                    RDP(5);
-                    LGKM_WAIT(4); ROWS16(3);
-                    LGKM_WAIT(2); ROWS16(4);
-                    LGKM_WAIT(0); ROWS16(5);
-                    __builtin_amdgcn_s_setprio(0);
-                    }
+                    if (!UNETRIR_ABL(abl, 4)) CONV3X3_KSTEP(acc, ba, aa, 4, PW_BYTES / 3, PRP, 1024);
                     __builtin_amdgcn_sched_barrier(0);
-#undef RDW
-#undef RDP
-#undef ROWS16
                     // ---- retire what the next step reads; younger DMAs (and, in a tile's first steps, the previous tile's
                     //      output stores, which are older than this step's DMAs only) stay in flight across the barrier
                     if (dx == 0) {
@@ -325,10 +271,7 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
             //      own atomic sequence waits vmcnt(0) on the spot, i.e. for every DMA and store in flight)
             const bool draw = have_next;                 // no further draw after the first ticket past the end
             unsigned tk_mine = 0xFFFFFFFFu;
-            if (draw && tid == 0) {
-                if (ctr) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(tk_mine) : "v"(ctr_addr), "v"(1u) : "memory");
-                else tk_mine = (unsigned)(slot / ntN + (kstat++) * (32 / ntN));
-            }
+            if (draw && tid == 0) TICKETS_DRAW(tk_mine, ctr, ctr_addr, FIXED_TICKET());
             int nst = 0;
             const int nb = n0 + wn * 64 + 8 * lq;
             float bias_[2][8];
@@ -348,8 +291,7 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
             // with the tile-constant part of the address in a scalar register
             const bool fast = !addend && cur.y0 + PTR <= a.H && cur.x0 + 32 <= a.W && n0 + PBN <= a.N;
             if (fast) {
-                const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
-                    (void*)(out + (size_t)cur.img * a.H * a.W * a.ldo), (short)0, (int)((((size_t)a.H * a.W - 1) * a.ldo + a.N) * 2), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rs_out = raw_rsrc(out + (size_t)cur.img * a.H * a.W * a.ldo, (int)((((size_t)a.H * a.W - 1) * a.ldo + a.N) * 2));
                 const int voff = (((cur.y0 + 4 * wm) * a.W + cur.x0 + l15) * a.ldo + nb) * 2;
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -408,7 +350,7 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
             nst_prev = nst;
             if (draw && tid == 0) {
                 if (nst == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                asm volatile("ds_write_b32 %0, %1 offset:8" :: "v"(sched_a), "v"(tk_mine) : "memory");
+                TICKETS_HAND_OVER(sched_a, tk_mine);
             }
             if (a.colstat) {
                 // over the 16 pixel columns of the lane group; lane l15 == 0 then adds to the words it owns (inline asm: an LDS
@@ -450,14 +392,8 @@ __global__ __launch_bounds__(512) void conv3x3p_bf16_kernel(const Conv3Args a, i
         g_stamps_conv3x3p[blockIdx.x & 255][1] = __builtin_amdgcn_s_memrealtime() - sr0;
     }
 #endif
-    // ---- the last workgroup to leave clears the launch's counters for the next launch on this stream (every workgroup has
-    //      drawn its last - failing - ticket before it counts itself out)
-    if (sched && tid == 0) {
-        const unsigned d = __hip_atomic_fetch_add(sched + 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (d == gridDim.x - 1) {
-            for (int i = 0; i < 65; ++i) __hip_atomic_store(sched + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if (sched && tid == 0) TICKETS_LEAVE(sched);
+#undef FIXED_TICKET
 }
 
 namespace {

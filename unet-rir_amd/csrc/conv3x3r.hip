@@ -13,14 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
-
-// The epilogue staging tile is private to a wave: LDS operations of one wave execute in issue order, so its reads see its
-// own earlier writes without a workgroup barrier; this only stops the compiler from moving LDS accesses across the point.
-#define WAVE_LDS_FENCE() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+#include "conv3x3_tile.h"
 
 #define RPC 34          // patch columns (32 + halo)
 #define RKE 32          // input channels per chunk
@@ -183,16 +176,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3r_bf16_kernel(const Conv3Args a
             for (int qd = 0; qd < 4; ++qd) {
                 const int nl = 32 * j + 8 * qd + 4 * hi;
                 const int n = n0 + wn * 64 + nl;
-                float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (a.bias && n + 3 < a.N) bv = *reinterpret_cast<const float4*>(a.bias + n);
-                else if (a.bias) { float* bp = &bv.x; for (int e = 0; e < 4; ++e) if (n + e < a.N) bp[e] = a.bias[n + e]; }
+                STAGE_BIAS4(bv, n);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const f32x16& c = acc[2 * half + i][j];
-                    bf16x4 o;
-                    o[0] = (__bf16)(c[4 * qd + 0] + bv.x); o[1] = (__bf16)(c[4 * qd + 1] + bv.y);
-                    o[2] = (__bf16)(c[4 * qd + 2] + bv.z); o[3] = (__bf16)(c[4 * qd + 3] + bv.w);
-                    *reinterpret_cast<bf16x4*>(stage + (32 * i + l31) * SROW + nl * 2) = o;
+                    STAGE4(stage + (32 * i + l31) * SROW + nl * 2, c[4 * qd + 0], c[4 * qd + 1], c[4 * qd + 2], c[4 * qd + 3], bv);
                 }
             }
         }
@@ -202,47 +190,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3r_bf16_kernel(const Conv3Args a
             const int p = ps * PPP + pl;
             const int y = y0 + 4 * wm + 2 * half + (p >> 5), x = x0 + (p & 31);
             if (y >= a.H || x >= a.W || nq >= a.N) continue;
-            uint4 v = *reinterpret_cast<const uint4*>(stage + p * SROW + cq * 16);
-            const size_t pix = ((size_t)img * a.H + y) * a.W + x;
-            if (addend) {
-                const bf16x8 ad = *reinterpret_cast<const bf16x8*>(addend + pix * a.ldadd + nq);
-                bf16x8 vv = __builtin_bit_cast(bf16x8, v);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) vv[e] = (__bf16)((float)vv[e] + (float)ad[e]);
-                v = __builtin_bit_cast(uint4, vv);
-            }
-            if (a.colstat) {
-                const bf16x8 sv = __builtin_bit_cast(bf16x8, v);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = (float)sv[e]; cs_s[e] += f; cs_q[e] += f * f; }
-            }
-            *reinterpret_cast<uint4*>(out + pix * a.ldo + nq) = v;
+            DRAIN8(stage + p * SROW + cq * 16, ((size_t)img * a.H + y) * a.W + x, nq);
         }
     }
     if constexpr (WN == 1) {
-        if (a.colstat) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-#pragma unroll
-                for (int off = 8; off < 64; off <<= 1) { cs_s[e] += __shfl_xor(cs_s[e], off); cs_q[e] += __shfl_xor(cs_q[e], off); }
-            }
-            float* red = reinterpret_cast<float*>(smem + 4 * 64 * SROW);   // [4 wm][64 ch][2], past the staging tiles
-            if (lane < 8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    red[(wm * 64 + lane * 8 + e) * 2 + 0] = cs_s[e];
-                    red[(wm * 64 + lane * 8 + e) * 2 + 1] = cs_q[e];
-                }
-            }
-            __syncthreads();
-            if (tid < 128) {
-                const int ch = tid >> 1, st = tid & 1;
-                const float t = ((red[(0 * 64 + ch) * 2 + st] + red[(1 * 64 + ch) * 2 + st]) + red[(2 * 64 + ch) * 2 + st]) +
-                                red[(3 * 64 + ch) * 2 + st];
-                const size_t row = ((size_t)img * tiles_y + ty) * tiles_x + tx;
-                if (n0 + ch < a.N) a.colstat[(row * a.N + n0 + ch) * 2 + st] = t;
-            }
-        }
+        if (a.colstat)                                // [4 wm][64 ch][2] floats past the staging tiles
+            COLSTAT_FOLD(4, 64, smem + 4 * 64 * SROW, wm, 0, ((size_t)img * tiles_y + ty) * tiles_x + tx, n0);
     }
 }
 

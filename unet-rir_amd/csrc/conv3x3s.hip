@@ -34,32 +34,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MMA16(accv, wfrag, pfrag) \
-    accv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfrag), __builtin_bit_cast(bf16x8, pfrag), accv, 0, 0, 0)
+#include "lds_dma.h"
+#include "tile_tickets.h"
 
 namespace {
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row_sum16(float v) {       // sum over the 16 lanes of a DPP row, in every lane of the row
-    v = dpp_add<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);     // row_half_mirror
-    return dpp_add<0x140>(v);  // row_mirror
-}
 constexpr int SPC = 34;                         // patch columns
 constexpr int STR = 8;                          // tile rows
 constexpr int SNPX = (STR + 2) * SPC;           // 340 patch pixels
-constexpr uint32_t OOB = 0xF0000000u;
 // CH = 64 (the layers the kernel was built for) or 32 (round 3: the full-resolution 32 -> 32 layers of the residual graphs,
 // dl_models/res_ae.py:466, and of the reference's own number_filters_0 = 32, main_training.py:154-161): values for 64 / 32 channels
 template <int CH> struct SC {
@@ -139,7 +120,7 @@ __global__ __launch_bounds__(512, CH == 32 ? 4 : 2) void conv3x3s_bf16_kernel(co
     const int l15 = lane & 15, lq = lane >> 4;
     const int tiles_x = (a.W + 31) / 32, tiles_y = (a.H + STR - 1) / STR;
     const int nstrips = a.B * tiles_x, njobs = nstrips * nseg;
-    // ---- jobs of this workgroup.  Job = strip * nseg + segment.  With tickets (sched != nullptr: kernels.h, sched_slot) XCD x
+    // ---- jobs of this workgroup.  Job = strip * nseg + segment.  With tickets (sched != nullptr: tile_tickets.h) XCD x
     // (= blockIdx & 7) owns per_xcd consecutive jobs - neighbouring strips and segments share its L2 - and its workgroups draw them
     // from one counter; without, the fixed assignment wg, wg + grid, ... over all jobs.
     int wg = blockIdx.x;
@@ -151,16 +132,12 @@ __global__ __launch_bounds__(512, CH == 32 ? 4 : 2) void conv3x3s_bf16_kernel(co
     const uint64_t ctr_addr = (uint64_t)(uintptr_t)ctr;
     int kfix = 0;                                         // fixed assignment: tickets handed out so far (thread 0)
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
-    if (tid == 0) {                                       // the first two tickets: one round trip
-        unsigned* tk = reinterpret_cast<unsigned*>(smem + T::TICK);
-        if (ctr) { const unsigned t = __hip_atomic_fetch_add(ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tk[0] = t; tk[1] = t + 1; }
-        else { tk[0] = (unsigned)wg; tk[1] = (unsigned)wg + gridDim.x; kfix = 2; }
-    }
+    if (tid == 0) { TICKETS_FIRST_TWO(ctr, smem + T::TICK, (unsigned)wg, (unsigned)wg + gridDim.x); if (!ctr) kfix = 2; }
 
     // ---- the kernel, once per workgroup, in fragment order.  Block (tap, kc, t), lane l: row r = l & 15 of the MFMA A operand is
     // output channel n(t, r) = 32 (t >> 1) + 8 (r >> 2) + 4 (t & 1) + (r & 3); k group l >> 4 = input channels 32 kc + 8 (l >> 4) ..
     {
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, CH * 9 * CH * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = raw_rsrc(a.w, CH * 9 * CH * 2);
         const uint32_t vw = (uint32_t)((8 * (l15 >> 2) + (l15 & 3)) * T::WP + lq * 16);
 #pragma unroll
         for (int j = 0; j < (T::NBLK + 7) / 8; ++j) {
@@ -186,8 +163,7 @@ __global__ __launch_bounds__(512, CH == 32 ? 4 : 2) void conv3x3s_bf16_kernel(co
     }
     int dma_x[T::NJ];                                        // ((pr - 1) W + ix) ldi 2 + 16 sg for this job's strip, or INT_MIN
     auto image_rsrc = [&](int img) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(in + (size_t)img * a.H * a.W * a.ldi), (short)0,
-                                                 (int)((((size_t)a.H * a.W - 1) * a.ldi + CH) * 2), 0x00020000);
+        return raw_rsrc(in + (size_t)img * a.H * a.W * a.ldi, (int)((((size_t)a.H * a.W - 1) * a.ldi + CH) * 2));
     };
     // source granule of LDS slot l % GPP: the granules of a pixel are XOR-swizzled with its column (64 channels: 8 granules, key
     // column & 7; 32 channels: 4 granules, key (column >> 2) & 3 - two pixels share a 128-byte line, four consecutive ones a key)
@@ -352,10 +328,7 @@ __global__ __launch_bounds__(512, CH == 32 ? 4 : 2) void conv3x3s_bf16_kernel(co
         //      the job's first tile, when the DMAs issued after it have landed anyway
         const bool draw = have_next;                      // no further draw after the first ticket past the end
         unsigned tk_mine = 0xFFFFFFFFu;
-        if (draw && tid == 0) {
-            if (ctr) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(tk_mine) : "v"(ctr_addr), "v"(1u) : "memory");
-            else tk_mine = (unsigned)wg + (unsigned)(kfix++) * gridDim.x;
-        }
+        if (draw && tid == 0) TICKETS_DRAW(tk_mine, ctr, ctr_addr, (unsigned)wg + (unsigned)(kfix++) * gridDim.x);
         for (int ty = ty0; ty < ty1; ++ty) {
             const int y0 = ty * STR;
             // ---- the next tile's patch: from this one (two halo rows through LDS, the rest by DMA) or the first of the next job
@@ -422,7 +395,7 @@ __global__ __launch_bounds__(512, CH == 32 ? 4 : 2) void conv3x3s_bf16_kernel(co
             else if (nst == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (ty == ty0 && draw && tid == 0)
-                asm volatile("ds_write_b32 %0, %1" :: "v"(lds0 + T::TICK + 8 + 4 * par), "v"(tk_mine) : "memory");
+                TICKETS_HAND_OVER(lds0 + T::TICK + 4 * par, tk_mine);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -432,11 +405,8 @@ __global__ __launch_bounds__(512, CH == 32 ? 4 : 2) void conv3x3s_bf16_kernel(co
         job = njob;
         have_next = false;
         if (draw) {                                       // the ticket drawn during the job just finished (behind >= 1 barrier)
-            unsigned v;
-            asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(lds0 + T::TICK + 8 + 4 * par));
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            const unsigned tk = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+            unsigned tk;
+            TICKETS_RECEIVE(tk, lds0 + T::TICK + 4 * par);
             have_next = tk < (unsigned)cnt;
             njob = pt0 + (int)tk;
         }
@@ -453,14 +423,7 @@ __global__ __launch_bounds__(512, CH == 32 ? 4 : 2) void conv3x3s_bf16_kernel(co
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no job: the kernel's DMAs must not land in LDS that is no longer ours
     }
 
-    // ---- the last workgroup to leave clears the launch's counters for the next launch on this stream (every workgroup has
-    //      drawn its last - failing - ticket before it counts itself out)
-    if (sched && tid == 0) {
-        const unsigned d = __hip_atomic_fetch_add(sched + 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (d == gridDim.x - 1) {
-            for (int i = 0; i < 65; ++i) __hip_atomic_store(sched + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if (sched && tid == 0) TICKETS_LEAVE(sched);
 }
 
 namespace {

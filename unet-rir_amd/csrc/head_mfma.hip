@@ -13,9 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "lds_dma.h"
 
 #define HM_ROWS 32            // output rows per workgroup
 
@@ -156,7 +154,6 @@ int launch_head_fwd_mfma(const void* x, int ldx, int B, int H, int W, int C, con
 // copies D' in a 6-slot LDS ring (528-byte (n,kw) stride: conflict-free ds_read_b64).  K order inside a 32-pixel step:
 // k = 8*lq + j  <->  pixel 4*lq + j (j < 4) or 16 + 4*lq + j - 4, the same on both operands.
 // ------------------------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_h;
 
 #define HW_XL 80              // x row stride in LDS, elements (160 B)

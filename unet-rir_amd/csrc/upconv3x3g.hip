@@ -14,17 +14,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MMA16(accv, wfrag, pfrag) \
-    accv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfrag), __builtin_bit_cast(bf16x8, pfrag), accv, 0, 0, 0)
+#include "lds_dma.h"
 
 namespace {
 constexpr int QR = 8, QC = 32;                 // coarse tile
@@ -37,7 +27,6 @@ constexpr int QW_INSTR = 9 * QBN / 16;         // 36: [9 taps][64 channels] rows
 constexpr int QW_BYTES = QW_INSTR * 1024;      // 36864
 constexpr int QSMEM = 3 * QP_BYTES + 2 * QW_BYTES;   // 132096
 constexpr int QSROW = 32 * 2 + 16;             // epilogue staging: 32 channels + pad per output pixel
-constexpr uint32_t QOOB = 0xF0000000u;
 }  // namespace
 
 __global__ __launch_bounds__(512) void upconv3x3g_bf16_kernel(const Conv3Args a) {
@@ -63,9 +52,8 @@ __global__ __launch_bounds__(512) void upconv3x3g_bf16_kernel(const Conv3Args a)
     const int nch = C / 32;
     const int ldw = 9 * C;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(in + (size_t)img * a.H * a.W * a.ldi), (short)0, (int)((((size_t)a.H * a.W - 1) * a.ldi + C) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)w, (short)0, (int)((size_t)a.N * ldw * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = raw_rsrc(in + (size_t)img * a.H * a.W * a.ldi, (int)((((size_t)a.H * a.W - 1) * a.ldi + C) * 2));
+    const __amdgpu_buffer_rsrc_t rs_w = raw_rsrc(w, (int)((size_t)a.N * ldw * 2));
     const int slot = lane & 3, sub = lane >> 2;
     uint32_t pa[3];
     int pi[3];
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(512) void upconv3x3g_bf16_kernel(const Conv3Args a)
         const int gs = slot ^ ((pc & 4) >> 1);
         const int iy = y0 - 1 + pr, ix = x0 - 1 + pc;
         const bool ok = p < QNP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        pa[j] = ok ? (uint32_t)(((iy * a.W + ix) * a.ldi + gs * 8) * 2) : QOOB;
+        pa[j] = ok ? (uint32_t)(((iy * a.W + ix) * a.ldi + gs * 8) * 2) : OOB;
     }
     uint32_t wp[5];
     int wi[5];
@@ -92,7 +80,7 @@ __global__ __launch_bounds__(512) void upconv3x3g_bf16_kernel(const Conv3Args a)
         const int t9 = row >> 6, nl = row & 63;
         const int gs = slot ^ ((nl & 4) >> 1);
         const int n = n0 + nl;
-        wp[j] = n < a.N ? (uint32_t)((n * ldw + t9 * C + gs * 8) * 2) : QOOB;
+        wp[j] = n < a.N ? (uint32_t)((n * ldw + t9 * C + gs * 8) * 2) : OOB;
     }
     auto issue_p = [&](int ch) {
         unsigned char* dst = smem + (ch % 3) * QP_BYTES;

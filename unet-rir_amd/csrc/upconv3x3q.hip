@@ -18,16 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define DSR128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MMA16(accv, wfrag, pfrag) \
-    accv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfrag), __builtin_bit_cast(bf16x8, pfrag), accv, 0, 0, 0)
+#include "lds_dma.h"
+#include "tile_tickets.h"
 
 namespace {
 constexpr int QR = 8, QC = 32;                 // coarse tile
@@ -42,7 +34,6 @@ constexpr int QRING = 3 * QP_BYTES + 2 * QW_BYTES;   // 132096
 constexpr int QBIAS = QRING;                   // bias of the workgroup's 64 channels
 constexpr int QSCHED = QBIAS + QBN * 4;          // tile tickets handed from thread 0 to the workgroup
 constexpr int QSMEM = QSCHED + 16;
-constexpr uint32_t QOOB = 0xF0000000u;
 
 struct Tile { int img, y0, x0; };
 }  // namespace
@@ -62,16 +53,16 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
 
     // ---- tiles of this workgroup (see conv3x3p.hip): job = pixel tile * ntN + channel tile, XCD-contiguous ranges
-    //      which pixel tile of its group (XCD, channel tile) a workgroup takes next is decided at run time by tickets (kernels.h,
-    //      sched_slot; conv3x3p.hip has the why)
+    //      which pixel tile of its group (XCD, channel tile) a workgroup takes next is decided at run time by tickets (tile_tickets.h)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int nt = slot % ntN, n0 = nt * QBN;
     const int pt0 = xcd * per_xcd, cnt = max(0, min(pix_tiles, (xcd + 1) * per_xcd) - pt0);
     unsigned* ctr = sched ? sched + xcd * 8 + nt : nullptr;
-    int kstat = 0;                                        // sched == nullptr: the fixed assignment q, q + 32 / ntN, ...
-    auto take = [&]() -> unsigned {                       // thread 0 only
+    int kstat = 0;                                        // sched == nullptr: the fixed assignment q, q + 32 / ntN, ... (thread 0)
+#define FIXED_TICKET() ((unsigned)(slot / ntN + (kstat++) * (32 / ntN)))
+    auto take = [&]() -> unsigned {                       // one ticket the plain way, thread 0 at start-up (see conv3x3p.hip)
         if (ctr) return __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return (unsigned)(slot / ntN + (kstat++) * (32 / ntN));
+        return FIXED_TICKET();
     };
     auto tile_of = [&](unsigned ticket) {
         Tile t;
@@ -82,21 +73,10 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
         return t;
     };
     if (tid < QBN) reinterpret_cast<float*>(smem + QBIAS)[tid] = (a.bias && n0 + tid < a.N) ? a.bias[n0 + tid] : 0.f;
-    if (tid == 0) {                                       // the first two tickets
-        unsigned* tk = reinterpret_cast<unsigned*>(smem + QSCHED);
-        if (ctr) { const unsigned t = __hip_atomic_fetch_add(ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tk[0] = t; tk[1] = t + 1; }   // one round trip
-        else { tk[0] = take(); tk[1] = take(); }
-    }
+    if (tid == 0) TICKETS_FIRST_TWO(ctr, smem + QSCHED, take(), take());
     __syncthreads();
     const unsigned tk0 = reinterpret_cast<const unsigned*>(smem + QSCHED)[0], tk1 = reinterpret_cast<const unsigned*>(smem + QSCHED)[1];
-    // the last workgroup to leave clears the launch's counters (every workgroup has drawn its last - failing - ticket by then)
-    auto leave = [&]() {
-        if (sched && tid == 0) {
-            const unsigned d = __hip_atomic_fetch_add(sched + 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (d == gridDim.x - 1)
-                for (int i = 0; i < 65; ++i) __hip_atomic_store(sched + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
+    auto leave = [&]() { if (sched && tid == 0) TICKETS_LEAVE(sched); };
     if (tk0 >= (unsigned)cnt) { leave(); return; }
     const uint32_t sched_a = lds0 + QSCHED;
 
@@ -126,13 +106,13 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
         const int gs = slot4 ^ ((nl & 4) >> 1);
         const int t = (nl >> 4) & 1, r = nl & 15;
         const int n = n0 + (nl & 32) + 8 * (r >> 2) + 4 * t + (r & 3);
-        wp[j] = n < a.N ? (uint32_t)((n * ldw + t9 * C + gs * 8) * 2) : QOOB;
+        wp[j] = n < a.N ? (uint32_t)((n * ldw + t9 * C + gs * 8) * 2) : OOB;
     }
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, (int)((size_t)a.N * ldw * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = raw_rsrc(a.w, (int)((size_t)a.N * ldw * 2));
     const int in_rec = (int)((((size_t)a.H * a.W - 1) * a.ldi + C) * 2);
     const size_t img_elems = (size_t)a.H * a.W * a.ldi;
     auto issue_p = [&](const Tile& t, int ch, int buf) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(in + t.img * img_elems), (short)0, in_rec, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = raw_rsrc(in + t.img * img_elems, in_rec);
         unsigned char* dst = smem + buf * QP_BYTES;
         const int base = (((t.y0 - 1) * a.W + t.x0 - 1) * a.ldi) * 2 + ch * 64;
 #pragma unroll
@@ -141,7 +121,7 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
             if (i > QP_INSTR - 1) i = QP_INSTR - 1;
             const int iy = t.y0 - 1 + (prc[j] & 0xFFFF), ix = t.x0 - 1 + (prc[j] >> 16);
             const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(dst + i * 1024), 16, ok ? (uint32_t)(base + (int)prel[j]) : QOOB, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(dst + i * 1024), 16, ok ? (uint32_t)(base + (int)prel[j]) : OOB, 0, 0, 0);
         }
     };
     auto issue_w = [&](int ch, int buf) {
@@ -208,16 +188,10 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
             //      sequence would wait vmcnt(0) on the spot), hands it over behind that step's counted wait, everybody reads it in the second
             unsigned tk_mine = 0xFFFFFFFFu;
             const bool draw = drawing && ch == 0;
-            if (draw && tid == 0) {
-                if (ctr) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(tk_mine) : "v"((uint64_t)(uintptr_t)ctr), "v"(1u) : "memory");
-                else tk_mine = (unsigned)(slot / ntN + (kstat++) * (32 / ntN));
-            }
+            if (draw && tid == 0) TICKETS_DRAW(tk_mine, ctr, (uint64_t)(uintptr_t)ctr, FIXED_TICKET());
             if (drawing && ch == 1) {
-                unsigned v;
-                asm volatile("ds_read_b32 %0, %1 offset:8" : "=v"(v) : "v"(sched_a));
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned tk = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+                unsigned tk;
+                TICKETS_RECEIVE(tk, sched_a);
                 have_nn = tk < (unsigned)cnt;
                 tk_nn = tk;
                 drawing = have_nn;
@@ -247,11 +221,9 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { const uint32_t u = bq[e >> 2][e & 3]; bias_[e] = __uint_as_float(u); }
                 }
-                const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
-                    (void*)(out + (size_t)prev.img * OH * OW * a.ldo), (short)0, (int)((((size_t)OH * OW - 1) * a.ldo + a.N) * 2), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rs_out = raw_rsrc(out + (size_t)prev.img * OH * OW * a.ldo, (int)((((size_t)OH * OW - 1) * a.ldo + a.N) * 2));
                 const int vbase = (((2 * (prev.y0 + 2 * wm)) * OW + 2 * (prev.x0 + l15)) * a.ldo + nb) * 2;
-                const __amdgpu_buffer_rsrc_t rs_add = __builtin_amdgcn_make_buffer_rsrc(
-                    (void*)(addend ? addend + (size_t)prev.img * OH * OW * a.ldadd : out), (short)0, (int)((((size_t)OH * OW - 1) * a.ldadd + a.N) * 2), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rs_add = raw_rsrc(addend ? addend + (size_t)prev.img * OH * OW * a.ldadd : out, (int)((((size_t)OH * OW - 1) * a.ldadd + a.N) * 2));
                 const int vadd = (((2 * (prev.y0 + 2 * wm)) * OW + 2 * (prev.x0 + l15)) * a.ldadd + nb) * 2;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
@@ -276,7 +248,7 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
 #pragma unroll
                             for (int e = 0; e < 8; ++e) ov[e] = (__bf16)v[e];
                             const int soff = (((2 * i + (c >> 1)) * OW + 32 * h + (c & 1)) * a.ldo) * 2;
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ov), rs_out, ok ? vbase : (int)QOOB, soff, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ov), rs_out, ok ? vbase : (int)OOB, soff, 0);
                             ++nst;
                         }
                 }
@@ -331,7 +303,7 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
             //      the output stores issued after it stay in flight
             if (more2) { if (nst == 16) asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (draw && tid == 0) asm volatile("ds_write_b32 %0, %1 offset:8" :: "v"(sched_a), "v"(tk_mine) : "memory");   // (older than every request of the step)
+            if (draw && tid == 0) TICKETS_HAND_OVER(sched_a, tk_mine);   // (the ticket is older than every request of the step)
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             ++g;
@@ -380,6 +352,7 @@ __global__ __launch_bounds__(512) void upconv3x3q_bf16_kernel(const Conv3Args a,
                 }
     }
     leave();
+#undef FIXED_TICKET
 }
 
 namespace {

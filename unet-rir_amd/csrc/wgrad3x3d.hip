@@ -25,15 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "lds_dma.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define TRR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM0() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
 namespace {
 constexpr int DPH = 4, DPW = 16;                       // output-pixel patch
@@ -45,7 +38,6 @@ constexpr int DD_INSTR = 2 * DPH * DPW / 8;            // 16: two 64-channel pla
 constexpr int DX_BYTES = DX_INSTR * 1024, DD_BYTES = DD_INSTR * 1024;
 constexpr int DBUF = DX_BYTES + DD_BYTES;              // 56320
 constexpr int DX_PER_WAVE = (DX_INSTR + 7) / 8;        // 5
-constexpr uint32_t DOOB = 0xF0000000u;
 
 __device__ __forceinline__ bf16x8 frag(const u32x2& lo, const u32x2& hi) {
     u32x4 v; v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
@@ -119,8 +111,8 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3d_bf16_kernel(const Wgrad3Args
         const int pyi = rem / a.npx, pxi = rem - pyi * a.npx;
         const int py0 = pyi * DPH, px0 = pxi * DPW;
         const int iy0 = 2 * py0, ix0 = 2 * px0;          // pad_before = 0
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + img * x_img), (short)0, x_rec, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dy + img * d_img), (short)0, d_rec, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx = raw_rsrc(a.x + img * x_img, x_rec);
+        const __amdgpu_buffer_rsrc_t rd = raw_rsrc(a.dy + img * d_img, d_rec);
         unsigned char* xb = smem + buf * DBUF;
         unsigned char* db = xb + DX_BYTES;
         const int xbase = ((iy0 * a.IW + ix0) * a.ldx + c0) * 2;
@@ -131,13 +123,13 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3d_bf16_kernel(const Wgrad3Args
             if (i >= DX_INSTR) continue;                 // wave-uniform
             const int iy = iy0 + (xr_[j] & 255), ix = ix0 + (xr_[j] >> 8);
             const bool ok = gv && xok[j] && iy < a.IH && ix < a.IW;
-            const uint32_t off = ok ? (uint32_t)(xbase + (int)xrel[j]) : DOOB;
+            const uint32_t off = ok ? (uint32_t)(xbase + (int)xrel[j]) : OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(xb + i * 1024), 16, off, 0, 0, 0);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const bool ok = gv && dok[j] && (py0 + (dpix[j] & 255)) < a.OH && (px0 + (dpix[j] >> 8)) < a.OW;
-            const uint32_t off = ok ? (uint32_t)(dbase + (int)drel[j]) : DOOB;
+            const uint32_t off = ok ? (uint32_t)(dbase + (int)drel[j]) : OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lptr_t)(db + (wave + 8 * j) * 1024), 16, off, 0, 0, 0);
         }
     };
@@ -170,7 +162,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3d_bf16_kernel(const Wgrad3Args
     // refilled with rows 2R+4 and 2R+3 once their products are issued.
 #define STEP(R, S0, S1, S2, DC_LO, DC_HI, DN_LO, DN_HI, MORE)                                                     \
     do {                                                                                                            \
-        LGKM0();                                                                                                    \
+        LGKM_WAIT(0);                                                                                                    \
         const bf16x8 fd = frag(DC_LO, DC_HI);                                                                       \
         MM(0, fd, frag(xl[S0][0], xh[S0][0])); MM(1, fd, frag(xl[S0][1], xh[S0][1])); MM(2, fd, frag(xl[S0][2], xh[S0][2])); \
         __builtin_amdgcn_sched_barrier(0);                                                                          \

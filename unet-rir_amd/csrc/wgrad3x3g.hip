@@ -14,15 +14,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
+#include "lds_dma.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define TRR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define LGKM0() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
 namespace {
 constexpr int WTPH = WG_ROW_TPH, WTPW = WG_ROW_TPW;
@@ -31,7 +24,6 @@ constexpr int WX_INSTR = (WXH * WXW + 7) / 8;          // 23 wave-instructions o
 constexpr int WD_INSTR = WTPH * WTPW / 8;              // 16
 constexpr int WX_BYTES = WX_INSTR * 1024, WD_BYTES = WD_INSTR * 1024;
 constexpr int WBUF = WX_BYTES + WD_BYTES;              // 39936
-constexpr uint32_t WOOB = 0xF0000000u;
 
 __device__ __forceinline__ bf16x8 frag(const u32x2& lo, const u32x2& hi) {
     u32x4 v; v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
@@ -131,8 +123,8 @@ __global__ __launch_bounds__(256 * NH, NH == 1 ? 2 : 1) void wgrad3x3g_bf16_kern
         const int pyi = rem / a.npx, pxi = rem - pyi * a.npx;
         q.py0 = pyi * WTPH; q.px0 = pxi * WTPW;
         q.iy0 = q.py0 - a.pad_t; q.ix0 = q.px0 - a.pad_l;
-        q.rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + img * x_img), (short)0, x_rec, 0x00020000);
-        q.rd = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dy + img * d_img), (short)0, d_rec, 0x00020000);
+        q.rx = raw_rsrc(a.x + img * x_img, x_rec);
+        q.rd = raw_rsrc(a.dy + img * d_img, d_rec);
         q.xbase = ((q.iy0 * a.IW + q.ix0) * a.ldx + c0) * 2;       // may be negative; only used for valid pixels
         q.dbase = ((q.py0 * a.OW + q.px0) * a.lddy + n0) * 2;
         return q;
@@ -145,12 +137,12 @@ __global__ __launch_bounds__(256 * NH, NH == 1 ? 2 : 1) void wgrad3x3g_bf16_kern
             if (i > WX_INSTR - 1) i = WX_INSTR - 1;
             const int iy = q.iy0 + xpr[j < 6 ? j : 0], ix = q.ix0 + xpc[j < 6 ? j : 0];
             const bool ok = q.gv && xcok[j < 6 ? j : 0] && (unsigned)iy < (unsigned)a.IH && (unsigned)ix < (unsigned)a.IW;
-            const uint32_t off = ok ? (uint32_t)(q.xbase + (int)xrel[j < 6 ? j : 0]) : WOOB;
+            const uint32_t off = ok ? (uint32_t)(q.xbase + (int)xrel[j < 6 ? j : 0]) : OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(q.rx, (lptr_t)(xb + i * 1024), 16, off, 0, 0, 0);
         } else {
             const int jj = j >= 6 ? j - 6 : 0;
             const bool ok = q.gv && dnok[jj] && (q.py0 + dr_[jj]) < a.OH && (q.px0 + dc_[jj]) < a.OW;
-            const uint32_t off = ok ? (uint32_t)(q.dbase + (int)drel[jj]) : WOOB;
+            const uint32_t off = ok ? (uint32_t)(q.dbase + (int)drel[jj]) : OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(q.rd, (lptr_t)(xb + WX_BYTES + (wave + 4 * jj) * 1024), 16, off, 0, 0, 0);
         }
     };
@@ -189,7 +181,7 @@ __global__ __launch_bounds__(256 * NH, NH == 1 ? 2 : 1) void wgrad3x3g_bf16_kern
     // kh = 0 products are issued), S1, S2 = slots of rows R+1, R+2.
 #define STEP(R, S0, S1, S2, DC_LO, DC_HI, DN_LO, DN_HI, MORE)                                                     \
     do {                                                                                                            \
-        LGKM0();                                                                                                    \
+        LGKM_WAIT(0);                                                                                                    \
         const bf16x8 fd = frag(DC_LO, DC_HI);                                                                       \
         MM(0, fd, frag(xl[S0][0], xh[S0][0])); MM(1, fd, frag(xl[S0][1], xh[S0][1])); MM(2, fd, frag(xl[S0][2], xh[S0][2])); \
         __builtin_amdgcn_sched_barrier(0);                                                                          \
