@@ -11,7 +11,7 @@ dev = "cuda:0"
 spec_in = torch.rand((B, 2, H, H), device=dev); spec_out = torch.rand((B, 2, H, H), device=dev)
 emb = torch.randint(26, 1282, (B, 2, 16), device=dev)
 def step():
-    ml, md = eng.make_dropout_masks()
+    ml, md = eng.make_dropout_mask()
     eng.forward(spec_in, emb, ml, md, target=spec_out, global_batch=B)
     eng.backward()
     eng.adam_step(5e-7)

@@ -18,10 +18,8 @@ import math
 import torch
 
 from . import _lib, ops
-from .engine_base import BN_EPS, BN_MOMENTUM, L2_COEF, EngineBase, ParamSpec
+from .engine_base import BN_EPS, BN_MOMENTUM, EMB_DIM, L2_COEF, VEC_CH, VOCAB, EngineBase, ParamSpec
 from .ops import Act
-
-VOCAB, EMB_DIM, VEC_CH = 2000, 256, 16   # dl_models/u_net.py:255-257
 
 
 def same_out(n, s):
@@ -197,6 +195,7 @@ class UNetEngine(EngineBase):
         F = lambda h, w, c: ops.new_act(B, h, w, c, dev)                      # always fp32
         PAD = self.PAD
         self.x4, self.down, self.y, self.a = A(self.H, self.W, PAD), {}, {}, {}
+        self.x_in = self.x4
         self.cat, self.g_cat = {}, {}
         self.g_down, self.g_y = {}, {}
         for l in range(1, self.L + 1):
@@ -231,10 +230,7 @@ class UNetEngine(EngineBase):
         self.logits, self.g_logits = F(self.H, self.W, 4), A(self.H, self.W, PAD)      # logits stay fp32 for sigmoid + loss
         if self.dtype == "bf16":    # glue to the fp32 information-vector branch
             self.v1x1, self.g_z32 = F(self.h5, self.w5, cL), F(self.h5, self.w5, cL)
-        self.pred = torch.empty((B, 2, self.H, self.W), dtype=torch.float32, device=dev)
-        self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
-        self.reg_out = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.loss_tot = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._alloc_outputs()
         self.bn_affine = {b: torch.empty(2 * self.specs[b + ".gamma"].numel, dtype=torch.float32, device=dev) for b in self.bn_names}
         self.bn_saved = {b: torch.empty(2 * self.specs[b + ".gamma"].numel, dtype=torch.float32, device=dev) for b in self.bn_names}
         self._mask = None             # the dropout keep mask of the last forward pass
@@ -353,19 +349,16 @@ class UNetEngine(EngineBase):
         """spec f32 [B,2,H,W] NCHW, emb int [B,2,16].  With `target` also evaluates compute_loss
         (main_training.py:203-235) and seeds the backward pass.  Returns the NCHW prediction buffer."""
         B, D, p = self.B, self.depth, self.p
-        if tuple(spec.shape) != (B, 2, self.H, self.W) or spec.dtype != torch.float32 or not spec.is_contiguous():
-            raise ValueError(f"spec must be a contiguous float32 [{B},2,{self.H},{self.W}] tensor, got {tuple(spec.shape)} {spec.dtype}")
-        if tuple(emb.shape) != (B,) + self.inf_vector_shape:
-            raise ValueError(f"emb must be [{B},{self.inf_vector_shape}]")
-        if spec.device != self.device:
-            raise ValueError("inputs must live on the engine's device")
+        # EngineBase.load_input in pieces: the hand schedule refreshes the work copies before the index conversion and starts the
+        # information-vector branch on the side stream before the input conversion, so every check comes first, here
+        self._check_batch(spec, "spec")
+        self._check_indices(emb)
+        if target is not None:
+            self._check_batch(target, "target")
         if self.t_dirty or self.training:
             self.refresh_transposed()
-        if emb.dtype not in (torch.int32, torch.int64):
-            emb = emb.to(torch.int64)
-        if emb.device != self.device:      # DataGenerator.__getitem__ hands over host arrays: a small copy, never a host pointer
-            emb = emb.to(self.device)
-        ops.index_to_i32(emb.contiguous(), self.emb_idx)
+        self.set_indices(emb)
+        self._last_spec = spec
         self._mask = dropout_mask
 
         def vec_branch(ws_):
@@ -413,23 +406,17 @@ class UNetEngine(EngineBase):
             ops.head6x6_fwd(cur, p["head.kernel"], p["head.bias"], self.logits)
         else:
             ops.conv2d_fwd(self.geo["head"], cur, p["head.kernel"], p["head.bias"], self.logits)
+        return self.loss_or_sigmoid(target, global_batch, alpha)
+
+    def loss_or_sigmoid(self, target, global_batch, alpha):
+        """The end of a forward pass on the fp32 logits: sigmoid, and with a target compute_loss and dL/dlogits (which seeds backward())."""
         if target is not None:
-            gb = B if global_batch is None else global_batch
-            inv_norm = 1.0 / (2.0 * self.H * self.W * gb)
-            ops.sigmoid_loss(self.logits, target, alpha, inv_norm, self.pred, self.g_logits, self.loss_out, self.ws, **self._loss_extras(spec))
+            gb = self.B if global_batch is None else global_batch
+            ops.sigmoid_loss(self.logits, target, alpha, 1.0 / (2.0 * self.H * self.W * gb), self.pred, self.g_logits, self.loss_out, self.ws,
+                             **self._loss_extras())
         else:
-            self._last_spec = spec
             ops.sigmoid_nchw(self.logits, self.pred)
         return self.pred
-
-    def loss_from_logits(self, target, global_batch=None, alpha=0.9):
-        """compute_loss for the logits of the last forward pass: rewrites the prediction (same values), the data loss and
-        dL/dlogits, which seeds backward()."""
-        gb = self.B if global_batch is None else global_batch
-        if tuple(target.shape) != (self.B, 2, self.H, self.W) or target.dtype != torch.float32 or not target.is_contiguous():
-            raise ValueError(f"target must be a contiguous float32 [{self.B},2,{self.H},{self.W}] tensor")
-        ops.sigmoid_loss(self.logits, target, alpha, 1.0 / (2.0 * self.H * self.W * gb), self.pred, self.g_logits, self.loss_out, self.ws,
-                         **self._loss_extras())
 
     # ------------------------------------------------------------------ backward
     def backward(self, dpred=None, on_ready=None, include_reg=True):
@@ -440,6 +427,7 @@ class UNetEngine(EngineBase):
         # d/dw of (l2(0.001) * sum w^2) / replicas, folded into the split-K reduction of the weight gradient
         reg = 2.0 * L2_COEF / self.n_replicas if include_reg else 0.0
         if dpred is not None:
+            self._check_batch(dpred, "dpred")
             ops.sigmoid_bwd(self.pred, dpred, self.g_logits)
 
         def ready(name):
@@ -544,6 +532,3 @@ class UNetEngine(EngineBase):
         self._end_backward()
 
     # ------------------------------------------------------------------ optimizer: DeviceCounters.adam_step / adam_begin / adam_range
-    def make_dropout_mask(self, generator=None):
-        """Keep mask of Dropout(.3) scaled by 1/(1-p), [B, vec_dim] (EngineBase.dropout_mask)."""
-        return self.dropout_mask(self.vec_dim, generator)

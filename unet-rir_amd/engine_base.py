@@ -1,7 +1,8 @@
 """What the two engine families share: engine.UNetEngine (the hand-scheduled U-Net) and graph.GraphEngine (the closure-list
-executor under UNetGraphEngine, ResAEEngine and AutoencoderEngine) differ in their forward and backward passes only.  The
-parameter store, its work copies and Keras layouts, the initialisers, the l2 term, the dropout mask buffers, the per-step
-device counters and the side-stream hand-overs of the backward pass live here, once.
+executor under UNetGraphEngine and, through ae.AEFamilyEngine, under AutoencoderEngine, ResAEEngine and VAEEngine) differ in their
+forward and backward passes only.  The input gate (every tensor a caller hands over is checked before the first launch), the
+parameter store, its work copies and Keras layouts, the initialisers, the output buffers, the l2 term, the dropout mask buffers,
+the per-step device counters and the side-stream hand-overs of the backward pass live here, once.
 
 Parameters, gradients and Adam moments are four flat fp32 buffers with identical layout, ordered by backward completion so
 gradient buckets for the all-reduce are contiguous slices that become final in order; every offset is a multiple of ALIGN.
@@ -20,6 +21,7 @@ BN_EPS = 1e-3          # keras BatchNormalization default (dl_models/u_net.py:36
 BN_MOMENTUM = 0.99
 L2_COEF = 1e-3         # l2(0.001) on strided Conv2D / Conv2DTranspose kernels (dl_models/u_net.py:274, :302)
 DROPOUT_P = 0.3        # dl_models/u_net.py:260
+VOCAB, EMB_DIM, VEC_CH = 2000, 256, 16   # information vector: Embedding(2000, 256), Reshape((h, w, 16)) (dl_models/u_net.py:255-257)
 ALIGN = 64             # parameter offsets are multiples of 64 floats (256 B)
 # parameter kinds that hold a kernel; *_padin / *_padout: the 2 real input / output channels zero-padded to PAD
 KERNEL_KINDS = ("conv", "convT", "conv_padin", "convT_padout", "conv_padout", "dense")
@@ -84,9 +86,7 @@ class DeviceCounters:
     loss_phase_weight = None     # sigmoid_loss: fp32 [W] column weights of the phase term (device tensor)
     _last_spec = None            # the input of the last forward pass (diff_loss through loss_from_logits)
 
-    def _loss_extras(self, spec=None):
-        if spec is not None:
-            self._last_spec = spec
+    def _loss_extras(self):
         ref = self._last_spec if self.loss_diff else None
         if self.loss_diff and ref is None:
             raise RuntimeError("diff_loss needs the network input of the last forward pass")
@@ -389,7 +389,51 @@ class EngineBase(DeviceCounters):
         """Trainable parameter count in the reference's sense (padding excluded)."""
         return sum(int(math.prod(s_.keras_shape)) for s_ in self.specs.values())
 
+    # ------------------------------------------------------------------ the input gate
+    def _check_batch(self, t, what):
+        """`t` (`what`: spec, target or dpred) goes to a kernel as a raw pointer: anything but a contiguous float32 [B,2,H,W]
+        tensor on the engine's device is refused here, before any launch (a host pointer handed to a kernel is a GPU memory
+        fault, not an exception)."""
+        if tuple(t.shape) != (self.B, 2, self.H, self.W) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+            raise ValueError(f"{what} must be a contiguous float32 [{self.B},2,{self.H},{self.W}] tensor on {self.device}, "
+                             f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+    def _check_indices(self, emb):
+        if tuple(emb.shape) != (self.B,) + self.inf_vector_shape:
+            raise ValueError(f"emb must be [{self.B},{self.inf_vector_shape}], got {tuple(emb.shape)}")
+
+    def set_indices(self, emb):
+        """The information vector's indices (any integer type, host or device) as int32 in the engine's index buffer."""
+        self._check_indices(emb)
+        if emb.dtype not in (torch.int32, torch.int64):
+            emb = emb.to(torch.int64)
+        if emb.device != self.device:      # DataGenerator.__getitem__ hands over host arrays: a small copy, never a host pointer
+            emb = emb.to(self.device)
+        ops.index_to_i32(emb.contiguous(), self.emb_idx)
+
+    def load_input(self, spec, emb):
+        """Check both inputs, then convert them into the engine's buffers: the indices, and the NCHW batch into the padded NHWC
+        input `x_in`.  `spec` is remembered for diff_loss (the phase target is taken relative to the input's phase)."""
+        self._check_batch(spec, "spec")
+        self.set_indices(emb)
+        self._last_spec = spec
+        ops.nchw_to_nhwc_pad(spec, self.x_in)
+
+    def _alloc_outputs(self):
+        """The NCHW prediction and the loss scalars: loss_out = (data loss, amplitude sum, phase sum, -), the l2 terms, their sum."""
+        dev = self.device
+        self.pred = torch.empty((self.B, 2, self.H, self.W), dtype=torch.float32, device=dev)
+        self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.reg_out = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.loss_tot = torch.zeros(1, dtype=torch.float32, device=dev)
+
     # ------------------------------------------------------------------ loss
+    def loss_from_logits(self, target, global_batch=None, alpha=0.9):
+        """compute_loss for the logits of the last forward pass: rewrites the prediction (same values), the data loss and
+        dL/dlogits, which seeds backward()."""
+        self._check_batch(target, "target")
+        self.loss_or_sigmoid(target, global_batch, alpha)
+
     def reg_loss(self, into=None, accumulate=False):
         """sum(model.losses) / replicas (main_training.py:232-233), evaluated on device into reg_out[0] (or added to `into`[0])."""
         out = self.reg_out if into is None else into
@@ -407,6 +451,10 @@ class EngineBase(DeviceCounters):
         self.loss_tot.copy_(self.loss_out[0:1])
         self.reg_loss(into=self.loss_tot, accumulate=True)
         return self.loss_tot
+
+    def make_dropout_mask(self, generator=None):
+        """The U-Net engines' keep mask of Dropout(.3) on the information vector, [B, vec_dim] (the autoencoder family draws its own)."""
+        return self.dropout_mask(self.vec_dim, generator)
 
     def dropout_mask(self, n, generator=None, slot=0):
         """Keep mask [B, n] of Dropout(.3) scaled by 1/(1-p).  Default: the HIP generator kernel, draw number `dropout_step` of

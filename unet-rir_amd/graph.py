@@ -53,6 +53,8 @@ class GraphEngine(EngineBase):
         self.bn_names, self.l2_names = [], []
         self.moving = {}
         self.masks = {}              # dropout keep masks by name (None = no dropout)
+        self.mask_width = {}         # ... and the width of the node each one multiplies
+        self._logits32 = None        # fp32 copy of a bf16 output layer's logits, made on first use
         self.ws = ops.Workspace(self.device, 1 << 20)
         # the split-K reductions of the weight gradients are parked and run together (ops.ReduceBatch): one launch per bucket
         # hand-over / full arena instead of one per convolution (configs[4]: 57 per step).  Every slab set is parked here: measured on
@@ -79,6 +81,12 @@ class GraphEngine(EngineBase):
     def _new(self, h, w, c, needs_grad=True, f32=False):
         """A trunk activation (storage type of the engine) or, f32=True, a node of the fp32 branches."""
         return self._reg(Node(ops.new_act(self.B, h, w, c, self.device, dtype=torch.float32 if f32 else self.adt), needs_grad))
+
+    def _input(self):
+        """The network input: the NCHW batch as NHWC with its 2 channels zero-padded to PAD (EngineBase.load_input writes it)."""
+        self.x4 = self._reg(Node(ops.new_act(self.B, self.H, self.W, self.PAD, self.device, dtype=self.adt), needs_grad=False))
+        self.x_in = self.x4.a
+        return self.x4
 
     def _cast(self, x: Node):
         """The same tensor in the other storage type (fp32 <-> bf16 seam between a Dense branch and the trunk)."""
@@ -315,6 +323,21 @@ class GraphEngine(EngineBase):
         self._push(fwd, bwd)
         return z
 
+    def _concat(self, x: Node, vec: Node):
+        """concatenate([Flatten(x), vec]) as an fp32 [B,1,1,n] node: a copy of two row blocks (the copies convert a bf16 x)."""
+        B, n_x = self.B, x.a.H * x.a.W * x.a.C
+        cat = self._new(1, 1, n_x + vec.a.C, f32=True)
+
+        def fwd():
+            cat.a.base.view(B, -1)[:, :n_x].copy_(x.a.base.view(B, -1))
+            cat.a.base.view(B, -1)[:, n_x:].copy_(vec.a.base.view(B, -1))
+
+        def bwd():
+            x.g.base.view(B, -1).copy_(cat.g.base.view(B, -1)[:, :n_x]); x.g_set = True
+            vec.g.base.view(B, -1).copy_(cat.g.base.view(B, -1)[:, n_x:]); vec.g_set = True
+        self._push(fwd, bwd)
+        return cat
+
     def _dense(self, x: Node, name, n_out):
         return self._conv(x, name, n_out, 1, 1, False, followed_by_bn=False, l2=False, dense=True)
 
@@ -324,6 +347,7 @@ class GraphEngine(EngineBase):
         if x.a.sfx != "f32":
             raise ValueError("Dropout sits on the fp32 Dense branches")
         self.masks.setdefault(which, None)
+        self.mask_width[which] = x.a.C
 
         def fwd():
             m = self.masks[which]
@@ -361,13 +385,6 @@ class GraphEngine(EngineBase):
         self._push(fwd, bwd)
         return node
 
-    def set_indices(self, emb):
-        if emb.dtype not in (torch.int32, torch.int64):
-            emb = emb.to(torch.int64)
-        if emb.device != self.device:      # host arrays from a DataGenerator: a small copy, never a host pointer to the kernel
-            emb = emb.to(self.device)
-        ops.index_to_i32(emb.contiguous(), self.emb_idx)
-
     def _reshape(self, x: Node, h, w, c):
         """Reshape of a [B,1,1,h*w*c] node to NHWC [B,h,w,c] (Keras Reshape is NHWC): a view, gradients alias."""
         v = self._reg(Node(Act(x.a.base.view(self.B, h, w, c)), True, Act(x.g.base.view(self.B, h, w, c))))
@@ -398,6 +415,7 @@ class GraphEngine(EngineBase):
         (gradient bucket all-reduce, trainer.GradBucketer)."""
         self.include_reg = include_reg
         if dpred is not None:
+            self._check_batch(dpred, "dpred")
             ops.sigmoid_bwd(self.pred, dpred, self.logits.g)
             self.logits.g_set = True
         for (_, bwd), end in zip(reversed(self.ops), reversed(self._op_ends)):
@@ -410,7 +428,9 @@ class GraphEngine(EngineBase):
         for node in self.nodes:          # next step: the first writer of every gradient writes again
             node.g_set = False
 
-    def loss_or_sigmoid(self, logits: Node, target, global_batch, alpha):
+    def loss_or_sigmoid(self, target, global_batch, alpha):
+        """The end of a forward pass: sigmoid, and with a target compute_loss and dL/dlogits (which seeds backward())."""
+        logits = self.logits
         la = logits.a
         if la.sfx == "bf16":          # a bf16 output layer (ResAE / Autoencoder): the sigmoid + loss kernel reads fp32 logits
             if self._logits32 is None:
@@ -425,17 +445,3 @@ class GraphEngine(EngineBase):
         else:
             ops.sigmoid_nchw(la, self.pred)
         return self.pred
-
-    def loss_from_logits(self, target, global_batch=None, alpha=0.9):
-        """compute_loss for the logits of the last forward pass (seeds backward())."""
-        if tuple(target.shape) != (self.B, 2, self.H, self.W) or target.dtype != torch.float32 or not target.is_contiguous():
-            raise ValueError(f"target must be a contiguous float32 [{self.B},2,{self.H},{self.W}] tensor")
-        self.loss_or_sigmoid(self.logits, target, global_batch, alpha)
-
-    def _alloc_outputs(self):
-        dev = self.device
-        self.loss_tot = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._logits32 = None
-        self.pred = torch.empty((self.B, 2, self.H, self.W), dtype=torch.float32, device=dev)
-        self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
-        self.reg_out = torch.zeros(1, dtype=torch.float32, device=dev)

@@ -2,15 +2,13 @@
 
 engine.UNetEngine is the hand-scheduled fast path for mode 0 (the only mode the live driver and every BASELINE config
 use); this engine covers mode 1 (convolutional_block_2), mode 2 (residual_block_1) and mode 3 (residual_block_2)
-(dl_models/u_net.py:324-386) with the same kernels, and mode 0 as a cross-check of the hand schedule.
+(dl_models/u_net.py:324-386) with the same kernels, and mode 0 as a cross-check of the hand schedule.  Inputs pass the same gate
+as everywhere (EngineBase.load_input); the dropout mask is the U-Net engines' common one (EngineBase.make_dropout_mask).
 """
 import math
 
-import torch
-
-from . import ops
-from .graph import GraphEngine, Node, RELU
-from .engine import VEC_CH, EMB_DIM
+from .engine_base import VEC_CH
+from .graph import GraphEngine, RELU
 
 
 class UNetGraphEngine(GraphEngine):
@@ -53,9 +51,8 @@ class UNetGraphEngine(GraphEngine):
 
     def _build(self):
         """UNet._build (dl_models/u_net.py:201-251)."""
-        B, dev, D, ch, k = self.B, self.device, self.depth, self.ch, self.k
-        self.x4 = self._reg(Node(ops.new_act(B, self.H, self.W, self.PAD, dev, dtype=self.adt), needs_grad=False))
-        x, h, w = self.x4, self.H, self.W
+        D, ch, k = self.depth, self.ch, self.k
+        x, h, w = self._input(), self.H, self.W
         skips, cats = [], []
         for l in range(1, D + 2):
             c = ch[l - 1]
@@ -86,16 +83,10 @@ class UNetGraphEngine(GraphEngine):
         self.logits = self._head6x6(x, "head")
         self.vec_dim = h5 * w5 * VEC_CH      # l2(0.001) sits only on the strided and the transposed convs (:274, :302)
 
-    def make_dropout_mask(self, generator=None):
-        return self.dropout_mask(self.vec_dim, generator)
-
     def forward(self, spec, emb, dropout_mask=None, target=None, global_batch=None, alpha=0.9):
-        B = self.B
-        if tuple(spec.shape) != (B, 2, self.H, self.W) or spec.dtype != torch.float32 or not spec.is_contiguous():
-            raise ValueError(f"spec must be a contiguous float32 [{B},2,{self.H},{self.W}] tensor")
-        self.set_indices(emb)
+        if target is not None:
+            self._check_batch(target, "target")
+        self.load_input(spec, emb)
         self.masks["vec"] = dropout_mask
-        self._last_spec = spec
-        ops.nchw_to_nhwc_pad(spec, self.x4.a)
         self.run_forward()
-        return self.loss_or_sigmoid(self.logits, target, global_batch, alpha)
+        return self.loss_or_sigmoid(target, global_batch, alpha)
