@@ -1,4 +1,4 @@
-// Stand-alone micro-benchmark of the split-K reduction out[i] = sum_s part[s][i] (igemm.hip: splitk_reduce_kernel): block shapes
+// Stand-alone micro-benchmark of the split-K reduction out[i] = sum_s part[s][i] (splitk_reduce.hip: splitk_reduce_kernel): block shapes
 // (L float4 lanes x G slab groups), slab stride padding, after a writer kernel that leaves the slabs in the caches the way the
 // weight-gradient kernel does.   hipcc --offload-arch=gfx950 -O3 scripts/micro_splitk.hip -o /tmp/ms && /tmp/ms
 #include <hip/hip_runtime.h>

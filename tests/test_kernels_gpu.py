@@ -1387,10 +1387,12 @@ def _tap_table_ab(U, case, switch, fixed, data="uniform"):
     for kk in ("y", "y2", "dx", "yt", "dxt"):
         assert torch.equal(out[1][kk], out[0][kk]), (kk, float((out[1][kk].float() - out[0][kk].float()).abs().max()))
     assert float(out[1]["y"][..., Co:].float().min()) == 3.0
+    for on in (1, 0):                                             # each leg's statistics against its own stored output
+        if out[on]["cs"] is not None:
+            td = out[on]["y2"].double()
+            close(out[on]["cs"][:, 0], td.sum(dim=(0, 1, 2)), 2e-6, f"colstat sum, {switch} = {on}")
+            close(out[on]["cs"][:, 1], (td * td).sum(dim=(0, 1, 2)), 2e-6, f"colstat sum of squares, {switch} = {on}")
     if out[1]["cs"] is not None:
-        td = out[1]["y2"].double()
-        close(out[1]["cs"][:, 0], td.sum(dim=(0, 1, 2)), 2e-6, "colstat sum")
-        close(out[1]["cs"][:, 1], (td * td).sum(dim=(0, 1, 2)), 2e-6, "colstat sum of squares")
         assert out[1]["rows"] >= out[0]["rows"]                   # 64-pixel tiles: at least as many rows as the 128-pixel kernel
     if exact:
         d = lambda t: t.double().cpu()

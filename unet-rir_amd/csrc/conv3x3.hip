@@ -13,9 +13,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "mfma_types.h"
 
 #define TROWS 8
 #define TCOLS 32
@@ -23,23 +21,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define PCOLS (TCOLS + 2)
 #define RSB 144                     // LDS row stride in bytes: 128 B of channels + 16 B pad (conflict-free b128 reads)
 #define NPIX (PROWS * PCOLS)        // 340 patch pixels
-
-template <typename T> struct Elem;
-template <> struct Elem<float> { static constexpr int KE = 32, EPS = 4; };
-template <> struct Elem<__bf16> { static constexpr int KE = 64, EPS = 8; };
-
-__device__ __forceinline__ void mma4(f32x16& acc, const uint4& a, const uint4& b, float) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
-// bf16: the weight fragment is the A operand, so the accumulator comes out TRANSPOSED (rows/registers = output channel,
-// columns/lanes = pixel): a lane then owns 4 consecutive channels per register quad, which pack into 8-byte LDS writes
-// for the staged epilogue (2-byte global stores straight from the MFMA layout cost 35-40 % of the kernel).
-__device__ __forceinline__ void mma4(f32x16& acc, const uint4& a, const uint4& b, __bf16) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), acc, 0, 0, 0);
-}
 
 template <typename T, int BN_>
 __global__ __launch_bounds__(512) void conv3x3_kernel(const Conv3Args a) {
@@ -177,7 +158,6 @@ __global__ __launch_bounds__(512) void conv3x3_kernel(const Conv3Args a) {
         // ---- bf16 epilogue through LDS: acc[i][j] holds D[n = 32j + (r&3) + 8(r>>2) + 4h][pixel = 32i + l31].
         // (1) + bias, pack 4 consecutive channels -> one ds_write_b64 into this wave's [64 px][BN/2 ch] staging tile;
         // (2) read it back as 16-byte channel runs of one pixel and store 16 B per lane (coalesced NHWC rows).
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
         constexpr int WN = BN_ / 2;                       // channels per wave
         constexpr int SROW = WN * 2 + 16;                 // staging row stride in bytes (16-byte pad)
         unsigned char* stage = smem + wave * (64 * SROW); // 8 waves x <= 9216 B, the K loop is over (barrier passed)

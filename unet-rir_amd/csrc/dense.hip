@@ -1,4 +1,5 @@
-// dense.hip - data gradient of Dense(N) on a small batch without a transposed weight copy (gfx950).
+// dense.hip - Dense(N) on a small batch (gfx950): the data gradient without a transposed weight copy (below), and the forward
+// launcher (at the end of the file: the fp32 tap-table kernel of igemm.hip with one tap, split along K).
 //
 //   dx[b][k] = sum_n dy[b][n] * w[n][k]        w = the [N][K] kernel exactly as the forward pass stores it
 //
@@ -84,4 +85,39 @@ int launch_dense_dgrad(const float* dy, int lddy, const float* w, float* dx, int
     int err = (int)hipGetLastError();
     if (err) return err;
     return launch_splitk_rows_reduce((const float*)ws, nsl, B, K, nullptr, dx, lddx, s);
+}
+
+// K slices of the small-batch Dense kernel: with only B <= 128 rows there are ceil(N / 128) (N <= 64: one) output tiles, so K is
+// split until ~512 workgroups stream the weight matrix; a slice keeps at least 256 k-values.  (16 for the U-Net's 8192 -> 4096
+// layer as before; the residual auto-encoder's 66 560 -> 32 latent layer had ONE tile and ran on 16 workgroups: 184 us.)
+static int dense_ksplit(int K, int N) {
+    const int tiles = N > 64 ? (N + 127) / 128 : 1;
+    int ks = (512 + tiles - 1) / tiles;
+    const int maxk = K / 256 > 0 ? K / 256 : 1;
+    if (ks > maxk) ks = maxk;
+    if (ks > 128) ks = 128;
+    if (ks < 1) ks = 1;
+    return ks;
+}
+size_t dense_fwd_ws_bytes(int B, int K, int N) { return (size_t)dense_ksplit(K, N) * B * N * sizeof(float); }
+
+// Dense(N) on a small batch: y[B][N] = x[B][K] . w[N][K]^T + bias.  The weight matrix is streamed once; with only B rows
+// there are N/128 output tiles, so the K dimension is split 16 ways to put >= 2 workgroups on every CU.
+int launch_dense_fwd(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int B, int K, int N,
+                     void* ws, size_t ws_bytes, hipStream_t s) {
+    if (ws_bytes < dense_fwd_ws_bytes(B, K, N)) return UNETRIR_EINVAL;
+    IgemmArgs a{};
+    a.g.B = B; a.g.PH = 1; a.g.PW = 1; a.g.IH = 1; a.g.IW = 1; a.g.C = K; a.g.ldi = ldx;
+    a.g.OH = 1; a.g.OW = 1; a.g.N = N; a.g.ldo = ldy; a.g.SI = 1; a.g.SO = 1;
+    a.g.ntaps = 1; a.g.wtaps = 1; a.g.tap[0] = 0;
+    a.in = x; a.w = w; a.out = y;
+    const int ks = dense_ksplit(K, N);
+    if (ks == 1) {            // enough output tiles on their own: the kernel's ordinary epilogue writes y (+ bias)
+        a.bias = bias; a.ksplit = 0; a.part = nullptr;
+        return launch_igemm_fwd(a, s);
+    }
+    a.ksplit = ks; a.part = (float*)ws;
+    int err = launch_igemm_fwd(a, s);
+    if (err) return err;
+    return launch_splitk_rows_reduce((const float*)ws, ks, B, N, bias, y, ldy, s);
 }

@@ -56,9 +56,9 @@ struct WgradArgs {
     long long chunks_per_split;
 };
 
-int launch_igemm_fwd(const IgemmArgs& a, hipStream_t s);
-int launch_transpose_weight(const float* w, float* wt, int N, int T, int C, hipStream_t s);
-int launch_splitk_reduce(const float* part, int nsplit, size_t n, float* out, float reg, const float* w, hipStream_t s);
+int launch_igemm_fwd(const IgemmArgs& a, hipStream_t s);                                                              // igemm.hip
+int launch_transpose_weight(const float* w, float* wt, int N, int T, int C, hipStream_t s);                          // weights.hip
+int launch_splitk_reduce(const float* part, int nsplit, size_t n, float* out, float reg, const float* w, hipStream_t s);   // splitk_reduce.hip
 
 // ---- weight gradients.  Every kernel below writes fp32 partial slabs [slab][N][taps][C] (grid.y = slab) that a fixed-order split-K
 // reduction sums - or, with one slab and no l2 term, dw itself.  Which kernel serves a layer, how it splits K and what becomes of the
@@ -77,7 +77,7 @@ int launch_splitk_reduce(const float* part, int nsplit, size_t n, float* out, fl
 int wgrad_plan(const IgemmGeom& g, int* nsplit, long long* chunks_per_split);       // the tap-table kernel's own split
 int launch_igemm_wgrad(const WgradArgs& a, int nsplit, hipStream_t s, int bf16_operands);
 
-// 3x3 weight gradient with a halo-staged x patch (wgrad3x3.hip)
+// 3x3 weight gradient with a halo-staged x patch (wgrad3x3.hip: fp32 here, the bf16 twin Wgrad3ArgsH / launch_wgrad3x3_bf16 below)
 struct Wgrad3Args {
     const float* x; int ldx; int IH, IW;      // layer input  [B,IH,IW,C]
     const float* dy; int lddy; int OH, OW;    // output grad  [B,OH,OW,N]
@@ -88,7 +88,7 @@ struct Wgrad3Args {
 };
 int launch_wgrad3x3(const Wgrad3Args& a, int stride, int nslabs, hipStream_t s);
 
-// ---- bf16-storage variants (igemm_bf16.hip): activations / weight work copies bf16, accumulate fp32 ----
+// ---- bf16-storage variants: activations / weight work copies bf16, accumulate fp32.  Tap-table forward kernel: igemm_bf16.hip ----
 struct IgemmArgsH {
     IgemmGeom g;
     const __bf16* in;
@@ -105,7 +105,6 @@ struct IgemmArgsH {
 // (switch off / too large): the general kernel with 128-pixel tiles.
 int igemm_bf16_tile_m(long long M, int N, int ncls);
 int launch_igemm2_fwd_bf16(const IgemmArgsH* a, int ncls, hipStream_t s);
-struct IgemmArgsH4 { IgemmArgsH a[4]; };
 // rows of column statistics one tap-table launch writes (= its pixel tiles)
 inline long long igemm_colstat_rows(long long M, int N, int ncls = 1) {
     const int bm = igemm_bf16_tile_m(M, N, ncls);
@@ -122,7 +121,7 @@ struct Wgrad3ArgsH {
 };
 int launch_igemm_fwd_bf16(const IgemmArgsH& a, hipStream_t s);
 int launch_igemm_fwd_bf16_x4(const IgemmArgsH* a, hipStream_t s);
-int launch_wgrad3x3_bf16(const Wgrad3ArgsH& a, int stride, int nslabs, hipStream_t s);     // the generic patch kernel
+int launch_wgrad3x3_bf16(const Wgrad3ArgsH& a, int stride, int nslabs, hipStream_t s);     // the generic patch kernel (wgrad3x3.hip)
 int launch_wgrad1x1_bf16(const Wgrad3ArgsH& a, int stride, int nslabs, hipStream_t s);
 // Shape rules of the bf16 3x3 weight-gradient kernels.  with_ld = false (the workspace query, which has no pixel strides): the limits
 // that depend on ldx / lddy are left out.
@@ -133,6 +132,7 @@ int launch_wgrad3x3r_bf16(const Wgrad3ArgsH& a, int nslabs, hipStream_t s);
 bool wgrad3x3d_applies(const Wgrad3ArgsH& a, bool with_ld);        // stride 2, even sizes: LDS-DMA kernel with the de-interleaved x patch
 void wgrad3x3d_plan(int B, int OH, int OW, int N, int C, int* nsplit, int* per_split, int* npy, int* npx);     // its own split
 int launch_wgrad3x3d_bf16(Wgrad3ArgsH a, int nslabs, hipStream_t s);
+// bf16 work copies of the fp32 masters (weights.hip)
 int launch_cast_weight(const float* w, void* o, int N, int T, int C, int Cp, hipStream_t s);
 int launch_cast_weights_batched(const unetrir_cast_desc* desc_dev, int n_layers, hipStream_t s);
 int launch_transpose_cast_weight(const float* w, void* wt, int N, int T, int C, int Np, hipStream_t s);
@@ -187,6 +187,7 @@ int launch_conv3x3d_bf16(const Conv3Args& a, hipStream_t s);
 bool conv3x3h_applies(const Conv3Args& a);
 long long conv3x3h_colstat_rows(const Conv3Args& a);
 int launch_conv3x3h_bf16(const Conv3Args& a, hipStream_t s);
+// Dense on a small batch (dense.hip); the row-slab reduction both directions end with is in splitk_reduce.hip
 int launch_dense_fwd(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int B, int K, int N,
                      void* ws, size_t ws_bytes, hipStream_t s);
 size_t dense_fwd_ws_bytes(int B, int K, int N);

@@ -3,13 +3,8 @@
 // Internal to csrc/; include after <hip/hip_runtime.h>.
 #pragma once
 #include <stdint.h>
+#include "mfma_types.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lptr_t;
 
 // Fragment reads are inline asm so that the compiler does not drain the DMA queue in front of them: it waits vmcnt(0) before

@@ -12,10 +12,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+#include "mfma_types.h"
 
 #define UR 8
 #define UC 32
@@ -25,27 +22,12 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #define RSB 144
 #define UBN 64                    // output channels per workgroup (4 parity classes share the accumulator budget)
 
-template <typename T> struct UElem;
-template <> struct UElem<float> { static constexpr int KE = 32, EPS = 4; };
-template <> struct UElem<__bf16> { static constexpr int KE = 64, EPS = 8; };
-
-__device__ __forceinline__ void umma(f32x16& acc, const uint4& a, const uint4& b, float) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
-// bf16: weights as the A operand -> transposed accumulator (registers = channel, lanes = pixel) for the staged epilogue
-__device__ __forceinline__ void umma(f32x16& acc, const uint4& a, const uint4& b, __bf16) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), acc, 0, 0, 0);
-}
-
 // CHUNKED (bf16): a 32-channel chunk (64-byte rows, 80-byte LDS stride) keeps the weights of ALL 9 taps in LDS, so a chunk
 // costs two barriers instead of nine and a patch fragment (2 rows x 2 row offsets x 2 column offsets) is read once for
 // the 9 taps: 17 fragment reads per 18 MFMAs instead of 12 per 8, 36 MFMAs per wave between barriers instead of 8.
 template <typename T, bool CHUNKED = false>
 __global__ __launch_bounds__(512) void upconv3x3_kernel(const Conv3Args a) {
-    constexpr int KE = CHUNKED ? 32 : UElem<T>::KE, EPS = UElem<T>::EPS;
+    constexpr int KE = CHUNKED ? 32 : Elem<T>::KE, EPS = Elem<T>::EPS;
     constexpr int RS = CHUNKED ? 80 : RSB;            // LDS row stride, bytes
     constexpr int SLOTS = KE / EPS;                   // 16-byte slots per row (4 chunked, 8 otherwise)
     constexpr int AJ = (UNP * SLOTS + 511) / 512;     // patch slots per thread
@@ -164,7 +146,7 @@ __global__ __launch_bounds__(512) void upconv3x3_kernel(const Conv3Args a) {
                         const uint4 fb = *reinterpret_cast<const uint4*>(Bs + b_lane + (kh * 3 + kw) * (UBN * RS) + kk * 32);
                         const int cls = (kh & 1) * 2 + (kw & 1);
 #pragma unroll
-                        for (int i = 0; i < 2; ++i) umma(acc[cls][i], fa[i][kh >> 1][kw >> 1], fb, T());
+                        for (int i = 0; i < 2; ++i) mma4(acc[cls][i], fa[i][kh >> 1][kw >> 1], fb, T());
                     }
             }
             __syncthreads();
@@ -204,7 +186,7 @@ __global__ __launch_bounds__(512) void upconv3x3_kernel(const Conv3Args a) {
     #pragma unroll
                         for (int i = 0; i < 2; ++i) {
                             const uint4 fa = *reinterpret_cast<const uint4*>(Ab + i * (UPC * RSB) + kk * 32);
-                            umma(acc[cls][i], fa, fb, T());
+                            mma4(acc[cls][i], fa, fb, T());
                         }
                     }
                     __syncthreads();

@@ -4,7 +4,7 @@
 //   dW[n][kh][kw][c] = sum_p dy[p][n] * x[2p + (kh, kw)][c]        (even sizes: TF 'same' pads (0, 1), pad_before = 0)
 //
 // Stride 2 reads FOUR input pixels per output pixel, so per flop the x operand is 4x the bytes of the stride-1 layer: the
-// register-staged kernel (igemm_bf16.hip, 8 x 4 pixel patches, a barrier pair per 18 MFMAs) reached 0.25 of the MFMA peak.
+// register-staged kernel (wgrad3x3.hip, 8 x 4 pixel patches, a barrier pair per 18 MFMAs) reached 0.25 of the MFMA peak.
 // Here
 //   * a workgroup is 8 waves (one per CU) and owns a 128 (n) x 64 (c) tile - wave (wr, wc) a 32 x 32 tile for all 9 taps (144
 //     accumulators) - and a split-K slice of 4 x 16 output-pixel patches: both operands of a patch are staged ONCE for all

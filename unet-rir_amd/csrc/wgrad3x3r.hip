@@ -2,7 +2,7 @@
 //
 // dW[n][kh][kw][c] = sum_p dy[p][n] * x[p + (kh-1, kw-1)][c]: a GEMM whose K dimension is pixels.  A workgroup (4 waves,
 // each a 32 x 32 (n, c) tile for all 9 taps: 144 accumulator registers) owns a 64 x 64 (n, c) tile and a split-K slice of
-// TPH x 16 pixel patches.  wgrad3x3_bf16_kernel (igemm_bf16.hip) makes one K step of 2 patch rows x 8 pixels and reads
+// TPH x 16 pixel patches.  wgrad3x3_bf16_kernel (wgrad3x3.hip) makes one K step of 2 patch rows x 8 pixels and reads
 // 1 + 9 operand fragments for its 9 MFMAs.  Here a K step is ONE patch row of 16 pixels, so the x fragment of tap
 // (kh, kw) at row r is the fragment of tap (kh-1, kw) at row r+1: a step reads only the three new fragments of x row
 // r + 2 and one dy fragment - 8 ds_read_b64_tr_b16 instead of 20 per 9 v_mfma_f32_32x32x16_bf16.
@@ -11,10 +11,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
+#include "mfma_types.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_r;
 
 #define RW_TPW WG_ROW_TPW
