@@ -556,6 +556,48 @@ int unetrir_vae_sample_kl_bwd_f32(const float* mu, int ld_mu, const float* log_v
                                   unetrir_stream_t stream);
 int unetrir_vae_loss_add_f32(const float* kl_out, float* loss_out, unetrir_stream_t stream);
 
+/* ---- the vector quantiser of the VQ-VAE (dl_models/vqvae.py:42-98, VectorQuantizer; built at :514-518): nearest-code search,
+ *      straight-through output, commitment + codebook loss, and the gradients of both into the layer's input and its codebook.
+ *      PARITY UNPINNED (no TensorFlow here): a restatement of the source text, held to an fp64 restatement and finite differences.
+ *      fp32 in both storage modes.  x / y / dy / dx are NHWC matrices of `rows` pixels with C channels and row strides ld_* >= C;
+ *      `reshape(x, [-1, D])` (:65) cuts every pixel's C channels into C / D consecutive vectors: vector v = p * (C / D) + j starts
+ *      at p * ld + j * D, nothing between C and ld is read or written.  E is the codebook `embeddings` [D][K] (:53-59), dense.
+ *      N = rows * C, r = 1 / replicas (0 switches the loss term and its gradients off).
+ *      UNETRIR_EINVAL before the device is touched: a null pointer; D % 4 != 0 or D outside [4, 64]; K % 4 != 0 or K outside
+ *      [4, 512]; C % D != 0; a row stride < C or not a multiple of 4; rows <= 0 (or rows * C / D >= 2^31); x / y / dy / dx / ws not
+ *      16-byte aligned; ws_bytes < unetrir_vq_ws_bytes().
+ *
+ * unetrir_vq_fwd_f32 (vqvae.py:61-98), ONE launch, one thread per vector, the codebook staged once per workgroup in LDS
+ *   (K * (D + 1) * 4 + 2048 bytes: 18.4 KB at K = 256, D = 16; 135 KB at K = 512, D = 64), no distance or one-hot matrix in memory:
+ *     idx[v] = the lowest k that minimises  dist_k = fl(n_k - 2 s_k)  (one fmaf), where
+ *              s_k = x . E_k  accumulated by fmaf over d = 0 .. D-1 in that order from 0  (vqvae.py:89),
+ *              n_k = ||E_k||^2 accumulated the same way, once per workgroup  (:92);
+ *              the row-constant ||x||^2 of :91 is DROPPED from the comparison (it changes no argmin in exact arithmetic).
+ *              Codes are visited in ascending k and replaced on a strictly smaller distance: ties go to the lowest k, as
+ *              tf.argmin does (:97).  A vector with a NaN gets index 0.
+ *     y      = fl(x + fl(E[:, idx] - x))   the straight-through output of :84 - two roundings, not E[:, idx]
+ *     vq_out[1] = S = sum over all N elements of fl(fl(E[:, idx] - x)^2), summed in fp64: every thread adds its elements in
+ *              order, a fixed tree per workgroup, the workgroups' partials (through ws) in a fixed order that depends on the
+ *              geometry alone, rounded to fp32 once.  Two runs are bit-identical.
+ *     vq_out[0] = fl(scale * vq_out[1]), scale = (float)(r (1 + beta) / N) formed in double: beta * commitment_loss +
+ *              codebook_loss (:79-81) as it enters `loss += sum(model.losses) / replicas` (main_training.py:232-233).
+ *   ws: unetrir_vq_ws_bytes() bytes that belong to the layer; its first 16 bytes must be zero before the first call and every
+ *   call leaves them zero (the arrival counter by which the last workgroup learns that it combines the partials).
+   Above 64 KB of LDS (K (D + 1) > 15 872) every call first raises the kernel's dynamic-LDS limit on the current device, a host-side
+   call outside the stream: make one call at that size before capturing the layer into a HIP graph.
+ * unetrir_vq_bwd_f32, TWO launches, writes (never accumulates) both gradients; dy = d(data term)/dy (straight-through):
+ *     dx        = fmaf(cdx, fl(x - E[:, idx]), dy),  cdx = (float)(2 r beta / N)          elementwise
+ *     dE[:, k]  = fl(cde * sum_{v : idx[v] == k} fl(E[:, k] - x_v)),  cde = (float)(2 r / N)
+ *   the segmented sum without atomics and without a count or offset pass: one workgroup per code scans the indices; its wave w
+ *   takes the vectors [64 w + 256 m, 64 w + 256 m + 64), m = 0, 1, ..., adds its matches in ascending vector order in fp32, and
+ *   the four waves' partials are added in wave order.  A code nobody chose gets exactly 0.  Two runs are bit-identical.
+ *   idx must be what unetrir_vq_fwd_f32 wrote; an index outside [0, K) is clamped for dx and matches no code for dE. */
+size_t unetrir_vq_ws_bytes(void);
+int unetrir_vq_fwd_f32(const float* x, long long rows, int ld, int C, int D, const float* E, int K, float beta, float r, int32_t* idx,
+                       float* y, int ld_y, float* vq_out, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_vq_bwd_f32(const float* x, long long rows, int ld, int C, int D, const int32_t* idx, const float* E, int K, const float* dy,
+                       int ld_dy, float beta, float r, float* dx, int ld_dx, float* dE, unetrir_stream_t stream);
+
 /* ---- input staging for a host-fed train step (DataGenerator.__getitem__, datageneratorv2.py:64-102, hands over host arrays):
  *      for k < n: memcpy src[k] -> pinned[k] (page-locked staging owned by the caller), then an asynchronous host -> device copy
  *      pinned[k] -> dev[k] on `stream`.  One call per batch from the producer thread: the foreign call runs without the

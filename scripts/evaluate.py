@@ -6,9 +6,10 @@
     python scripts/evaluate.py --checkpoint CKPT_DIR --dataset DIR NAME [--rooms ...] [--arrays ...] --out REPORT_DIR
     python scripts/evaluate.py --synthetic 8 --out REPORT_DIR            # no dataset, no checkpoint: random weights and data
 
---load         a folder written by `UNet.save` / `ResAE.save` / `Autoencoder.save` / `VAE.save` (--arch picks the class)
+--load         a folder written by `UNet.save` / `ResAE.save` / `Autoencoder.save` / `VAE.save` / `VQVAE.save` (--arch picks the class)
 --checkpoint   a `CheckpointManager` directory; the latest checkpoint is restored into a U-Net built from --filters / --kernels
-               (--arch vae: into the VAE of rir_generation.py:78-87, latent size --latent)
+               (--arch vae: into the VAE of rir_generation.py:78-87, latent size --latent; --arch vqvae: into the VQ-VAE of
+               dl_models/vqvae.py:522-531)
 --data         a directory of .npz files, one test batch each: spec_in, spec_out fp32 [B, H, W, 2] (or [B, 2, H, W]), emb int
                [B, 2, 16], wav_true fp32 [B, T], room = B room names (or indices into evaluate.ROOMS)
 --dataset      the impulse-response tree DIR/NAME/Room/ZoneX/...Array/*.wav itself: the test partition of `unet_rir_amd.Dataset`
@@ -31,13 +32,18 @@ from unet_rir_amd.features import PostProcess
 
 
 def build_model(a, dev):
-    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder, "vae": U.VAE}[a.arch]
+    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder, "vae": U.VAE, "vqvae": U.VQVAE}[a.arch]
     if a.load:
         return cls.load(a.load, batch_size=a.batch, device=dev)
-    if a.arch == "vae":        # as rir_generation.py:78-87 builds it (latent 32 there, 64 in main_training.py:143-152: --latent)
-        m = U.VAE((a.height, a.width, 2), (2, 16), conv_filters=(64, 128, 256, 512), conv_kernels=(3, 3, 3, 3),
-                  conv_strides=(2, 2, 2, 2), latent_space_dim=a.latent, n_neurons=32 * 64, name=a.name, batch_size=a.batch, device=dev,
-                  dropout=False)
+    if a.arch in ("vae", "vqvae"):
+        if a.arch == "vae":    # as rir_generation.py:78-87 builds it (latent 32 there, 64 in main_training.py:143-152: --latent)
+            m = U.VAE((a.height, a.width, 2), (2, 16), conv_filters=(64, 128, 256, 512), conv_kernels=(3, 3, 3, 3),
+                      conv_strides=(2, 2, 2, 2), latent_space_dim=a.latent, n_neurons=32 * 64, name=a.name, batch_size=a.batch, device=dev,
+                      dropout=False)
+        else:                  # the model of dl_models/vqvae.py's own __main__ block (:522-531)
+            m = U.VQVAE((a.height, a.width, 2), (2, 16), conv_filters=(32, 64, 128, 256), conv_kernels=(3, 3, 3, 3),
+                        conv_strides=(2, 2, 2, 2), latent_space_dim=16, n_neurons=320, name=a.name, batch_size=a.batch, device=dev,
+                        dropout=False)
         if a.checkpoint:
             mgr = U.CheckpointManager(U.Trainer(m.engine, dropout=False), a.checkpoint)
             if mgr.latest_checkpoint is None:
@@ -46,7 +52,7 @@ def build_model(a, dev):
             print("restored", mgr.latest_checkpoint)
         return m
     if a.arch != "unet":
-        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net or a VAE; use --load for the other autoencoders")
+        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net, a VAE or a VQ-VAE; use --load for the other autoencoders")
     m = U.UNet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, kernels=a.kernels, batch_size=a.batch, device=dev,
                dropout=False)
     if a.checkpoint:
@@ -91,7 +97,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--load")
     ap.add_argument("--checkpoint")
-    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae"), default="unet")
+    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae", "vqvae"), default="unet")
     ap.add_argument("--latent", type=int, default=32, help="latent_space_dim of --arch vae built without --load")
     ap.add_argument("--filters", type=int, default=32)
     ap.add_argument("--kernels", type=int, default=3)

@@ -2,6 +2,7 @@
 (optimizer, loss switches, learning rate) -> CheckpointManager -> fit.  One process, one GPU.
 
     python scripts/train.py --dataset ../datasets room_impulse --rooms LargeMeetingRoom --name unet --out ../results/unet
+    python scripts/train.py --synthetic 8 --name vqvae --epochs 3 --lr 1e-4 --out ../results/vqvae       # no data set: 8 random batches
 
 The defaults are main_training.py's (:27-47): target size (144, 160, 2), LargeMeetingRoom, both arrays, debug data set, U-Net,
 alpha 0.9, no sigmoid / diff loss, 500 epochs, lr 5e-7 with the exponential decay from epoch 80, batch 16, Adam.  A run continues
@@ -31,17 +32,22 @@ def build_model(a, dev):
     if a.name == "vae":
         return U.VAE(shape, (2, 16), conv_filters=(64, 128, 256, 512), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
                      latent_space_dim=64, n_neurons=32 * 64, name=a.name, **common)
+    if a.name == "vqvae":      # main_training.py does not build it: the model of dl_models/vqvae.py's own __main__ block (:522-531)
+        return U.VQVAE(shape, (2, 16), conv_filters=(32, 64, 128, 256), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
+                       latent_space_dim=16, n_neurons=320, name=a.name, **common)
     return U.UNet(shape, (2, 16), mode=0, number_filters_0=a.filters, kernels=a.kernels, name="U-Net", **common)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--dataset", nargs=2, metavar=("DIR", "NAME"), required=True, help="the tree is DIR/NAME/Room/ZoneX/...Array/*.wav")
+    ap.add_argument("--dataset", nargs=2, metavar=("DIR", "NAME"), help="the tree is DIR/NAME/Room/ZoneX/...Array/*.wav")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N",
+                    help="instead of --dataset: N batches of synthetic_batches per epoch (the same ones every epoch), no validation")
     ap.add_argument("--rooms", nargs="+", default=["LargeMeetingRoom"], help="room names, or All")
     ap.add_argument("--arrays", nargs="+", default=["PlanarMicrophoneArray", "CircularMicrophoneArray"])
     ap.add_argument("--no-debug", action="store_true", help="load the whole tree (main_training.py runs with debug = True)")
     ap.add_argument("--extract", action="store_true", help="unpack the zone archives first")
-    ap.add_argument("--name", choices=("ae", "resae", "vae", "unet"), default="unet")
+    ap.add_argument("--name", choices=("ae", "resae", "vae", "vqvae", "unet"), default="unet")
     ap.add_argument("--filters", type=int, default=32, help="number_filters_0 of the U-Net")
     ap.add_argument("--kernels", type=int, default=3)
     ap.add_argument("--height", type=int, default=144)
@@ -62,6 +68,18 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("training runs on the GPU; there is none here")
     dev = torch.device("cuda:0")
+    if bool(a.synthetic) == bool(a.dataset):
+        raise SystemExit("give either --dataset DIR NAME or --synthetic N")
+    if a.synthetic:
+        batches = list(U.synthetic_batches(a.synthetic, a.batch, a.height, a.width, dev))
+        model = build_model(a, dev)
+        trainer = U.Trainer(model, lr=a.lr, alpha=a.alpha, sigmoid_loss=a.sigmoid_loss, diff_loss=a.diff_loss, beta=a.beta,
+                            optimizer=a.optimizer)
+        history = U.fit(trainer, lambda epoch: batches, a.epochs, None, lr0=a.lr, lr_exp_decay=(not a.no_lr_decay, a.decay_from))
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "history.json"), "w") as f:
+            json.dump(history, f, indent=1)
+        return
 
     dataset = U.Dataset(a.dataset[0], a.dataset[1], normalization=True, debugging=not a.no_debug, extract=a.extract,
                         room=["All"] if a.rooms == ["All"] else a.rooms, array=a.arrays, device=dev, input_shape=(a.height, a.width))

@@ -200,6 +200,11 @@ _SIGS = {
     "unetrir_vae_sample_kl_bwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float,
                                                 c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
     "unetrir_vae_loss_add_f32": (C.c_int, [c_f32p, c_f32p, c_stream]),
+    "unetrir_vq_ws_bytes": (C.c_size_t, []),
+    "unetrir_vq_fwd_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                     c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_vq_bwd_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, c_f32p, C.c_int, c_f32p, C.c_int,
+                                     C.c_float, C.c_float, c_f32p, C.c_int, c_f32p, c_stream]),
     "unetrir_gather_batch_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, c_f32p, C.c_longlong, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int, c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, c_stream]),
     "unetrir_griffinlim_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -15,7 +15,7 @@ class AEFamilyEngine(GraphEngine):
     entry (Dense -> Dropout -> Reshape), the padded two-channel output layer, and forward / encode / decode over one op list cut
     at the latent node.  A subclass writes `_build` from these pieces and names its two Dropout layers in MASKS."""
     n_dropout_draws = 2               # two Dropout layers: two masks per step
-    MASKS = (None, "dec")             # names in self.masks of the encoder-side Dropout (None: there is none) and the decoder's
+    MASKS = (None, "dec")             # names in self.masks of the encoder-side Dropout and the decoder's (None: there is none)
     DEFAULTS = None                   # (conv_filters, latent_space_dim, n_neurons) main_training.py builds the model with
 
     def __init__(self, H, W, B, conv_filters=None, conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2), latent_space_dim=None,
@@ -96,6 +96,12 @@ class AEFamilyEngine(GraphEngine):
             return (dropout_mask[0] if len(dropout_mask) > 1 else None), dropout_mask[-1]
         return None, dropout_mask
 
+    def _latent_shape(self):
+        """What model.encoder returns, from the latent node: [B, latent_space_dim] for a Dense latent, NHWC [B, h, w, C] for a
+        feature map (vqvae.VQVAEEngine)."""
+        a = self._latent.a
+        return (self.B, a.C) if a.H == a.W == 1 else (self.B, a.H, a.W, a.C)
+
     def _prepare_forward(self, global_batch):
         """Called between the input conversion and the op list of forward / encode (VAEEngine draws its noise here)."""
 
@@ -109,7 +115,8 @@ class AEFamilyEngine(GraphEngine):
         self.load_input(spec, emb)
         if self.MASKS[0] is not None:
             self.masks[self.MASKS[0]] = mask_a
-        self.masks[self.MASKS[1]] = mask_b
+        if self.MASKS[1] is not None:
+            self.masks[self.MASKS[1]] = mask_b
         self._prepare_forward(global_batch)
         self.run_forward()
         return self.loss_or_sigmoid(target, global_batch, alpha)
@@ -121,15 +128,17 @@ class AEFamilyEngine(GraphEngine):
             self.masks[self.MASKS[0]] = self._mask_pair(dropout_mask)[0]
         self._prepare_forward(global_batch)
         self.run_forward(0, self._n_enc_ops)
-        return self._latent.a.base.view(self.B, self.latent).clone()
+        return self._latent.a.base.view(self._latent_shape()).clone()
 
     def decode(self, z, dropout_mask=None):
         """model.decoder(z) (autoencoder.py:222-233, res_ae.py:63, :233-245, vae.py:274-284): z [B, latent_space_dim] -> prediction
         [B,2,H,W] (NCHW buffer)."""
-        if tuple(z.shape) != (self.B, self.latent) or z.dtype != torch.float32:
-            raise ValueError(f"z must be float32 [{self.B},{self.latent}]")
-        self._latent.a.base.view(self.B, self.latent).copy_(z)
-        self.masks[self.MASKS[1]] = self._mask_pair(dropout_mask)[1]
+        shape = self._latent_shape()
+        if tuple(z.shape) != shape or z.dtype != torch.float32:
+            raise ValueError(f"z must be float32 [{','.join(str(n) for n in shape)}]")
+        self._latent.a.base.view(shape).copy_(z)
+        if self.MASKS[1] is not None:
+            self.masks[self.MASKS[1]] = self._mask_pair(dropout_mask)[1]
         self.run_forward(self._n_enc_ops, None)
         return self.loss_or_sigmoid(None, None, 0.9)
 

@@ -312,7 +312,7 @@ class EngineBase(DeviceCounters):
         with torch.no_grad():
             for n, s_ in self.specs.items():
                 t, ks = self.p[n], s_.keras_shape
-                if s_.kind == "embedding":
+                if s_.kind in ("embedding", "codebook"):        # codebook: tf.random_uniform_initializer() (dl_models/vqvae.py:52)
                     t.copy_((torch.rand(s_.shape, generator=generator) * 0.1 - 0.05).to(self.device))
                 elif s_.kind in KERNEL_KINDS:
                     if len(ks) == 4:

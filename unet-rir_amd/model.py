@@ -6,6 +6,7 @@ whose forward and backward run on the HIP engines.
   ``ResAE``  dl_models/res_ae.py:35-70 - the residual autoencoder, with ``.encoder`` / ``.decoder`` / ``.model``
   ``Autoencoder``  dl_models/autoencoder.py:34-62 - the plain conv / conv-transpose autoencoder, same surface
   ``VAE``    dl_models/vae.py:41-77    - the variational autoencoder: ``.encoder`` returns (z, mean, log_var)
+  ``VQVAE``  dl_models/vqvae.py:100-136 - the vector-quantised autoencoder: ``.encoder`` returns the quantised feature map
 
 Both keep the reference's call shape ``model.model([spec_in, emb], training=...)`` (NHWC, main_training.py:261),
 ``model.model.trainable_variables`` / ``.losses``, ``summary()``, ``save()`` / ``load()`` / ``load_weights()``,
@@ -41,6 +42,7 @@ from .engine import L2_COEF, UNetEngine
 from .resae import ResAEEngine
 from .unet_graph import UNetGraphEngine
 from .vae import VAEEngine
+from .vqvae import VQVAEEngine
 
 
 class _ModelFunction(torch.autograd.Function):
@@ -517,3 +519,36 @@ class VAE(_AEFamily):
         is not implemented, and fitting plain MSE under its name would be a different model."""
         raise NotImplementedError("VAE.compile_and_fit (the legacy Keras recipe with its combined loss) is not implemented: "
                                   "use Trainer / fit, the train step of main_training.py")
+
+
+class VQVAE(_AEFamily):
+    """Vector-quantised autoencoder of the reference (dl_models/vqvae.py:100-136; main_training.py does not build it - its own
+    size is the __main__ block's, :522-531: input 160 x 144 x 2, filters (32,64,128,256), kernels 3, strides 2, latent_space_dim 16,
+    n_neurons 320).  Constructor arguments keep the reference's names, order and default (``name="VAE"``, :115); ``batch_size``,
+    ``device``, ``n_replicas``, ``dropout``, ``dtype``, ``overlap`` are additions.
+
+    ``model.encoder([spec, emb], training=...)`` returns the quantiser's output, NHWC ``[B, h, w, conv_filters[-1]]`` (:434, :518),
+    and ``model.decoder`` takes one (:350).  The quantiser has no ``training`` switch: inference quantises too.  Training runs
+    through ``Trainer.step`` / ``fit`` (the quantiser's loss term and its gradients live in the engine's kernels); autograd
+    through the module is not available for this model, so ``forward`` needs ``torch.no_grad()``."""
+    ENGINE = VQVAEEngine
+
+    def __init__(self, input_shape, inf_vector_shape, conv_filters, conv_kernels, conv_strides, latent_space_dim, n_neurons,
+                 name="VAE", **kw):
+        self.reconstruction_loss_weight = 100000           # dl_models/vqvae.py:126 (used by the legacy combined loss only)
+        super().__init__(input_shape, inf_vector_shape, conv_filters, conv_kernels, conv_strides, latent_space_dim, n_neurons,
+                         name, **kw)
+
+    def forward(self, spec, emb, dropout_mask=None):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("VQVAE: the module's autograd bridge carries dL/dprediction only, not the gradient of the "
+                                      "quantiser's loss term into the encoder and the codebook - train with Trainer.step / fit, call "
+                                      "forward under torch.no_grad()")
+        return super().forward(spec, emb, dropout_mask)
+
+    def compile_and_fit(self, *args, **kwargs):
+        """dl_models/vqvae.py:157-195 compiles a combined loss whose KL part reads self.mu / self.log_variance (:268-276), which this
+        class never defines: the recipe cannot run in the reference either, and fitting another loss under its name would be a
+        different model."""
+        raise NotImplementedError("VQVAE.compile_and_fit refers to self.mu / self.log_variance, which dl_models/vqvae.py never "
+                                  "defines: use Trainer / fit, the train step of main_training.py")

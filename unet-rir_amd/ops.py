@@ -772,6 +772,39 @@ def vae_loss_add(kl_out, loss_out):
     check(_lib.lib().unetrir_vae_loss_add_f32(_p(kl_out), _p(loss_out), _stream()), "vae_loss_add")
 
 
+# ---- vector quantiser (dl_models/vqvae.py:42-98) -------------------------------------------------------
+
+def vq_workspace(device):
+    """The quantiser layer's own scratch (include/unetrir.h: zero before the first call, every call leaves its head zero)."""
+    return torch.zeros(_lib.lib().unetrir_vq_ws_bytes(), dtype=torch.uint8, device=device)
+
+
+def _vq_check(x: Act, D, E, idx):
+    if x.sfx != "f32" or E.dtype != torch.float32 or E.dim() != 2 or E.shape[0] != D or not E.is_contiguous():
+        raise ValueError("the quantiser is fp32: x an fp32 Act, E a contiguous float32 [D, K] tensor")
+    if x.C % D or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != x.P * (x.C // D):
+        raise ValueError(f"indices must be a contiguous int32 tensor of {x.P} * {x.C} / {D} elements")
+
+
+def vq_fwd(x: Act, D, E, beta, r, idx, y: Act, vq_out, ws):
+    """VectorQuantizer.call (dl_models/vqvae.py:61-98) in one launch: idx int32 [pixels * C / D], y = x + (E[:, idx] - x),
+    vq_out[1] = S = sum (E[:, idx] - x)^2, vq_out[0] = r (1 + beta) S / N.  ws: vq_workspace()."""
+    _vq_check(x, D, E, idx)
+    if y.sfx != "f32" or (y.P, y.C) != (x.P, x.C) or vq_out.dtype != torch.float32 or vq_out.numel() < 2:
+        raise ValueError("y must be an fp32 Act of x's shape, vq_out float32 [>= 2]")
+    check(_lib.lib().unetrir_vq_fwd_f32(_p(x), x.P, x.ld, x.C, int(D), _p(E), E.shape[1], float(beta), float(r), _p(idx), _p(y), y.ld,
+                                        _p(vq_out), _p(ws), ws.numel(), _stream()), "vq_fwd")
+
+
+def vq_bwd(x: Act, D, idx, E, dy: Act, beta, r, dx: Act, dE):
+    """Backward of vq_fwd (two launches, both outputs written): dx = dy + 2 r beta (x - q) / N, dE[:, k] = 2 r sum_{idx == k} (q - x) / N."""
+    _vq_check(x, D, E, idx)
+    if any(a.sfx != "f32" or (a.P, a.C) != (x.P, x.C) for a in (dy, dx)) or dE.dtype != torch.float32 or dE.shape != E.shape or not dE.is_contiguous():
+        raise ValueError("dy / dx must be fp32 Acts of x's shape, dE a contiguous float32 tensor of E's shape")
+    check(_lib.lib().unetrir_vq_bwd_f32(_p(x), x.P, x.ld, x.C, int(D), _p(idx), _p(E), E.shape[1], _p(dy), dy.ld, float(beta), float(r),
+                                        _p(dx), dx.ld, _p(dE), _stream()), "vq_bwd")
+
+
 def reset_tile_tickets():
     check(_lib.lib().unetrir_reset_tile_tickets(), "reset_tile_tickets")
 

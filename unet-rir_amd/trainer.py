@@ -457,6 +457,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         nb = 0
         has_kl = hasattr(eng, "kl_out")           # VAE: train_loss_kl / val_loss_kl (main_training.py:246-250, :286-288, :318-320)
         ktot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_kl else None      # raw KL sums: training, validation
+        has_vq = hasattr(eng, "vq_out")           # VQ-VAE: the quantiser's S = sum (q - x)^2 of every step (dl_models/vqvae.py:79-80)
+        qtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_vq else None
         eng.reg_loss()
         reg0 = eng.reg_out[0].double()           # l2 terms on the weights the first step of the epoch sees
         for spec_in, emb, spec_out in train_batches(epoch):
@@ -464,6 +466,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
             tot[:3] += eng.loss_out[:3].double()     # total data loss, amplitude term, phase term of this step (raw sums ~1e5: fp64)
             if has_kl:
                 ktot[0] += eng.kl_out[1].double()
+            if has_vq:
+                qtot[0] += eng.vq_out[1].double()
             nb += 1
         # the l2 terms drift over an epoch (Adam moves every weight by ~lr per step whatever the gradient's scale): the reported
         # mean takes the trapezoid of their value before the first and after the last step instead of nine reductions per step
@@ -476,6 +480,9 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         if has_kl:         # tf.keras.metrics.Mean over every (b, l) element of kl_loss_object, across steps and replicas
             per_kl = 1.0 / (eng.kl_elems * trainer.world_size)
             rec["train_kl"] = float(reduce_(ktot[0:1].clone())[0]) * per_kl / n
+        if has_vq:         # mean((q - x)^2) over every element, across steps and replicas
+            per_vq = 1.0 / (eng.vq_elems * trainer.world_size)
+            rec["train_vq"] = float(reduce_(qtot[0:1].clone())[0]) * per_vq / n
         if val_batches is not None:
             vt = torch.zeros(3, dtype=torch.float64, device=eng.device)
             vb = 0
@@ -488,6 +495,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 vt += eng.loss_out[:3].double()
                 if has_kl:
                     ktot[1] += eng.kl_out[1].double()
+                if has_vq:
+                    qtot[1] += eng.vq_out[1].double()
                 vb += 1
             if saved_moving is not None:
                 for k, v in saved_moving.items():
@@ -497,6 +506,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
             rec.update(val_loss=float(vt[0]) / m, val_amp=float(vt[1]) * per_elem / m, val_phase=float(vt[2]) * per_elem / m)
             if has_kl:
                 rec["val_kl"] = float(reduce_(ktot[1:2].clone())[0]) * per_kl / m
+            if has_vq:
+                rec["val_vq"] = float(reduce_(qtot[1:2].clone())[0]) * per_vq / m
         if manager is not None and epoch % 2 == 0:
             rec["checkpoint"] = manager.save(epoch=epoch)
         history.append(rec)
