@@ -342,9 +342,20 @@ int unetrir_splitk_reduce_batched(const unetrir_reduce_desc* desc, int n, unetri
  * 16 input channels at a time; from the [N][9][C] copy that is a gather of 32-byte pieces.  A PACKED copy holds the same values
  * in the order the kernel's LDS-DMA reads them - [N / 128][C / 16][9 taps][4 blocks of 32 channels][64 lanes][8 values], lane =
  * (row of the block, permuted as the MFMA accumulator layout wants it; 8-channel half) - so every DMA piece is 1 KB of
- * contiguous memory (measured: 22-26 us of 100-160 per launch).  unetrir_cast_weights_batched_bf16 writes it when the
- * descriptor carries a destination; the _packed entry points take it beside the plain copy (NULL: plain copy only).
- * unetrir_conv3x3s2_packed_elems returns the element count of the packed copy, 0 where none is defined (N or C not a
+ * contiguous memory (measured: 22-26 us of 100-160 per launch).  In full, element (n, t, c) of the [N][9][C] kernel lies at
+ *   group   n / 128        (N / 128 rounded up: a last group of 64 channels fills blocks 0 and 1, blocks 2 and 3 are never written)
+ *   chunk   c / 16         (16 input channels)
+ *   tap     t              (0 .. 8)
+ *   block   (n / 32) % 4   (32 output channels)
+ *   lane    row + 32 * ((c / 8) % 2), where row is the position m = n % 32 of the channel in its block with bits 2 and 3 of m
+ *           exchanged: m = 16 a + 8 b + 4 c' + d (a, b, c' in {0, 1}, d in 0 .. 3) sits in row 16 a + 8 c' + 4 b + d.  (Lane half h
+ *           of a 32 x 32 MFMA accumulator holds rows 8 j + 4 h + e, j, e in 0 .. 3: with this order they are the channels
+ *           8 h .. 8 h + 7 and 16 + 8 h .. 16 + 8 h + 7 of the block - two runs of 8 consecutive channels, two 16-byte stores.)
+ *   value   c % 8
+ * with every dimension contiguous inside the one before it.  unetrir_cast_weights_batched_bf16 writes it when the
+ * descriptor carries a destination, T == 9 and C % 16 == 0 - whether or not the descriptor also asks for the `same` or the
+ * transposed copy - and never touches it otherwise; the _packed entry points take it beside the plain copy (NULL: plain copy
+ * only).  unetrir_conv3x3s2_packed_elems returns the element count of the packed copy, 0 where none is defined (N or C not a
  * multiple of 64). */
 size_t unetrir_conv3x3s2_packed_elems(int N, int C);
 int unetrir_conv2d_fwd_packed_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* w,

@@ -834,7 +834,10 @@ def _head_exact(ops, B, H, W, Cc):
         assert float(dxa.base[..., :8].float().min()) == 3.0 and float(dxa.base[..., :8].float().max()) == 3.0
 
 
-@X.parametrize_kinds("B,K,N", [(32, 8192, 4096), (3, 520, 72), (4, 4096, 8192), (32, 64, 46080), (32, 48128, 64)])
+@X.parametrize_kinds("B,K,N", [(32, 8192, 4096), (3, 520, 72), (4, 4096, 8192), (32, 64, 46080), (32, 48128, 64),
+                               # forward K-splits 1, 3, 5, 7, 8, 9 and data-gradient slice counts 1, 2, 9: a last slice of one row, K below
+                               # one column strip, B at 1, 31 and 32
+                               (1, 256, 8), (31, 776, 64), (32, 1300, 40), (5, 1800, 129), (32, 2048, 72), (3, 2400, 200), (2, 260, 1025)])
 def test_dense_split_k(U, B, K, N, data):
     """Dense on a small batch through the split-K entry point (dl_models/u_net.py:259) and its data gradient."""
     ops = U.ops
@@ -848,23 +851,27 @@ def test_dense_split_k(U, B, K, N, data):
         w = torch.tensor(detrand.uniform(f"dw{K,N}", (N, K), -1, 1)) * 0.05
         b = torch.tensor(detrand.uniform(f"db{N}", (N,), -1, 1))
     xa = ops.Act(x.view(B, 1, 1, K).to(DEV))
-    ya = ops.Act(torch.full((B, 1, 1, N), 7.0, device=DEV))
+    ldn = -(-N // 4) * 4                 # ops.Act keeps pixel strides at multiples of 4 floats: an odd N lives in a padded row
+    ya = ops.Act(torch.full((B, 1, 1, ldn), 7.0, device=DEV), 0, N)
     ws = ops.Workspace(DEV)
     ops.dense_fwd(xa, w.to(DEV), b.to(DEV), ya, ws)
     torch.cuda.synchronize()
-    cmp32(exact, ya.base.view(B, N), x.double() @ w.double().t() + b.double(), 2e-6 * math.sqrt(K) + 1e-6, "dense fwd")
+    cmp32(exact, ya.base.view(B, ldn)[:, :N], x.double() @ w.double().t() + b.double(), 2e-6 * math.sqrt(K) + 1e-6, "dense fwd")
+    assert bool((ya.base.view(B, ldn)[:, N:] == 7.0).all())
     # data gradient from the kernel as stored (no transposed copy): dx = dy . w, rows beyond B untouched, ld > K honoured
     dy = X.acts(f"ddy{B,N}", (B, N)).float() if exact else torch.tensor(detrand.uniform(f"ddy{B,N}", (B, N), -1, 1))
     assert ops.dense_dgrad_supported(B, K, N) == (B <= 32 and K % 4 == 0)
     if ops.dense_dgrad_supported(B, K, N):
         ldx = K + 8
         dxa = ops.Act(torch.full((B, 1, 1, ldx), 7.0, device=DEV), 0, K)
-        ops.dense_dgrad(ops.Act(dy.view(B, 1, 1, N).to(DEV)), w.to(DEV), dxa, ws)
+        dyb = torch.full((B, 1, 1, ldn), float("nan"), device=DEV)             # the padding of dy holds NaNs: nothing may read it
+        dyb[..., :N] = dy.view(B, 1, 1, N).to(DEV)
+        ops.dense_dgrad(ops.Act(dyb, 0, N), w.to(DEV), dxa, ws)
         torch.cuda.synchronize()
         cmp32(exact, dxa.base.view(B, ldx)[:, :K], dy.double() @ w.double(), 2e-6 * math.sqrt(N) + 1e-6, "dense dgrad")
         assert bool((dxa.base.view(B, ldx)[:, K:] == 7.0).all())
         again = ops.Act(torch.zeros((B, 1, 1, ldx), device=DEV), 0, K)
-        ops.dense_dgrad(ops.Act(dy.view(B, 1, 1, N).to(DEV)), w.to(DEV), again, ws)
+        ops.dense_dgrad(ops.Act(dyb, 0, N), w.to(DEV), again, ws)
         assert torch.equal(again.base[..., :K], dxa.base[..., :K])        # fixed-order reduction: bit-reproducible
 
 

@@ -148,7 +148,10 @@ def _check_given_indices(res, x, E, dy, Dv, r, what):
     return int((~unused).sum())
 
 
-CASES = [(3, 8, 8, 4, 4), (37, 24, 28, 8, 12), (90, 256, 256, 16, 256), (5, 128, 132, 64, 512), (1031, 16, 16, 16, 8)]
+CASES = [(3, 8, 8, 4, 4), (37, 24, 28, 8, 12), (90, 256, 256, 16, 256), (5, 128, 132, 64, 512), (1031, 16, 16, 16, 8),
+         (131200, 8, 8, 4, 4),          # 262 400 vectors want 1025 workgroups: the grid is capped at 1024 (a second trip of the grid-stride
+                                        # loop) and every combining thread adds four partials
+         (65600, 64, 68, 64, 8)]        # 257 workgroups; 1 049 600 float4 units: past the 4096-block cap of vq_bwd_dx
 
 
 @pytest.mark.parametrize("rows,C,ld,Dv,K", CASES)

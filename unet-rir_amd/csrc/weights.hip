@@ -105,10 +105,8 @@ __global__ __launch_bounds__(256) void cast_both_batched_kernel(const unetrir_ca
 
 __global__ __launch_bounds__(256) void cast_weights_batched_kernel(const unetrir_cast_desc* __restrict__ desc) {
     const unetrir_cast_desc d = desc[blockIdx.y];
-    if (!d.same || cast_fused_applies(d)) return;
-    __bf16* o = (__bf16*)d.same;
-    const size_t total = (size_t)d.N * d.T * d.Cp;
-    if (d.packed_s2 && d.T == 9 && (d.C & 15) == 0) {     // packed copy for conv3x3d where the fused kernel does not run
+    if (cast_fused_applies(d)) return;
+    if (d.packed_s2 && d.T == 9 && (d.C & 15) == 0) {     // packed copy for conv3x3d where the fused kernel does not run (with or without `same`)
         __bf16* pk = (__bf16*)d.packed_s2;
         const size_t tot = (size_t)d.N * 9 * d.C;
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < tot; i += (size_t)gridDim.x * 256) {
@@ -120,6 +118,9 @@ __global__ __launch_bounds__(256) void cast_weights_batched_kernel(const unetrir
             pk[po] = (__bf16)d.w[i];
         }
     }
+    if (!d.same) return;
+    __bf16* o = (__bf16*)d.same;
+    const size_t total = (size_t)d.N * d.T * d.Cp;
     if (d.C == d.Cp && (total & 7) == 0 && (((uintptr_t)d.w | (uintptr_t)o) & 15) == 0) {     // flat copy, 8 elements per thread
         const size_t n8 = total >> 3;
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
