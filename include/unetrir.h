@@ -338,6 +338,52 @@ int unetrir_conv2d_transpose_wgrad_partials_bf16(const unetrir_conv_geom* g, con
                                                  const unetrir_bf16* dy, int lddy, float* dw, float reg_coef, const float* w,
                                                  void* ws, size_t ws_bytes, unetrir_reduce_desc* desc, unetrir_stream_t stream);
 int unetrir_splitk_reduce_batched(const unetrir_reduce_desc* desc, int n, unetrir_stream_t stream);
+/* ---- The 2x2 stride-2 layers of AENet: Conv2D(k=2, strides=2, 'same') (dl_models/ae_net.py:273-279) and
+ *      Conv2DTranspose(k=2, strides=2, 'same') (dl_models/ae_net.py:301-307), bf16 storage (conv2x2.hip).  On even sizes the windows
+ *      do not overlap (TF 'same': pad_before 0, out = in / 2), so each pass is a GEMM with an index map: a gather-GEMM
+ *      (M = B H/2 W/2, K = 4 Cin, N = Cout: Conv2D forward, Conv2DTranspose data gradient), a scatter-GEMM (K = Cin, N = 4 Cout,
+ *      every output pixel written exactly once: Conv2DTranspose forward, Conv2D data gradient) and one weight-gradient launch for
+ *      the four taps.  These entry points are the only way to the kernels - unetrir_conv2d_* never choose them - and take the SAME
+ *      geometry, tensors, weight copies ([Cout][2][2][Cin] / [Cin][2][2][Cout], the orientation the corresponding unetrir_conv2d_*
+ *      entry point takes), addend rule, workspace and descriptor conventions as their unetrir_conv2d_* / unetrir_conv2d_transpose_*
+ *      twins, whose results they reproduce.
+ *      The kernels compute: k == 2, stride == 2, (Conv2D: H and W even), both channel counts powers of two in [16, 1024] with at
+ *      most 512 on the fine (larger) grid, ld >= channels and ld % 8 == 0, fewer than 2^31 fine pixels.
+ *      *_supported_bf16(g, ld_in, ld_out): the passes of the layer with input / output pixel strides ld_in / ld_out that the caller
+ *      should run here, as a mask of UNETRIR_C22_FWD | UNETRIR_C22_DGRAD | UNETRIR_C22_WGRAD: those the kernels compute AND
+ *      profiles/aenet.json measured as not slower than the unetrir_conv2d_* twin (the weight gradient: always; forward and data
+ *      gradient: up to K = 256, i.e. 4 x the fine-grid channels of a gather, the coarse-grid channels of a scatter).  The other
+ *      passes - 0: all of them - run on the unetrir_conv2d_* entry points.
+ *      UNETRIR_EINVAL before the device is touched: a geometry the kernels do not compute, a null required pointer, a pointer that
+ *      is not 16-byte aligned, reg_coef != 0 without w, a workspace smaller than *_wgrad_ws_bytes (unless one slab suffices and
+ *      reg_coef == 0: dw is then written directly), the _partials_ forms without a descriptor. */
+#define UNETRIR_C22_FWD 1
+#define UNETRIR_C22_DGRAD 2
+#define UNETRIR_C22_WGRAD 4
+int unetrir_conv2x2s2_supported_bf16(const unetrir_conv_geom* g, int ld_in, int ld_out);
+int unetrir_conv2x2s2_fwd_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* w, const float* bias,
+                               const unetrir_bf16* addend, int ldadd, unetrir_bf16* y, int ldy, unetrir_stream_t stream);
+int unetrir_conv2x2s2_dgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* wt,
+                                 const unetrir_bf16* addend, int ldadd, unetrir_bf16* dx, int lddx, unetrir_stream_t stream);
+size_t unetrir_conv2x2s2_wgrad_ws_bytes(const unetrir_conv_geom* g);
+int unetrir_conv2x2s2_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy,
+                                 float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_conv2x2s2_wgrad_partials_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy,
+                                          int lddy, float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
+                                          unetrir_reduce_desc* desc, unetrir_stream_t stream);
+int unetrir_conv2x2s2_transpose_supported_bf16(const unetrir_conv_geom* g, int ld_in, int ld_out);
+int unetrir_conv2x2s2_transpose_fwd_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* wt,
+                                         const float* bias, unetrir_bf16* y, int ldy, unetrir_stream_t stream);
+int unetrir_conv2x2s2_transpose_dgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* w,
+                                           const unetrir_bf16* addend, int ldadd, unetrir_bf16* dx, int lddx,
+                                           unetrir_stream_t stream);
+size_t unetrir_conv2x2s2_transpose_wgrad_ws_bytes(const unetrir_conv_geom* g);
+int unetrir_conv2x2s2_transpose_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy,
+                                           int lddy, float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
+                                           unetrir_stream_t stream);
+int unetrir_conv2x2s2_transpose_wgrad_partials_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx,
+                                                    const unetrir_bf16* dy, int lddy, float* dw, float reg_coef, const float* w,
+                                                    void* ws, size_t ws_bytes, unetrir_reduce_desc* desc, unetrir_stream_t stream);
 /* The stride-2 3x3 forward kernel (conv3x3d.hip: strided Conv2D forward, Conv2DTranspose data gradient) streams its kernel
  * 16 input channels at a time; from the [N][9][C] copy that is a gather of 32-byte pieces.  A PACKED copy holds the same values
  * in the order the kernel's LDS-DMA reads them - [N / 128][C / 16][9 taps][4 blocks of 32 channels][64 lanes][8 values], lane =
@@ -460,6 +506,20 @@ int unetrir_sigmoid_loss_ex_bf16(const float* logits, int ldl, const float* targ
                                  unetrir_bf16* dlogits, float* loss_out, void* ws, size_t ws_bytes, unetrir_stream_t stream);
 int unetrir_sigmoid_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits,
                              unetrir_stream_t stream);
+/* The clipped-ReLU output of AENet, `tf.keras.activations.relu(out, alpha=0.0, max_value=1)` (dl_models/ae_net.py:249), in place of
+ * the sigmoid: pred = min(max(logit, 0), 1); dL/dlogit = dL/dpred where 0 < logit < 1, else 0 (the stored prediction tells it:
+ * 0 < pred < 1).  unetrir_relu1_loss_ex_*: arguments, loss_out layout, phase_ref / phase_weight, alpha, inv_norm, workspace and the
+ * fixed-order sums of unetrir_sigmoid_loss_ex_*; unetrir_relu1_nchw_f32: inference, as unetrir_sigmoid_nchw_f32; unetrir_relu1_bwd_*:
+ * the autograd bridge, as unetrir_sigmoid_bwd_*. */
+int unetrir_relu1_loss_ex_f32(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                              int B, int H, int W, float alpha, float inv_norm, float* pred, float* dlogits, float* loss_out,
+                              void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_relu1_loss_ex_bf16(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                               int B, int H, int W, float alpha, float inv_norm, float* pred, unetrir_bf16* dlogits, float* loss_out,
+                               void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_relu1_nchw_f32(const float* logits, int ldl, int B, int H, int W, float* pred, unetrir_stream_t stream);
+int unetrir_relu1_bwd_f32(const float* pred, const float* dpred, int B, int H, int W, float* dlogits, unetrir_stream_t stream);
+int unetrir_relu1_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits, unetrir_stream_t stream);
 /* glue between the bf16 trunk and the fp32 information-vector branch: y = a + b (Add(), dl_models/u_net.py:229);
  * fp32 copy of a bf16 gradient.  n is a multiple of 4. */
 int unetrir_add_f32_to_bf16(const unetrir_bf16* a, const float* b, unetrir_bf16* y, long long n,

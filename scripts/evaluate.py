@@ -32,7 +32,7 @@ from unet_rir_amd.features import PostProcess
 
 
 def build_model(a, dev):
-    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder, "vae": U.VAE, "vqvae": U.VQVAE}[a.arch]
+    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder, "vae": U.VAE, "vqvae": U.VQVAE, "aenet": U.AENet}[a.arch]
     if a.load:
         return cls.load(a.load, batch_size=a.batch, device=dev)
     if a.arch in ("vae", "vqvae"):
@@ -51,10 +51,13 @@ def build_model(a, dev):
             mgr.restore()
             print("restored", mgr.latest_checkpoint)
         return m
-    if a.arch != "unet":
-        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net, a VAE or a VQ-VAE; use --load for the other autoencoders")
-    m = U.UNet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, kernels=a.kernels, batch_size=a.batch, device=dev,
-               dropout=False)
+    if a.arch not in ("unet", "aenet"):
+        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net, an AENet, a VAE or a VQ-VAE; use --load for the other autoencoders")
+    if a.arch == "aenet":
+        m = U.AENet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, batch_size=a.batch, device=dev, dropout=False)
+    else:
+        m = U.UNet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, kernels=a.kernels, batch_size=a.batch, device=dev,
+                   dropout=False)
     if a.checkpoint:
         mgr = U.CheckpointManager(U.Trainer(m.engine, dropout=False), a.checkpoint)
         if mgr.latest_checkpoint is None:
@@ -97,7 +100,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--load")
     ap.add_argument("--checkpoint")
-    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae", "vqvae"), default="unet")
+    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae", "vqvae", "aenet"), default="unet")
     ap.add_argument("--latent", type=int, default=32, help="latent_space_dim of --arch vae built without --load")
     ap.add_argument("--filters", type=int, default=32)
     ap.add_argument("--kernels", type=int, default=3)

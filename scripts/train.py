@@ -35,6 +35,8 @@ def build_model(a, dev):
     if a.name == "vqvae":      # main_training.py does not build it: the model of dl_models/vqvae.py's own __main__ block (:522-531)
         return U.VQVAE(shape, (2, 16), conv_filters=(32, 64, 128, 256), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
                        latent_space_dim=16, n_neurons=320, name=a.name, **common)
+    if a.name == "aenet":      # dl_models/ae_net.py with its defaults (rir_generation.py:6 imports it; main_training.py has no branch)
+        return U.AENet(shape, (2, 16), number_filters_0=a.filters, name="AENet", **common)
     return U.UNet(shape, (2, 16), mode=0, number_filters_0=a.filters, kernels=a.kernels, name="U-Net", **common)
 
 
@@ -47,7 +49,7 @@ def main():
     ap.add_argument("--arrays", nargs="+", default=["PlanarMicrophoneArray", "CircularMicrophoneArray"])
     ap.add_argument("--no-debug", action="store_true", help="load the whole tree (main_training.py runs with debug = True)")
     ap.add_argument("--extract", action="store_true", help="unpack the zone archives first")
-    ap.add_argument("--name", choices=("ae", "resae", "vae", "vqvae", "unet"), default="unet")
+    ap.add_argument("--name", choices=("ae", "resae", "vae", "vqvae", "aenet", "unet"), default="unet")
     ap.add_argument("--filters", type=int, default=32, help="number_filters_0 of the U-Net")
     ap.add_argument("--kernels", type=int, default=3)
     ap.add_argument("--height", type=int, default=144)

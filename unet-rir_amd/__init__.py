@@ -8,7 +8,8 @@ from ._lib import UnetrirError  # noqa: F401
 from .engine import UNetEngine  # noqa: F401
 from .device import HipRuntime  # noqa: F401
 from .ae import AutoencoderEngine  # noqa: F401
-from .model import VAE, VQVAE, Autoencoder, ResAE, UNet  # noqa: F401
+from .aenet import AENetEngine  # noqa: F401
+from .model import VAE, VQVAE, AENet, Autoencoder, ResAE, UNet  # noqa: F401
 from .resae import ResAEEngine  # noqa: F401
 from .unet_graph import UNetGraphEngine  # noqa: F401
 from .vae import VAEEngine  # noqa: F401
@@ -18,4 +19,4 @@ from .evaluate import Evaluator, score, write_report  # noqa: F401
 from .dataset import DataGenerator, Dataset, read_wav  # noqa: F401
 from .trainer import CheckpointManager, GradBucketer, Trainer, fit, lr_schedule  # noqa: F401
 
-__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "HipRuntime", "Trainer", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "write_report", "Dataset", "DataGenerator", "read_wav"]
+__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "HipRuntime", "Trainer", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "write_report", "Dataset", "DataGenerator", "read_wav"]

@@ -118,6 +118,25 @@ _SIGS = {
     "unetrir_splitk_reduce_batched": (C.c_int, [C.POINTER(ReduceDesc), C.c_int, c_stream]),
     "unetrir_conv2d_transpose_wgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p,
                                                       C.c_float, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    # the 2x2 stride-2 layers (conv2x2.hip): the argument lists of their unetrir_conv2d_* twins
+    "unetrir_conv2x2s2_supported_bf16": (C.c_int, [C.POINTER(ConvGeom), C.c_int, C.c_int]),
+    "unetrir_conv2x2s2_transpose_supported_bf16": (C.c_int, [C.POINTER(ConvGeom), C.c_int, C.c_int]),
+    "unetrir_conv2x2s2_fwd_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int,
+                                             c_stream]),
+    "unetrir_conv2x2s2_dgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_conv2x2s2_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
+    "unetrir_conv2x2s2_wgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float, c_f32p,
+                                               C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_conv2x2s2_wgrad_partials_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float, c_f32p,
+                                                        C.c_void_p, C.c_size_t, C.POINTER(ReduceDesc), c_stream]),
+    "unetrir_conv2x2s2_transpose_fwd_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_stream]),
+    "unetrir_conv2x2s2_transpose_dgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int,
+                                                         c_stream]),
+    "unetrir_conv2x2s2_transpose_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
+    "unetrir_conv2x2s2_transpose_wgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float, c_f32p,
+                                                         C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_conv2x2s2_transpose_wgrad_partials_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float,
+                                                                  c_f32p, C.c_void_p, C.c_size_t, C.POINTER(ReduceDesc), c_stream]),
     "unetrir_cast_weight_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "unetrir_transpose_cast_weight_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "unetrir_bn_stats_bf16": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_float, C.c_float,
@@ -187,6 +206,13 @@ _SIGS = {
                                               c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "unetrir_sigmoid_loss_ex_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                                c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_relu1_loss_ex_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                            c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_relu1_loss_ex_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                             c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_relu1_nchw_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
+    "unetrir_relu1_bwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
+    "unetrir_relu1_bwd_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
     "unetrir_sgd_f32": (C.c_int, [c_f32p, c_f32p, C.c_longlong, C.c_float, C.c_float, c_stream]),
     "unetrir_nadam_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     C.c_float, C.c_float, C.c_float, c_stream]),

@@ -599,11 +599,155 @@ int run_wgrad(const unetrir_conv_geom* gin, bool transposed, const void* x, int 
     return 0;
 }
 
+// ---- the 2x2 stride-2 layers on even sizes (conv2x2.hip): entry points of their own, never chosen by plan_conv / plan_wgrad.
+// A layer as the kernels see it: a coarse grid B x PH x PW and a fine grid of twice the size; Conv2D(2, strides=2) maps fine ->
+// coarse (H, W of the geometry = the fine grid, which must be even), Conv2DTranspose(2, strides=2) coarse -> fine (H, W = the
+// coarse grid).
+struct C22Layer { int B, PH, PW, Cfine, Ccoarse; };
+inline bool c22_layer(const unetrir_conv_geom* g, bool transposed, C22Layer* l) {
+    if (!geom_ok(g) || g->k != 2 || g->stride != 2) return false;
+    if (!transposed && ((g->H | g->W) & 1)) return false;
+    *l = transposed ? C22Layer{g->B, g->H, g->W, g->Cout, g->Cin} : C22Layer{g->B, g->H / 2, g->W / 2, g->Cin, g->Cout};
+    return l->Cfine <= 512;           // the gather form keeps 32 kernel rows of 4 Cfine values in LDS
+}
+inline double c22_flops(const C22Layer& l) { return 2.0 * l.B * l.PH * l.PW * 4.0 * l.Cfine * l.Ccoarse; }
+
+// gather: fine -> coarse (Conv2D forward, Conv2DTranspose data gradient); scatter: coarse -> fine (the other two)
+int run_c22_gemm(const unetrir_conv_geom* g, bool transposed, bool scatter, int fam, const void* in, int ldi, const void* w,
+                 const float* bias, const void* addend, int ldadd, void* out, int ldo, hipStream_t s) {
+    C22Layer l;
+    if (!c22_layer(g, transposed, &l) || !in || !w || !out) return UNETRIR_EINVAL;
+    C22Args a{};
+    a.in = (const __bf16*)in; a.ldi = ldi; a.w = (const __bf16*)w; a.bias = bias; a.addend = (const __bf16*)addend; a.ldadd = ldadd;
+    a.out = (__bf16*)out; a.ldo = ldo; a.B = l.B; a.PH = l.PH; a.PW = l.PW;
+    a.C = scatter ? l.Ccoarse : l.Cfine; a.N = scatter ? l.Cfine : l.Ccoarse;
+    if (!conv2x2s2_gemm_applies(a, scatter)) return UNETRIR_EINVAL;
+    ProfScope ps(fam, c22_flops(l), s);
+    return launch_conv2x2s2_gemm_bf16(a, scatter, s);
+}
+
+C22WgradArgs c22_wgrad_args(const C22Layer& l, const void* coarse, int ldc, const void* fine, int ldf) {
+    C22WgradArgs a{};
+    a.small = (const __bf16*)coarse; a.lds = ldc; a.S = l.Ccoarse; a.large = (const __bf16*)fine; a.ldl = ldf; a.L = l.Cfine;
+    a.B = l.B; a.PH = l.PH; a.PW = l.PW;
+    return a;
+}
+
+size_t c22_wgrad_ws_bytes(const unetrir_conv_geom* g, bool transposed) {
+    C22Layer l;
+    if (!c22_layer(g, transposed, &l)) return 0;
+    if (!conv2x2s2_wgrad_applies(c22_wgrad_args(l, nullptr, l.Ccoarse, nullptr, l.Cfine))) return 0;
+    int nslabs; long long per;
+    conv2x2s2_wgrad_plan(l.B, l.PH, l.PW, l.Ccoarse, l.Cfine, &nslabs, &per);
+    return (size_t)nslabs * l.Ccoarse * 4 * l.Cfine * sizeof(float);
+}
+
+// dw in the layer's primary layout [coarse channel][2][2][fine channel] (Conv2D: [Cout][2][2][Cin]; Conv2DTranspose:
+// [Cin][2][2][Cout]) = sum over pixels + reg * w; slabs, direct write and the deferred reduction as run_wgrad has them.
+int run_c22_wgrad(const unetrir_conv_geom* g, bool transposed, const void* x, int ldx, const void* dy, int lddy, float* dw, float reg,
+                  const float* w, void* ws, size_t ws_bytes, unetrir_reduce_desc* defer, hipStream_t s) {
+    if (defer) *defer = unetrir_reduce_desc{};
+    C22Layer l;
+    if (!c22_layer(g, transposed, &l) || !x || !dy || !dw || (reg != 0.f && !w)) return UNETRIR_EINVAL;
+    C22WgradArgs a = transposed ? c22_wgrad_args(l, x, ldx, dy, lddy) : c22_wgrad_args(l, dy, lddy, x, ldx);
+    if (!conv2x2s2_wgrad_applies(a)) return UNETRIR_EINVAL;
+    int nslabs;
+    conv2x2s2_wgrad_plan(l.B, l.PH, l.PW, l.Ccoarse, l.Cfine, &nslabs, &a.blocks_per_split);
+    const size_t nout = (size_t)l.Ccoarse * 4 * l.Cfine;
+    const bool direct = nslabs == 1 && reg == 0.f;
+    if (!direct && (!ws || ws_bytes < (size_t)nslabs * nout * sizeof(float))) return UNETRIR_EINVAL;
+    a.part = direct ? dw : (float*)ws;
+    ProfScope ps(UNETRIR_FAM_CONV_WGRAD, c22_flops(l), s);
+    const int err = launch_conv2x2s2_wgrad_bf16(a, nslabs, s);
+    if (err || direct) return err;
+    if (!defer) return launch_splitk_reduce(a.part, nslabs, nout, dw, reg, w, s);
+    *defer = unetrir_reduce_desc{a.part, nslabs, nout, dw, reg, w};
+    return 0;
+}
+
+// Which passes of the layer the caller should run on these kernels: UNETRIR_C22_FWD | _DGRAD | _WGRAD (ld_fine / ld_coarse: pixel
+// strides of the tensors on the two grids).  A pass is offered where the kernel computes it AND the record (profiles/aenet.json: the
+// default AENet at 144 x 160, batch 32, both variants alternating in one process) shows it not slower than the generic entry point:
+// the weight gradient everywhere (2.06 - 2.58 x), the GEMM forms up to K = 256 (1.07 - 2.01 x; at K = 512 and 1024 a 32 ... 128
+// channel tile re-reads the pixels N / tile times through L2 and the tap-table kernel's 128-pixel tiles win: 0.70 - 0.86 x).
+// The rule is GENERALISED from those eight layer shapes (batch 32, number_filters_0 = 32, channels 32 ... 512): the shapes of
+// number_filters_0 = 16 and 64 (16 and 1024 channels) and small batches were not timed, yet the predicate decides for them too.
+constexpr int C22_GEMM_MAX_K = 256;
+int c22_supported(const unetrir_conv_geom* g, bool transposed, int ld_fine, int ld_coarse) {
+    C22Layer l;
+    if (!c22_layer(g, transposed, &l)) return 0;
+    C22Args ga{}, sc{};
+    ga.B = sc.B = l.B; ga.PH = sc.PH = l.PH; ga.PW = sc.PW = l.PW;
+    ga.C = l.Cfine; ga.N = l.Ccoarse; ga.ldi = ld_fine; ga.ldo = ld_coarse;
+    sc.C = l.Ccoarse; sc.N = l.Cfine; sc.ldi = ld_coarse; sc.ldo = ld_fine;
+    const bool gather = conv2x2s2_gemm_applies(ga, false) && 4 * ga.C <= C22_GEMM_MAX_K;
+    const bool scatter = conv2x2s2_gemm_applies(sc, true) && sc.C <= C22_GEMM_MAX_K;
+    int mask = conv2x2s2_wgrad_applies(c22_wgrad_args(l, nullptr, ld_coarse, nullptr, ld_fine)) ? UNETRIR_C22_WGRAD : 0;
+    if (transposed ? scatter : gather) mask |= UNETRIR_C22_FWD;
+    if (transposed ? gather : scatter) mask |= UNETRIR_C22_DGRAD;
+    return mask;
+}
+
 }  // namespace
 
 extern "C" {
 
 int unetrir_abi_version(void) { return UNETRIR_ABI_VERSION; }
+
+int unetrir_conv2x2s2_supported_bf16(const unetrir_conv_geom* g, int ld_in, int ld_out) { return c22_supported(g, false, ld_in, ld_out); }
+int unetrir_conv2x2s2_transpose_supported_bf16(const unetrir_conv_geom* g, int ld_in, int ld_out) {
+    return c22_supported(g, true, ld_out, ld_in);
+}
+
+int unetrir_conv2x2s2_fwd_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* w, const float* bias,
+                               const unetrir_bf16* addend, int ldadd, unetrir_bf16* y, int ldy, unetrir_stream_t stream) {
+    return run_c22_gemm(g, false, false, UNETRIR_FAM_CONV_FWD, x, ldx, w, bias, addend, ldadd, y, ldy, (hipStream_t)stream);
+}
+
+int unetrir_conv2x2s2_dgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* wt,
+                                 const unetrir_bf16* addend, int ldadd, unetrir_bf16* dx, int lddx, unetrir_stream_t stream) {
+    return run_c22_gemm(g, false, true, UNETRIR_FAM_CONV_DGRAD, dy, lddy, wt, nullptr, addend, ldadd, dx, lddx, (hipStream_t)stream);
+}
+
+size_t unetrir_conv2x2s2_wgrad_ws_bytes(const unetrir_conv_geom* g) { return c22_wgrad_ws_bytes(g, false); }
+
+int unetrir_conv2x2s2_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy, float* dw,
+                                 float reg_coef, const float* w, void* ws, size_t ws_bytes, unetrir_stream_t stream) {
+    return run_c22_wgrad(g, false, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, nullptr, (hipStream_t)stream);
+}
+
+int unetrir_conv2x2s2_wgrad_partials_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy,
+                                          float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
+                                          unetrir_reduce_desc* desc, unetrir_stream_t stream) {
+    if (!desc) return UNETRIR_EINVAL;
+    return run_c22_wgrad(g, false, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, desc, (hipStream_t)stream);
+}
+
+int unetrir_conv2x2s2_transpose_fwd_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* wt,
+                                         const float* bias, unetrir_bf16* y, int ldy, unetrir_stream_t stream) {
+    return run_c22_gemm(g, true, true, UNETRIR_FAM_CONV_FWD, x, ldx, wt, bias, nullptr, 0, y, ldy, (hipStream_t)stream);
+}
+
+int unetrir_conv2x2s2_transpose_dgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* dy, int lddy, const unetrir_bf16* w,
+                                           const unetrir_bf16* addend, int ldadd, unetrir_bf16* dx, int lddx,
+                                           unetrir_stream_t stream) {
+    return run_c22_gemm(g, true, false, UNETRIR_FAM_CONV_DGRAD, dy, lddy, w, nullptr, addend, ldadd, dx, lddx, (hipStream_t)stream);
+}
+
+size_t unetrir_conv2x2s2_transpose_wgrad_ws_bytes(const unetrir_conv_geom* g) { return c22_wgrad_ws_bytes(g, true); }
+
+int unetrir_conv2x2s2_transpose_wgrad_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy,
+                                           float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
+                                           unetrir_stream_t stream) {
+    return run_c22_wgrad(g, true, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, nullptr, (hipStream_t)stream);
+}
+
+int unetrir_conv2x2s2_transpose_wgrad_partials_bf16(const unetrir_conv_geom* g, const unetrir_bf16* x, int ldx, const unetrir_bf16* dy,
+                                                    int lddy, float* dw, float reg_coef, const float* w, void* ws, size_t ws_bytes,
+                                                    unetrir_reduce_desc* desc, unetrir_stream_t stream) {
+    if (!desc) return UNETRIR_EINVAL;
+    return run_c22_wgrad(g, true, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, desc, (hipStream_t)stream);
+}
 
 int unetrir_conv2d_fwd_f32(const unetrir_conv_geom* g, const float* x, int ldx, const float* w, const float* bias,
                            const float* addend, int ldadd, float* y, int ldy, unetrir_stream_t stream) {

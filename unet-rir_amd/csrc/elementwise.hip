@@ -456,11 +456,17 @@ __global__ void nchw_to_nhwc_pad_kernel(const float* __restrict__ x, int B, int 
 // sigmoid + amplitude/phase loss (main_training.py:184-235) + dL/dlogits, one thread per pixel
 // -------------------------------------------------------------------------------------------
 __device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
+// The output activation of the loss / inference / bridge kernels below.  ACT 0: sigmoid (dl_models/u_net.py:249).  ACT 1: the clipped
+// ReLU relu(out, max_value=1) of dl_models/ae_net.py:249: pred = min(max(z, 0), 1), d pred / d z = 1 where 0 < z < 1, else 0 - which
+// the stored prediction tells as well (0 < pred < 1), so the bridge kernel needs no logits.
+template <int ACT> __device__ __forceinline__ float out_act(float z) { return ACT ? fminf(fmaxf(z, 0.f), 1.f) : sigmoidf_(z); }
+// g * d pred / d logit, the sigmoid's product in the order it always had: (g * p) * (1 - p)
+template <int ACT> __device__ __forceinline__ float out_dact(float g, float p) { return ACT ? ((p > 0.f && p < 1.f) ? g : 0.f) : g * p * (1.f - p); }
 
 // phase_ref (nullable): the network INPUT, NCHW - the `diff_loss` switch of main_training.py:214-217 (phase target = phase_true -
 // phase_x).  phase_w (nullable): [W] column weights of the phase term - the `sigmoid_loss` switch (:221-222, preprocess.py:116-121).
 // part: three doubles per block (amplitude sum, phase sum as the metrics see it, phase sum as the loss sees it = weighted).
-template <typename T>
+template <typename T, int ACT>
 __global__ __launch_bounds__(256) void sigmoid_loss_kernel(const float* __restrict__ logits, int ldl,
                                                            const float* __restrict__ target, int B, int H, int W,
                                                            float alpha, float inv_norm, float* __restrict__ pred,
@@ -473,7 +479,7 @@ __global__ __launch_bounds__(256) void sigmoid_loss_kernel(const float* __restri
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
         const long long b = i / hw, r = i - b * hw;
-        const float p0 = sigmoidf_(logits[i * ldl + 0]), p1 = sigmoidf_(logits[i * ldl + 1]);
+        const float p0 = out_act<ACT>(logits[i * ldl + 0]), p1 = out_act<ACT>(logits[i * ldl + 1]);
         pred[(b * 2 + 0) * hw + r] = p0;
         pred[(b * 2 + 1) * hw + r] = p1;
         if (target) {
@@ -491,7 +497,7 @@ __global__ __launch_bounds__(256) void sigmoid_loss_kernel(const float* __restri
             spw += (double)(eph * wgt);
             const float g0 = -2.f * da * alpha * inv_norm;
             const float g1 = -(1.f - alpha) * inv_norm * TWO_PI * sinf(ph) * wgt;
-            st4(dlogits + i * ldd, make_float4(g0 * p0 * (1.f - p0), g1 * p1 * (1.f - p1), 0.f, 0.f));
+            st4(dlogits + i * ldd, make_float4(out_dact<ACT>(g0, p0), out_dact<ACT>(g1, p1), 0.f, 0.f));
             if (ldd > 4) st4(dlogits + i * ldd + 4, make_float4(0.f, 0.f, 0.f, 0.f));
         }
     }
@@ -524,18 +530,19 @@ __global__ void loss_finalize_kernel(const double* __restrict__ part, int nblk, 
     out[2] = (float)sp;
 }
 
+template <int ACT>
 __global__ void sigmoid_only_kernel(const float* __restrict__ logits, int ldl, int B, int H, int W,
                                     float* __restrict__ pred) {
     const long long hw = (long long)H * W, total = (long long)B * hw;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
         const long long b = i / hw, r = i - b * hw;
-        pred[(b * 2 + 0) * hw + r] = sigmoidf_(logits[i * ldl + 0]);
-        pred[(b * 2 + 1) * hw + r] = sigmoidf_(logits[i * ldl + 1]);
+        pred[(b * 2 + 0) * hw + r] = out_act<ACT>(logits[i * ldl + 0]);
+        pred[(b * 2 + 1) * hw + r] = out_act<ACT>(logits[i * ldl + 1]);
     }
 }
 
-template <typename T>
+template <typename T, int ACT>
 __global__ void sigmoid_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ dpred, int B, int H,
                                    int W, T* __restrict__ dlogits, int ldd) {
     const long long hw = (long long)H * W, total = (long long)B * hw;
@@ -544,7 +551,7 @@ __global__ void sigmoid_bwd_kernel(const float* __restrict__ pred, const float* 
         const long long b = i / hw, r = i - b * hw;
         const float p0 = pred[(b * 2 + 0) * hw + r], p1 = pred[(b * 2 + 1) * hw + r];
         const float g0 = dpred[(b * 2 + 0) * hw + r], g1 = dpred[(b * 2 + 1) * hw + r];
-        st4(dlogits + i * ldd, make_float4(g0 * p0 * (1.f - p0), g1 * p1 * (1.f - p1), 0.f, 0.f));
+        st4(dlogits + i * ldd, make_float4(out_dact<ACT>(g0, p0), out_dact<ACT>(g1, p1), 0.f, 0.f));
         if (ldd > 4) st4(dlogits + i * ldd + 4, make_float4(0.f, 0.f, 0.f, 0.f));
     }
 }
@@ -822,7 +829,7 @@ int relu_bwd_impl(const T* da, int ldda, const T* x, int ldx, long long P, int C
 }
 
 #define LOSS_BLOCKS 1024
-template <typename T>
+template <typename T, int ACT = 0>
 int sigmoid_loss_impl(const float* logits, int ldl, const float* target, int B, int H, int W, float alpha, float inv_norm,
                       float* pred, T* dlogits, int ldd, float* loss_out, void* ws, size_t ws_bytes, hipStream_t s,
                       const float* phase_ref = nullptr, const float* phase_w = nullptr) {
@@ -830,7 +837,7 @@ int sigmoid_loss_impl(const float* logits, int ldl, const float* target, int B, 
         B <= 0 || H <= 0 || W <= 0 || (ldd != 4 && ldd != 8))
         return UNETRIR_EINVAL;
     const unsigned nb = grid_for((long long)B * H * W, 256, LOSS_BLOCKS);
-    hipLaunchKernelGGL(sigmoid_loss_kernel<T>, dim3(nb), dim3(256), 0, s, logits, ldl, target, B, H, W, alpha, inv_norm, pred,
+    hipLaunchKernelGGL((sigmoid_loss_kernel<T, ACT>), dim3(nb), dim3(256), 0, s, logits, ldl, target, B, H, W, alpha, inv_norm, pred,
                        dlogits, ldd, (double*)ws, phase_ref, phase_w);
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, (int)nb, alpha, inv_norm, loss_out);
     return (int)hipGetLastError();
@@ -920,7 +927,7 @@ int unetrir_sigmoid_loss_ex_f32(const float* logits, int ldl, const float* targe
 
 int unetrir_sigmoid_nchw_f32(const float* logits, int ldl, int B, int H, int W, float* pred, unetrir_stream_t stream) {
     if (!logits || ldl < 2 || !pred || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
-    hipLaunchKernelGGL(sigmoid_only_kernel, dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, logits,
+    hipLaunchKernelGGL(sigmoid_only_kernel<0>, dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, logits,
                        ldl, B, H, W, pred);
     return (int)hipGetLastError();
 }
@@ -928,7 +935,7 @@ int unetrir_sigmoid_nchw_f32(const float* logits, int ldl, int B, int H, int W, 
 int unetrir_sigmoid_bwd_f32(const float* pred, const float* dpred, int B, int H, int W, float* dlogits,
                             unetrir_stream_t stream) {
     if (!pred || !dpred || !dlogits || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
-    hipLaunchKernelGGL(sigmoid_bwd_kernel<float>, dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
+    hipLaunchKernelGGL((sigmoid_bwd_kernel<float, 0>), dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
                        dpred, B, H, W, dlogits, 4);
     return (int)hipGetLastError();
 }
@@ -1145,7 +1152,43 @@ int unetrir_sigmoid_loss_ex_bf16(const float* logits, int ldl, const float* targ
 int unetrir_sigmoid_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits,
                              unetrir_stream_t stream) {
     if (!pred || !dpred || !dlogits || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
-    hipLaunchKernelGGL(sigmoid_bwd_kernel<__bf16>, dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
+    hipLaunchKernelGGL((sigmoid_bwd_kernel<__bf16, 0>), dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
+                       dpred, B, H, W, (__bf16*)dlogits, 8);
+    return (int)hipGetLastError();
+}
+
+/* the clipped-ReLU output relu(out, max_value=1) of dl_models/ae_net.py:249: the three kernels above with ACT = 1 */
+int unetrir_relu1_loss_ex_f32(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                              int B, int H, int W, float alpha, float inv_norm, float* pred, float* dlogits, float* loss_out,
+                              void* ws, size_t ws_bytes, unetrir_stream_t stream) {
+    return sigmoid_loss_impl<float, 1>(logits, ldl, target, B, H, W, alpha, inv_norm, pred, dlogits, 4, loss_out, ws, ws_bytes,
+                                       (hipStream_t)stream, phase_ref, phase_weight);
+}
+
+int unetrir_relu1_loss_ex_bf16(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                               int B, int H, int W, float alpha, float inv_norm, float* pred, unetrir_bf16* dlogits, float* loss_out,
+                               void* ws, size_t ws_bytes, unetrir_stream_t stream) {
+    return sigmoid_loss_impl<__bf16, 1>(logits, ldl, target, B, H, W, alpha, inv_norm, pred, (__bf16*)dlogits, 8, loss_out, ws, ws_bytes,
+                                        (hipStream_t)stream, phase_ref, phase_weight);
+}
+
+int unetrir_relu1_nchw_f32(const float* logits, int ldl, int B, int H, int W, float* pred, unetrir_stream_t stream) {
+    if (!logits || ldl < 2 || !pred || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL(sigmoid_only_kernel<1>, dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, logits,
+                       ldl, B, H, W, pred);
+    return (int)hipGetLastError();
+}
+
+int unetrir_relu1_bwd_f32(const float* pred, const float* dpred, int B, int H, int W, float* dlogits, unetrir_stream_t stream) {
+    if (!pred || !dpred || !dlogits || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL((sigmoid_bwd_kernel<float, 1>), dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
+                       dpred, B, H, W, dlogits, 4);
+    return (int)hipGetLastError();
+}
+
+int unetrir_relu1_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits, unetrir_stream_t stream) {
+    if (!pred || !dpred || !dlogits || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL((sigmoid_bwd_kernel<__bf16, 1>), dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
                        dpred, B, H, W, (__bf16*)dlogits, 8);
     return (int)hipGetLastError();
 }

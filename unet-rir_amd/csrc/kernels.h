@@ -215,6 +215,33 @@ bool pw1x1_applies(const PwArgs& a);
 long long pw1x1_colstat_rows(const PwArgs& a);
 int launch_pw1x1_bf16(const PwArgs& a, hipStream_t s);   // H, W = coarse (input) grid; output 2H x 2W
 
+// 2x2 stride-2 layers on even sizes (conv2x2.hip).  The iteration grid is the COARSE grid B x PH x PW, the fine grid is
+// B x 2 PH x 2 PW; tap t = 2 kh + kw.  Gather form: out[coarse p][n] = sum_t sum_c in[fine(p, t)][c] w[n][t][c] + bias[n]
+// (+ addend); scatter form: out[fine(p, t)][n] = sum_c in[coarse p][c] w[n][t][c] + bias[n] (+ addend).
+struct C22Args {
+    const __bf16* in; int ldi;
+    const __bf16* w;                 // [N][4][C], C contiguous
+    const float* bias;               // nullable
+    const __bf16* addend; int ldadd; // nullable; indexed like out (may be out itself)
+    __bf16* out; int ldo;
+    int B, PH, PW;
+    int C, N;
+    int cshift;                      // log2(C): filled by the launcher
+};
+bool conv2x2s2_gemm_applies(const C22Args& a, bool scatter);
+int launch_conv2x2s2_gemm_bf16(C22Args a, bool scatter, hipStream_t s);
+// weight gradient: part[slab][S][4][L] = sum over the slab's coarse pixels p of small[p][s] * large[fine(p, t)][l]
+struct C22WgradArgs {
+    const __bf16* small; int lds; int S;      // the coarse-grid tensor [B,PH,PW,S]
+    const __bf16* large; int ldl; int L;      // the fine-grid tensor [B,2PH,2PW,L]
+    int B, PH, PW;
+    float* part;
+    long long blocks_per_split;               // 32-pixel K blocks per slab
+};
+bool conv2x2s2_wgrad_applies(const C22WgradArgs& a);
+void conv2x2s2_wgrad_plan(int B, int PH, int PW, int S, int L, int* nslabs, long long* blocks_per_split);
+int launch_conv2x2s2_wgrad_bf16(const C22WgradArgs& a, int nslabs, hipStream_t s);
+
 // splitmix64 finaliser: the hash of the counter-based generators - dropout_mask_kernel (elementwise.hip) and normal_kernel (vae.hip,
 // which also holds the sampling / KL kernels of the variational autoencoder; their entry points are in include/unetrir.h)
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {

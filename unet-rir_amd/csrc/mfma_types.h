@@ -37,3 +37,12 @@ __device__ __forceinline__ void mma4(f32x16& acc, const uint4& a, const uint4& b
 __device__ __forceinline__ void mma4(f32x16& acc, const uint4& a, const uint4& b, __bf16) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), acc, 0, 0, 0);
 }
+
+// two fp32 values rounded to bf16 (nearest even) in one 32-bit word, and the halves of such a word as fp32 (pw1x1.hip, conv2x2.hip:
+// the register epilogues that store 16 consecutive channels of a pixel)
+__device__ __forceinline__ unsigned pack2(float a, float b) {
+    const __bf16 x = (__bf16)a, y = (__bf16)b;
+    return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
+}
+__device__ __forceinline__ float lo16(unsigned v) { return __builtin_bit_cast(float, v << 16); }
+__device__ __forceinline__ float hi16(unsigned v) { return __builtin_bit_cast(float, v & 0xffff0000u); }

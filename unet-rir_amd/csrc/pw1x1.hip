@@ -25,13 +25,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const __bf16 x = (__bf16)a, y = (__bf16)b;
-    return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
-__device__ __forceinline__ float lo16(unsigned v) { return __builtin_bit_cast(float, v << 16); }
-__device__ __forceinline__ float hi16(unsigned v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
-
 // row-of-16 total in every lane of the row (DPP row rotations: full-rate VALU, no LDS)
 __device__ __forceinline__ float row16_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));   // row_ror:8

@@ -80,6 +80,7 @@ class DeviceCounters:
     once into a HIP graph and replayed (trainer.Trainer(graph=True)).  The host mirrors (`adam_t`, `dropout_step`) are kept in
     step either way; checkpoints hold the host values."""
     n_dropout_draws = 1          # dropout masks drawn per step
+    dropout_p = DROPOUT_P        # rate of the engine's Dropout layers (aenet.AENetEngine: Dropout(.5), dl_models/ae_net.py:258, :267)
     n_noise_draws = 0            # draws of the same counter made in every forward pass, with or without Dropout (vae.VAEEngine: eps)
     # compute_loss switches (main_training.py:38-39, :214-222); set through trainer.Trainer(sigmoid_loss=, diff_loss=, beta=)
     loss_diff = False            # diff_loss: the phase target is phase_true - phase of the network input
@@ -144,9 +145,9 @@ class DeviceCounters:
         """Fill `buf` with the next keep mask of this engine's dropout stream."""
         dev = self._dev()
         if dev is None:
-            ops.dropout_mask(buf, DROPOUT_P, self.dropout_seed, self._shared["dropout_step"])
+            ops.dropout_mask(buf, self.dropout_p, self.dropout_seed, self._shared["dropout_step"])
         else:
-            ops.dropout_mask_dev(buf, DROPOUT_P, self.dropout_seed, dev["state"], dev["offset"])
+            ops.dropout_mask_dev(buf, self.dropout_p, self.dropout_seed, dev["state"], dev["offset"])
             dev["offset"] += 1
         self._shared["dropout_step"] += 1
         return buf
@@ -457,11 +458,11 @@ class EngineBase(DeviceCounters):
         return self.dropout_mask(self.vec_dim, generator)
 
     def dropout_mask(self, n, generator=None, slot=0):
-        """Keep mask [B, n] of Dropout(.3) scaled by 1/(1-p).  Default: the HIP generator kernel, draw number `dropout_step` of
+        """Keep mask [B, n] of Dropout(dropout_p) scaled by 1/(1-p).  Default: the HIP generator kernel, draw number `dropout_step` of
         stream `dropout_seed` (reproducible; the trainer offsets the seed by the replica rank), written into one reused buffer
         per `slot`.  With a torch generator: torch's own stream of random numbers (tests)."""
         if generator is not None:
-            return (torch.rand((self.B, n), device=self.device, generator=generator) >= DROPOUT_P).to(torch.float32) / (1.0 - DROPOUT_P)
+            return (torch.rand((self.B, n), device=self.device, generator=generator) >= self.dropout_p).to(torch.float32) / (1.0 - self.dropout_p)
         buf = self._mask_bufs.get(slot)
         if buf is None or buf.shape[1] != n:
             buf = self._mask_bufs[slot] = torch.empty((self.B, n), dtype=torch.float32, device=self.device)

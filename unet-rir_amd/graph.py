@@ -34,6 +34,7 @@ class Node:
 
 class GraphEngine(EngineBase):
     mask_on_side_stream = False      # the dropout masks are consumed by nodes of the main stream (trainer.Trainer._make_mask)
+    output_act = "sigmoid"           # the output activation fused into the loss kernel: "sigmoid" | "relu1" (dl_models/ae_net.py:249)
 
     def __init__(self, B, device="cuda:0", n_replicas=1, runtime=None, share=None, dtype="f32", overlap_wgrad=False):
         """dtype: storage type of the trunk ("f32" or "bf16").
@@ -44,6 +45,7 @@ class GraphEngine(EngineBase):
         runtime, share: see EngineBase (share: an engine of the same class and configuration)."""
         super().__init__(device, n_replicas, dtype, runtime, share)
         self._h_kernels = []                           # kernels of the convolutions that run in bf16 (work copies needed)
+        self.c22_passes = {}                           # layer name -> passes served by the 2x2 stride-2 kernels (_conv2x2)
         self._s2_kernels = []                          # 3x3 stride-2 kernels among them
         self._share = share
         self.include_reg = True       # backward adds d/dw of the l2 terms (False: the caller differentiates them itself)
@@ -118,8 +120,9 @@ class GraphEngine(EngineBase):
             ch.g_set = True
 
     def _conv(self, x: Node, name, cout, k, stride, transpose=False, followed_by_bn=True, pad_in=0, pad_out=0, l2=True,
-              dense=False, out: Node = None):
-        """Conv2D / Conv2DTranspose (TF 'same'; 1x1 'valid' is the same geometry) + bias."""
+              dense=False, out: Node = None, c22=False):
+        """Conv2D / Conv2DTranspose (TF 'same'; 1x1 'valid' is the same geometry) + bias.  c22: a 2x2 stride-2 layer whose passes run
+        on csrc/conv2x2.hip where ops.conv2x2s2_supported offers them (_conv2x2)."""
         B, cin = self.B, x.a.C
         if transpose:
             H, W = x.a.H * stride, x.a.W * stride
@@ -165,6 +168,10 @@ class GraphEngine(EngineBase):
             return cs["rows"], cs["buf"]
 
         colstat()
+        # the passes of a 2x2 stride-2 layer that the conv2x2 kernels take (0: every other layer)
+        m22 = ops.conv2x2s2_supported(g, x.a, y.a, transpose) if c22 else 0
+        if c22:
+            self.c22_passes[name] = m22
 
         def dense_dgrad(dst, add):
             if add is None:      # split-K path: the weight matrix streams from every CU
@@ -183,6 +190,8 @@ class GraphEngine(EngineBase):
                 else:
                     ops.conv2d_fwd_colstat(g, x.a, wf(), self.p[bname], y.a, cst)
                 y.cst = (rows, cst)
+            elif m22 & ops.C22_FWD:
+                (ops.conv2x2s2_transpose_fwd if transpose else ops.conv2x2s2_fwd)(g, x.a, wb() if transpose else wf(), self.p[bname], y.a)
             elif transpose:
                 ops.conv2d_transpose_fwd(g, x.a, wb(), self.p[bname], y.a)
             else:
@@ -190,7 +199,10 @@ class GraphEngine(EngineBase):
 
         def bwd():
             with self._wg() as ws_:       # leaves of the backward pass: side stream when there is one
-                if transpose:
+                if m22 & ops.C22_WGRAD:
+                    (ops.conv2x2s2_transpose_wgrad if transpose else ops.conv2x2s2_wgrad)(
+                        g, x.a, y.g, self.g[kname], ws_, reg=reg(), w=self.p[kname], defer=self._rb if self.park_reduces else None)
+                elif transpose:
                     ops.conv2d_transpose_wgrad(g, x.a, y.g, self.g[kname], ws_, reg=reg(), w=self.p[kname], defer=self._rb if self.park_reduces else None)
                 else:
                     ops.conv2d_wgrad(g, x.a, y.g, self.g[kname], ws_, reg=reg(), w=self.p[kname], defer=self._rb if self.park_reduces else None)
@@ -198,10 +210,38 @@ class GraphEngine(EngineBase):
                     ops.colsum(y.g, self.g[bname], ws_)
             if dense:
                 self._emit(x, dense_dgrad)
+            elif m22 & ops.C22_DGRAD and transpose:
+                self._emit(x, lambda dst, add: ops.conv2x2s2_transpose_dgrad(g, y.g, wf(), dst, addend=add))
+            elif m22 & ops.C22_DGRAD:
+                self._emit(x, lambda dst, add: ops.conv2x2s2_dgrad(g, y.g, wb(), dst, addend=add))
             elif transpose:
                 self._emit(x, lambda dst, add: ops.conv2d_transpose_dgrad(g, y.g, wf(), dst, addend=add, w_packed=wpk()))
             else:
                 self._emit(x, lambda dst, add: ops.conv2d_dgrad(g, y.g, wb(), dst, addend=add))
+        self._push(fwd, bwd)
+        return y
+
+    def _conv2x2(self, x: Node, name, cout, transpose=False, out: Node = None, generic=False):
+        """Conv2D / Conv2DTranspose(k=2, strides=2, 'same', l2(0.001)) (dl_models/ae_net.py:273-279, :301-307), no BatchNorm behind it.
+        On a bf16 trunk the passes ops.conv2x2s2_supported offers run on the 2x2 kernels, the others - generic=True, fp32 storage,
+        odd sizes: all of them - on the tap-table kernels of _conv."""
+        y = self._conv(x, name, cout, 2, 2, transpose=transpose, followed_by_bn=False, l2=True, out=out,
+                       c22=not generic and x.a.sfx == "bf16")
+        self.c22_passes.setdefault(name, 0)
+        return y
+
+    def _pad2(self, x: Node, h, w):
+        """Reshape((h, w, 2)) of a [B,1,1,h*w*2] fp32 node with the 2 channels zero-padded to 4, as the network input is: a strided copy."""
+        B = self.B
+        y = self._new(h, w, 4, f32=True)
+        y.a.base.zero_()
+
+        def fwd():
+            y.a.base.view(B, h * w, 4)[:, :, :2].copy_(x.a.base.view(B, h * w, 2))
+
+        def bwd():
+            x.g.base.view(B, h * w, 2).copy_(y.g.base.view(B, h * w, 4)[:, :, :2])
+            x.g_set = True
         self._push(fwd, bwd)
         return y
 
@@ -342,7 +382,7 @@ class GraphEngine(EngineBase):
         return self._conv(x, name, n_out, 1, 1, False, followed_by_bn=False, l2=False, dense=True)
 
     def _dropout(self, x: Node, which):
-        """Dropout(.3) with an externally supplied keep mask self.masks[which] (already scaled by 1/(1-p))."""
+        """Dropout(dropout_p) with an externally supplied keep mask self.masks[which] (already scaled by 1/(1-p))."""
         y = self._new(x.a.H, x.a.W, x.a.C, f32=x.a.sfx == "f32")
         if x.a.sfx != "f32":
             raise ValueError("Dropout sits on the fp32 Dense branches")
@@ -416,7 +456,7 @@ class GraphEngine(EngineBase):
         self.include_reg = include_reg
         if dpred is not None:
             self._check_batch(dpred, "dpred")
-            ops.sigmoid_bwd(self.pred, dpred, self.logits.g)
+            (ops.relu1_bwd if self.output_act == "relu1" else ops.sigmoid_bwd)(self.pred, dpred, self.logits.g)
             self.logits.g_set = True
         for (_, bwd), end in zip(reversed(self.ops), reversed(self._op_ends)):
             bwd()
@@ -439,9 +479,9 @@ class GraphEngine(EngineBase):
             la = self._logits32
         if target is not None:
             gb = self.B if global_batch is None else global_batch
-            ops.sigmoid_loss(la, target, alpha, 1.0 / (2.0 * self.H * self.W * gb), self.pred, logits.g, self.loss_out, self.ws,
-                             **self._loss_extras())
+            (ops.relu1_loss if self.output_act == "relu1" else ops.sigmoid_loss)(
+                la, target, alpha, 1.0 / (2.0 * self.H * self.W * gb), self.pred, logits.g, self.loss_out, self.ws, **self._loss_extras())
             logits.g_set = True
         else:
-            ops.sigmoid_nchw(la, self.pred)
+            (ops.relu1_nchw if self.output_act == "relu1" else ops.sigmoid_nchw)(la, self.pred)
         return self.pred

@@ -38,6 +38,7 @@ from torch import nn
 from . import ops
 from .device import HipRuntime
 from .ae import AutoencoderEngine
+from .aenet import AENetEngine
 from .engine import L2_COEF, UNetEngine
 from .resae import ResAEEngine
 from .unet_graph import UNetGraphEngine
@@ -381,6 +382,36 @@ class UNet(_EngineModule):
         dtype = prm[8] if len(prm) > 8 else "f32"
         ue = cls(input_shape, inf_vector_shape, lr, mode, f0, kernels, bn, depth=depth, batch_size=batch_size, device=device,
                  dtype=dtype, **kw)
+        ue.load_weights(os.path.join(save_folder, "weights.npz"))
+        return ue
+
+
+class AENet(UNet):
+    """AENet of the reference (dl_models/ae_net.py:34-62): the U-Net skeleton with 2x2 stride-2 convolutions, a Flatten || Dense
+    bottleneck with Dropout(.5) and a clipped-ReLU output, on aenet.AENetEngine.  Constructor arguments keep the reference's names,
+    order and defaults (it has no `kernels`); the additions are UNet's.  `compile_and_fit`, `get_callbacks`, `summary`, `save` /
+    `load` / `load_weights`, `predict_stft` and `model.model.trainable_variables` / `.losses` are the shared ones."""
+
+    def __init__(self, input_shape, inf_vector_shape, learning_rate=1e-5, mode=0, number_filters_0=32, BatchNorm=True,
+                 resize_factor_0=None, res_factor=None, name="AENet", batch_size=None, device="cuda:0", n_replicas=1, dropout=True,
+                 dtype="f32", overlap=False, fold_l2=True, runtime=None):
+        super().__init__(input_shape, inf_vector_shape, learning_rate, mode, number_filters_0, 2, BatchNorm, resize_factor_0, res_factor,
+                         name, 4, batch_size, device, n_replicas, dropout, dtype, overlap, fold_l2, runtime)
+
+    def _new_engine(self, B, share):
+        return AENetEngine(self.H, self.W, B, F0=self.number_filters_0, mode=self.mode, batchnorm=self.BatchNorm,
+                           inf_vector_shape=self.inf_vector_shape, device=self._device, n_replicas=self.n_replicas, runtime=self._rt,
+                           share=share, dtype=self.dtype_name, overlap_wgrad=self.overlap)
+
+    def _ctor_parameters(self):            # dl_models/ae_net.py:176-183, then this build's dtype
+        return [self.input_shape, self.inf_vector_shape, self.learning_rate, self.mode, self.number_filters_0, self.BatchNorm,
+                self.dtype_name]
+
+    @classmethod
+    def load(cls, save_folder=".", batch_size=1, device="cuda:0", **kw):
+        with open(os.path.join(save_folder, "parameters.pkl"), "rb") as f:
+            prm = pickle.load(f)
+        ue = cls(*prm[:6], batch_size=batch_size, device=device, dtype=prm[6] if len(prm) > 6 else "f32", **kw)
         ue.load_weights(os.path.join(save_folder, "weights.npz"))
         return ue
 

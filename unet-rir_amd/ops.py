@@ -269,6 +269,64 @@ def conv2d_transpose_wgrad(g, x: Act, dy: Act, dw, ws: Workspace, reg=0.0, w=Non
     _wgrad("conv2d_transpose_wgrad", g, x, dy, dw, ws, reg, w, defer, conv2d_transpose_wgrad_ws_bytes(g))
 
 
+# ---- the 2x2 stride-2 layers (dl_models/ae_net.py:273-279, :301-307; csrc/conv2x2.hip): same arguments as the conv2d_* twins
+
+C22_FWD, C22_DGRAD, C22_WGRAD = 1, 2, 4
+
+
+def conv2x2s2_supported(g, x: Act, y: Act, transpose=False):
+    """The passes of the layer with input x and output y that the 2x2 stride-2 kernels should run, as a mask of C22_FWD | C22_DGRAD |
+    C22_WGRAD (bf16 storage, even sizes, power-of-two channel counts, and not slower than the generic kernels in the measured
+    record; include/unetrir.h).  The caller runs the other passes - 0: the whole layer - on conv2d_* / conv2d_transpose_*."""
+    if x.sfx != "bf16" or y.sfx != "bf16":
+        return 0
+    fn = _lib.lib().unetrir_conv2x2s2_transpose_supported_bf16 if transpose else _lib.lib().unetrir_conv2x2s2_supported_bf16
+    return int(fn(C.byref(g), x.ld, y.ld))
+
+
+def conv2x2s2_fwd(g, x: Act, w, bias, y: Act, addend: Act = None):
+    """Conv2D(k=2, strides=2, 'same') forward on even sizes (dl_models/ae_net.py:273-279); w [Cout][2][2][Cin] bf16."""
+    check(_lib.lib().unetrir_conv2x2s2_fwd_bf16(C.byref(g), _p(x), x.ld, _p(w), _p(bias), _p(addend),
+                                                addend.ld if addend is not None else 0, _p(y), y.ld, _stream()), "conv2x2s2_fwd")
+
+
+def conv2x2s2_dgrad(g, dy: Act, wt, dx: Act, addend: Act = None):
+    """Its data gradient; wt [Cin][2][2][Cout] bf16.  Every dx pixel is written once."""
+    check(_lib.lib().unetrir_conv2x2s2_dgrad_bf16(C.byref(g), _p(dy), dy.ld, _p(wt), _p(addend),
+                                                  addend.ld if addend is not None else 0, _p(dx), dx.ld, _stream()), "conv2x2s2_dgrad")
+
+
+def conv2x2s2_wgrad_ws_bytes(g):
+    return _lib.lib().unetrir_conv2x2s2_wgrad_ws_bytes(C.byref(g))
+
+
+def conv2x2s2_wgrad(g, x: Act, dy: Act, dw, ws: Workspace, reg=0.0, w=None, defer: ReduceBatch = None):
+    """Its weight gradient dw [Cout][2][2][Cin] fp32 (+ reg * w); defer as conv2d_wgrad."""
+    _wgrad("conv2x2s2_wgrad", g, x, dy, dw, ws, reg, w, defer, conv2x2s2_wgrad_ws_bytes(g))
+
+
+def conv2x2s2_transpose_fwd(g, x: Act, wt, bias, y: Act):
+    """Conv2DTranspose(k=2, strides=2, 'same') forward (dl_models/ae_net.py:301-307); wt [Cout][2][2][Cin] bf16."""
+    check(_lib.lib().unetrir_conv2x2s2_transpose_fwd_bf16(C.byref(g), _p(x), x.ld, _p(wt), _p(bias), _p(y), y.ld, _stream()),
+          "conv2x2s2_transpose_fwd")
+
+
+def conv2x2s2_transpose_dgrad(g, dy: Act, w, dx: Act, addend: Act = None):
+    """Its data gradient; w [Cin][2][2][Cout] bf16 (the primary layout)."""
+    check(_lib.lib().unetrir_conv2x2s2_transpose_dgrad_bf16(C.byref(g), _p(dy), dy.ld, _p(w), _p(addend),
+                                                            addend.ld if addend is not None else 0, _p(dx), dx.ld, _stream()),
+          "conv2x2s2_transpose_dgrad")
+
+
+def conv2x2s2_transpose_wgrad_ws_bytes(g):
+    return _lib.lib().unetrir_conv2x2s2_transpose_wgrad_ws_bytes(C.byref(g))
+
+
+def conv2x2s2_transpose_wgrad(g, x: Act, dy: Act, dw, ws: Workspace, reg=0.0, w=None, defer: ReduceBatch = None):
+    """Its weight gradient dw [Cin][2][2][Cout] fp32 (+ reg * w)."""
+    _wgrad("conv2x2s2_transpose_wgrad", g, x, dy, dw, ws, reg, w, defer, conv2x2s2_transpose_wgrad_ws_bytes(g))
+
+
 def dense_fwd(x: Act, w, bias, y: Act, ws: Workspace):
     """Dense on a small batch (dl_models/u_net.py:259): x [B,1,1,K] . w[N][K]^T + bias -> y [B,1,1,N]."""
     B, K, N = x.B, x.C, y.C
@@ -665,6 +723,25 @@ def sigmoid_nchw(logits: Act, pred):
 def sigmoid_bwd(pred, dpred, dlogits: Act):
     B, _, H, W = pred.shape
     check(_fn("sigmoid_bwd", dlogits.sfx)(_p(pred), _p(dpred), B, H, W, _p(dlogits), _stream()), "sigmoid_bwd")
+
+
+def relu1_loss(logits: Act, target, alpha, inv_norm, pred, dlogits: Act, loss_out, ws: Workspace, phase_ref=None, phase_weight=None):
+    """Clipped-ReLU head `relu(out, max_value=1)` (dl_models/ae_net.py:249) + compute_loss + dL/dlogits: sigmoid_loss with the other
+    output activation (same arguments, same loss_out)."""
+    B, _, H, W = target.shape
+    ws.reserve(_lib.lib().unetrir_loss_ws_bytes(B * H * W))
+    check(_fn("relu1_loss_ex", dlogits.sfx)(_p(logits), logits.ld, _p(target), _p(phase_ref), _p(phase_weight), B, H, W, alpha,
+                                            inv_norm, _p(pred), _p(dlogits), _p(loss_out), ws.ptr, ws.nbytes, _stream()), "relu1_loss_ex")
+
+
+def relu1_nchw(logits: Act, pred):
+    B, _, H, W = pred.shape
+    check(_lib.lib().unetrir_relu1_nchw_f32(_p(logits), logits.ld, B, H, W, _p(pred), _stream()), "relu1_nchw")
+
+
+def relu1_bwd(pred, dpred, dlogits: Act):
+    B, _, H, W = pred.shape
+    check(_fn("relu1_bwd", dlogits.sfx)(_p(pred), _p(dpred), B, H, W, _p(dlogits), _stream()), "relu1_bwd")
 
 
 # ---- information vector ----------------------------------------------------------------------

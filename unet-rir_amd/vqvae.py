@@ -55,21 +55,6 @@ class VQVAEEngine(AEFamilyEngine):
             q = self._cast(q)                                               # the quantiser is fp32, the transposed-conv trunk bf16
         self._conv_decoder(q, RELU, l2=False)                               # no Dense / Dropout / Reshape at the entry (:343-423)
 
-    def _pad2(self, x: Node, h, w):
-        """Reshape((h, w, 2)) (:512) with the 2 channels zero-padded to 4, as the network input is: a strided copy."""
-        B = self.B
-        y = self._new(h, w, 4, f32=True)
-        y.a.base.zero_()
-
-        def fwd():
-            y.a.base.view(B, h * w, 4)[:, :, :2].copy_(x.a.base.view(B, h * w, 2))
-
-        def bwd():
-            x.g.base.view(B, h * w, 2).copy_(y.g.base.view(B, h * w, 4)[:, :, :2])
-            x.g_set = True
-        self._push(fwd, bwd)
-        return y
-
     def _vq(self, x: Node, K, D):
         """VectorQuantizer (:42-98) over the fp32 node x; the codebook `embeddings` [D, K] is an ordinary parameter."""
         name = "vector_quantizer.embeddings"
