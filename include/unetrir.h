@@ -289,6 +289,52 @@ int unetrir_adam_dev_f32(float* theta, const float* g, float* m, float* v, long 
 int unetrir_dropout_mask_dev_f32(float* mask, long long n, float p, unsigned long long seed,
                                  const unsigned long long* step_base, unsigned long long step_offset, unetrir_stream_t stream);
 
+/* ---- tfa.optimizers.LAMB(learning_rate) (trainer.py:37-38; tensorflow_addons' _resource_apply_dense).  PARITY UNPINNED
+ *      (tensorflow_addons is not available here): a restatement of the source text, held to an fp64 restatement.  Per variable,
+ *      step t (1-based), g already multiplied by grad_scale:
+ *          m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2;   m^ = m / corr1;   v^ = v / corr2
+ *          u = m^ / (sqrt(v^) + eps)  [+ weight_decay w  if the variable is flagged UNETRIR_LAMB_DECAY]
+ *          r = ||w||_2 / ||u||_2  if the variable is flagged UNETRIR_LAMB_ADAPT and both norms are > 0, else 1
+ *          w = w - (lr r) u
+ *      corr1 = 1 - beta1^t, corr2 = 1 - beta2^t, formed in fp64 from the fp32 betas and rounded to fp32 once (by the caller, or -
+ *      the _dev form - by the kernels from state[0] and cfg of unetrir_step_advance: lr, the betas, eps and grad_scale then come
+ *      from cfg too, so a captured step replays correctly; weight_decay stays a launch argument).  tfa's defaults: beta1 .9,
+ *      beta2 .999, eps 1e-6, weight_decay 0; the reference passes learning_rate only (no decay, every variable adapted).
+ *      The variables are described by a table of unetrir_lamb_seg, one per variable, slots back to back in the flat buffers:
+ *      only the first `count` elements of a slot are read for the norms or written (the alignment tail is carried through
+ *      unchanged).  unetrir_lamb_table_init validates a table (offsets / slots multiples of 4, 1 <= count <= slot, contiguous),
+ *      fills every chunk0 and - when chunk_seg is given, with room for chunk_cap entries - the map chunk -> variable; it returns
+ *      the number of chunks (-1: invalid table).  A chunk is unetrir_lamb_chunk_elems() consecutive elements of ONE variable,
+ *      numbered from the variable's own start: the reduction order of a variable does not depend on the range a call covers.
+ *      unetrir_lamb_f32 / _dev_f32 run the step on the variables whose slots are exactly [lo, hi) (element offsets into theta /
+ *      g / m / v, which all share the table's layout) in THREE launches whatever the number of variables: moments + fp64 partial
+ *      sums of w^2 and u^2 per chunk; one workgroup per variable combines them in a fixed order (comparison with zero and the
+ *      division in fp64, one rounding to fp32); the step, with u recomputed from the stored m, v and the old w by the same
+ *      arithmetic.  No atomics; two runs are bit-identical, and so are a whole-buffer call and calls range by range.
+ *      segs_host and segs are the same initialised table in host and in device memory, chunk_seg is in device memory.
+ *      ws: unetrir_lamb_ws_bytes(n_seg, n_chunks) bytes, 8-byte aligned, shared by every range of one table:
+ *      n_chunks x {sum w^2, sum u^2} doubles, then n_seg floats r (readable after the call).
+ *      UNETRIR_EINVAL before any launch: a null pointer, n_seg <= 0, theta / g / m / v not 16-byte aligned, [lo, hi) not beginning
+ *      and ending on a variable boundary, ws_bytes too small. */
+#define UNETRIR_LAMB_DECAY 1
+#define UNETRIR_LAMB_ADAPT 2
+typedef struct unetrir_lamb_seg {
+    long long offset;   /* first element of the variable's slot */
+    long long count;    /* the variable's own elements */
+    long long slot;     /* slot length: the next variable starts at offset + slot */
+    int flags;          /* UNETRIR_LAMB_DECAY | UNETRIR_LAMB_ADAPT */
+    int chunk0;         /* number of the variable's first chunk (written by unetrir_lamb_table_init) */
+} unetrir_lamb_seg;
+int unetrir_lamb_chunk_elems(void);
+long long unetrir_lamb_table_init(unetrir_lamb_seg* segs, int n_seg, int32_t* chunk_seg, long long chunk_cap);
+size_t unetrir_lamb_ws_bytes(int n_seg, long long n_chunks);
+int unetrir_lamb_f32(float* theta, const float* g, float* m, float* v, const unetrir_lamb_seg* segs_host, const unetrir_lamb_seg* segs,
+                     const int32_t* chunk_seg, int n_seg, long long lo, long long hi, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, float corr1, float corr2, float grad_scale, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_lamb_dev_f32(float* theta, const float* g, float* m, float* v, const unetrir_lamb_seg* segs_host, const unetrir_lamb_seg* segs,
+                         const int32_t* chunk_seg, int n_seg, long long lo, long long hi, float weight_decay,
+                         const unsigned long long* state, const float* cfg, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+
 /* ---- bf16-storage variants (BASELINE.json configs[1] names bf16): activations, their gradients and the weight work
  *      copies are bfloat16 (unetrir_bf16), accumulation is fp32 (v_mfma_f32_32x32x16_bf16), bias / BatchNorm parameters /
  *      statistics / weight gradients / master weights stay fp32.  Channel counts and pixel strides are multiples of 8

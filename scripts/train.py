@@ -64,9 +64,12 @@ def main():
     ap.add_argument("--no-lr-decay", action="store_true")
     ap.add_argument("--decay-from", type=int, default=80)
     ap.add_argument("--batch", type=int, default=16)
-    ap.add_argument("--optimizer", default="adam", help="adam, nadam or sgd")
+    ap.add_argument("--optimizer", default="adam", help="adam, nadam, sgd (main_training.py:164-169) or lamb (trainer.py:37-38)")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="LAMB only: tfa's weight_decay")
     ap.add_argument("--out", required=True, help="checkpoint directory (main_training.py: ../results/<name>)")
     a = ap.parse_args()
+    if a.optimizer.lower() == "lamb":          # the Trainer takes LAMB as an object mirroring tfa's constructor, never as a name
+        a.optimizer = U.LAMB(learning_rate=a.lr, weight_decay=a.weight_decay)
     if not torch.cuda.is_available():
         raise SystemExit("training runs on the GPU; there is none here")
     dev = torch.device("cuda:0")

@@ -17,6 +17,7 @@ from .vqvae import VQVAEEngine  # noqa: F401
 from .data import DeviceBatchPipeline, synthetic_batches  # noqa: F401
 from .evaluate import Evaluator, score, write_report  # noqa: F401
 from .dataset import DataGenerator, Dataset, read_wav  # noqa: F401
+from .lamb import LAMB  # noqa: F401
 from .trainer import CheckpointManager, GradBucketer, Trainer, fit, lr_schedule  # noqa: F401
 
-__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "HipRuntime", "Trainer", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "write_report", "Dataset", "DataGenerator", "read_wav"]
+__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "HipRuntime", "Trainer", "LAMB", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "write_report", "Dataset", "DataGenerator", "read_wav"]

@@ -24,6 +24,11 @@ class ReduceDesc(C.Structure):
     _fields_ = [("part", C.c_void_p), ("nsplit", C.c_int), ("n", C.c_size_t), ("out", C.c_void_p), ("reg", C.c_float), ("w", C.c_void_p)]
 
 
+class LambSeg(C.Structure):
+    """unetrir_lamb_seg (include/unetrir.h): one variable of the LAMB segment table."""
+    _fields_ = [("offset", C.c_longlong), ("count", C.c_longlong), ("slot", C.c_longlong), ("flags", C.c_int), ("chunk0", C.c_int)]
+
+
 class Config(C.Structure):
     """unetrir_config: kernel-selection switches (include/unetrir.h)."""
     _fields_ = [(n, C.c_int) for n in ("conv3x3", "conv3x3g", "conv3x3g_pair", "conv3x3h", "conv3x3s", "conv3x3r", "stem",
@@ -238,6 +243,15 @@ _SIGS = {
                                          C.c_int, C.c_int, C.c_float, c_f32p, C.c_ulonglong, C.c_ulonglong, c_f32p, C.c_void_p,
                                          C.c_size_t, c_stream]),
     "unetrir_uniform_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_ulonglong, c_stream]),
+    # tfa.optimizers.LAMB (lamb.hip)
+    "unetrir_lamb_chunk_elems": (C.c_int, []),
+    "unetrir_lamb_table_init": (C.c_longlong, [C.POINTER(LambSeg), C.c_int, C.c_void_p, C.c_longlong]),
+    "unetrir_lamb_ws_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
+    "unetrir_lamb_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(LambSeg), C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
+                                   C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                   C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_lamb_dev_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(LambSeg), C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
+                                       C.c_longlong, C.c_float, C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "unetrir_prof_enable": (C.c_int, [C.c_int]),
     "unetrir_prof_collect": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }

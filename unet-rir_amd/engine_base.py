@@ -136,6 +136,9 @@ class DeviceCounters:
         """Device counters only: the optimizer's scalars as the next step_advance launch reads them.  Copies only when a value
         changed (the rate changes once per epoch, main_training.py:342-344): a blocking 20-byte transfer, outside any graph."""
         dev = self._dev()
+        if self.optimizer == "lamb":               # the LAMB kernels read the betas and eps from cfg: the selected object's, not Adam's defaults
+            o = self._shared["lamb"]["opt"]
+            beta1, beta2, eps = o.beta_1, o.beta_2, o.epsilon
         cfg = (float(lr), beta1, beta2, eps, float(grad_scale))
         if dev is not None and dev["cfg_host"] != cfg:
             dev["cfg"][:5].copy_(torch.tensor(cfg, dtype=torch.float32))
@@ -152,9 +155,39 @@ class DeviceCounters:
         self._shared["dropout_step"] += 1
         return buf
 
-    optimizer = "adam"           # "adam" | "nadam" | "sgd" (main_training.py:164-169); set through trainer.Trainer(optimizer=)
+    # "adam" | "nadam" | "sgd" (main_training.py:164-169) | "lamb" (trainer.py:37-38); set through trainer.Trainer(optimizer=)
+    optimizer = "adam"
+
+    def set_lamb(self, opt):
+        """Select tfa.optimizers.LAMB with the hyperparameters of `opt` (lamb.LAMB).  The segment table - one entry per ParamSpec, the
+        exclusion lists resolved into its flags - is built on first use and shared by every engine over this parameter set."""
+        self.optimizer = "lamb"
+        old = self._shared.get("lamb")
+        same_flags = old is not None and opt.segments(self.specs) == old["opt"].segments(self.specs)
+        self._shared["lamb"] = {"opt": opt, "table": old["table"] if same_flags else None}
+
+    def _lamb_table(self):
+        st = self._shared["lamb"]
+        if st["table"] is None:
+            st["table"] = ops.make_lamb_table(st["opt"].segments(self.specs), self.device)
+        return st["table"]
+
+    def _lamb(self, lo, hi, lr, beta1, beta2, eps, weight_decay, corr1, corr2, grad_scale):
+        tab = self._lamb_table()
+        if lo is None:
+            lo, hi = tab.begin, tab.end
+        if not tab.is_range(lo, hi):
+            raise ValueError(f"LAMB needs a range of whole variables: [{lo}, {hi}) does not begin and end on a parameter boundary")
+        dev = self._dev()
+        if dev is None:
+            ops.lamb(tab, self.theta, self.grad, self.adam_m, self.adam_v, lo, hi, lr, beta1, beta2, eps, weight_decay, corr1, corr2, grad_scale)
+        else:
+            ops.lamb_dev(tab, self.theta, self.grad, self.adam_m, self.adam_v, lo, hi, weight_decay, dev["state"], dev["cfg"])
+        self.t_dirty = True
 
     def _adam(self, lo, hi, *args):
+        if args[0] == "lamb":
+            return self._lamb(lo, hi, *args[1:])
         dev = self._dev()
         th, g, m, v = (self.theta, self.grad, self.adam_m, self.adam_v) if lo is None else \
             (self.theta[lo:hi], self.grad[lo:hi], self.adam_m[lo:hi], self.adam_v[lo:hi])
@@ -175,9 +208,15 @@ class DeviceCounters:
     def adam_begin(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
         """Advance the step count once and return the arguments of adam_range for this step (bucket-wise optimizer).  Adam: the
         bias-corrected rate; Nadam: the momentum-schedule coefficients of this step (the running product of the schedule lives
-        beside the step count); SGD: the rate."""
+        beside the step count); SGD: the rate; LAMB: the hyperparameters of the selected object (not the beta / eps arguments) and
+        the two bias corrections 1 - beta^t."""
         self.adam_t += 1
         t = self.adam_t
+        if self.optimizer == "lamb":
+            # in fp64 from the betas as the kernels see them (fp32): the expression the device form evaluates from state[0] and cfg
+            o = self._shared["lamb"]["opt"]
+            b1, b2 = _as_f32(o.beta_1), _as_f32(o.beta_2)
+            return ("lamb", lr, o.beta_1, o.beta_2, o.epsilon, o.weight_decay, 1.0 - b1 ** t, 1.0 - b2 ** t, grad_scale)
         if self.optimizer == "sgd":
             return ("sgd", lr, grad_scale)
         if self.optimizer == "nadam":
@@ -192,7 +231,8 @@ class DeviceCounters:
         return (lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t), beta1, beta2, eps, grad_scale)
 
     def adam_range(self, lo, hi, *args):
-        """The optimizer on the flat parameter range [lo, hi) (element offsets, multiples of the 64-float alignment)."""
+        """The optimizer on the flat parameter range [lo, hi) (element offsets, multiples of the 64-float alignment; LAMB: a range
+        of whole parameters, else ValueError)."""
         self._adam(lo, hi, *args)
 
 

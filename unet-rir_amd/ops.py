@@ -802,6 +802,89 @@ def adam_dev(theta, g, m, v, hyper):
     check(_lib.lib().unetrir_adam_dev_f32(_p(theta), _p(g), _p(m), _p(v), theta.numel(), _p(hyper), _stream()), "adam_dev")
 
 
+# ---- tfa.optimizers.LAMB (trainer.py:37-38; csrc/lamb.hip) ---------------------------------------------
+
+LAMB_DECAY, LAMB_ADAPT = 1, 2
+
+
+def lamb_chunk_elems():
+    """Elements of one chunk of the LAMB kernels (a chunk never crosses a variable)."""
+    return int(_lib.lib().unetrir_lamb_chunk_elems())
+
+
+def lamb_ws_bytes(n_seg, n_chunks):
+    return int(_lib.lib().unetrir_lamb_ws_bytes(int(n_seg), int(n_chunks)))
+
+
+class LambTable:
+    """The segment table of the LAMB kernels, built once per parameter set: one entry (offset, real element count, slot length,
+    flags) per variable, slots back to back, in host memory (argument checks) and in device memory (the kernels), the map
+    chunk -> variable, and the workspace every range of the table shares (per-chunk partial sums, then one ratio per variable)."""
+
+    def __init__(self, segments, device):
+        """segments: (offset, count, slot, decayed, adapted) per variable, in buffer order."""
+        L = _lib.lib()
+        self.n_seg = len(segments)
+        self.host = (_lib.LambSeg * max(self.n_seg, 1))()
+        for s_, (off, cnt, slot, dec, ada) in zip(self.host, segments):
+            s_.offset, s_.count, s_.slot = int(off), int(cnt), int(slot)
+            s_.flags = (LAMB_DECAY if dec else 0) | (LAMB_ADAPT if ada else 0)
+        self.n_chunks = int(L.unetrir_lamb_table_init(self.host, self.n_seg, None, 0))
+        if self.n_chunks <= 0:
+            raise ValueError("LAMB segment table: slots must be contiguous, 4-element aligned and hold 1 <= count <= slot elements")
+        chunk_seg = torch.empty(self.n_chunks, dtype=torch.int32)
+        L.unetrir_lamb_table_init(self.host, self.n_seg, C.c_void_p(chunk_seg.data_ptr()), self.n_chunks)
+        self.device = torch.device(device)
+        self.segs = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(self.device)
+        self.chunk_seg = chunk_seg.to(self.device)
+        self.starts = {int(s[0]): i for i, s in enumerate(segments)}
+        self.ends = {int(s[0]) + int(s[2]): i + 1 for i, s in enumerate(segments)}
+        self.begin, self.end = int(segments[0][0]), int(segments[-1][0]) + int(segments[-1][2])
+        self.ws_bytes = lamb_ws_bytes(self.n_seg, self.n_chunks)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+
+    def is_range(self, lo, hi):
+        """[lo, hi) begins and ends on a variable boundary."""
+        return lo in self.starts and hi in self.ends and self.starts[lo] < self.ends[hi]
+
+    def ratios(self, ws=None):
+        """The trust ratios the last call wrote, one per variable (fp32 view of the workspace)."""
+        ws = self.ws if ws is None else ws
+        return ws[16 * self.n_chunks:16 * self.n_chunks + 4 * self.n_seg].view(torch.float32)
+
+
+def make_lamb_table(segments, device):
+    return LambTable(segments, device)
+
+
+def _lamb_buffers(table, theta, g, m, v, ws):
+    for t in (theta, g, m, v):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != table.device or t.numel() < table.end:
+            raise ValueError(f"lamb: theta, g, m and v must be contiguous float32 buffers of >= {table.end} elements on {table.device}")
+    ws = table.ws if ws is None else ws
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != table.device:
+        raise ValueError("lamb: the workspace is a contiguous uint8 tensor on the table's device")
+    return ws
+
+
+def lamb(table, theta, g, m, v, lo, hi, lr, beta1, beta2, eps, weight_decay, corr1, corr2, grad_scale=1.0, ws=None):
+    """tfa.optimizers.LAMB step (trainer.py:37-38) on the variables whose slots are [lo, hi) of the WHOLE flat buffers theta / g /
+    m / v; corr1 = 1 - beta1^t, corr2 = 1 - beta2^t (engine_base.DeviceCounters.adam_begin).  Three launches."""
+    ws = _lamb_buffers(table, theta, g, m, v, ws)
+    check(_lib.lib().unetrir_lamb_f32(_p(theta), _p(g), _p(m), _p(v), table.host, _p(table.segs), _p(table.chunk_seg), table.n_seg,
+                                      int(lo), int(hi), float(lr), beta1, beta2, eps, float(weight_decay), float(corr1), float(corr2),
+                                      float(grad_scale), _p(ws), ws.numel(), _stream()), "lamb")
+
+
+def lamb_dev(table, theta, g, m, v, lo, hi, weight_decay, state, cfg, ws=None):
+    """lamb() with the step count read from state[0] and lr, the betas, eps and grad_scale from cfg (the device memory
+    step_advance works on): HIP-graph replay."""
+    ws = _lamb_buffers(table, theta, g, m, v, ws)
+    check(_lib.lib().unetrir_lamb_dev_f32(_p(theta), _p(g), _p(m), _p(v), table.host, _p(table.segs), _p(table.chunk_seg), table.n_seg,
+                                          int(lo), int(hi), float(weight_decay), _p(state), _p(cfg), _p(ws), ws.numel(), _stream()),
+          "lamb_dev")
+
+
 def dropout_mask_dev(mask, p, seed, state, offset):
     """dropout_mask() with draw number state[2] + offset read from device memory (state: the uint64 [3] of step_advance)."""
     check(_lib.lib().unetrir_dropout_mask_dev_f32(_p(mask), mask.numel(), float(p), int(seed), C.c_void_p(state.data_ptr() + 16),

@@ -13,6 +13,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .lamb import LAMB
+
 
 class GradBucketer:
     """Cuts a flat gradient buffer, laid out in backward-completion order, into contiguous buckets and all-reduces
@@ -129,7 +131,7 @@ class Trainer:
       trainer.apply_gradients()                                  #   optimizer.apply_gradients
     """
 
-    def __init__(self, model, lr=5e-7, alpha=0.9, world_size=1, group=None, bucket_bytes=32 << 20, dropout=True, force_dp=False,
+    def __init__(self, model, lr=None, alpha=0.9, world_size=1, group=None, bucket_bytes=32 << 20, dropout=True, force_dp=False,
                  sigmoid_loss=False, diff_loss=False, beta=0.5, graph=False, dropout_seed=None, optimizer="adam"):
         """force_dp: run the bucketed all-reduce path even at world_size 1 (needs an initialised process group; rehearsal).
         sigmoid_loss / diff_loss / beta: the switches of compute_loss (main_training.py:38-40, :214-222; both False in the
@@ -138,7 +140,9 @@ class Trainer:
         graph: capture `step` once into a HIP graph (after one ordinary step that is undone) and replay it - one host call per
         step instead of several hundred launches; single-replica steps without an externally supplied dropout mask only
         (anything else runs the ordinary way).
-        optimizer: "adam" (the live configuration), "nadam" or "sgd" - main_training.py:164-169 selects by substring, so does this.
+        optimizer: "adam" (the live configuration), "nadam" or "sgd" - main_training.py:164-169 selects by substring, so does this -
+        or a `unet_rir_amd.LAMB(...)` object: tfa.optimizers.LAMB of the legacy trainer (trainer.py:37-38).
+        lr: the rate of every step that is not given one (`step(..., lr=)`).  Default 5e-7, or the LAMB object's learning_rate.
         dropout_seed: base seed of the Dropout streams; replica r draws from stream seed + r (independent masks per replica, as
         under MirroredStrategy).  Default: the engine's own seed (torch.initial_seed())."""
         self.module = None
@@ -150,6 +154,8 @@ class Trainer:
                 raise RuntimeError("build the model first (batch_size=...): the trainer drives the engine of one batch size")
         self.engine = engine
         self.rt = engine.rt
+        if lr is None:
+            lr = optimizer.learning_rate if isinstance(optimizer, LAMB) else 5e-7
         self.lr, self.alpha = lr, alpha
         self.world_size = world_size
         self.group = group
@@ -166,11 +172,15 @@ class Trainer:
             engine._seed_offset_by_rank = True
         engine.loss_diff = bool(diff_loss)
         engine.loss_phase_weight = phase_weight(beta, engine.W).to(engine.device) if sigmoid_loss else None
-        opt = str(optimizer).lower()
-        engine.optimizer = "nadam" if "nadam" in opt else ("sgd" if "sgd" in opt else "adam")
-        if "adam" not in opt and "sgd" not in opt:
-            raise ValueError("optimizer must name adam, nadam or sgd (main_training.py:164-169)")
-        self.use_graph = bool(graph) and not dp and engine.optimizer == "adam"
+        if isinstance(optimizer, LAMB):
+            engine.set_lamb(optimizer)
+        else:
+            opt = str(optimizer).lower()
+            if "adam" not in opt and "sgd" not in opt:
+                raise ValueError("optimizer must name adam, nadam or sgd (main_training.py:164-169) or be a unet_rir_amd.LAMB object "
+                                 "(trainer.py:37-38)")
+            engine.optimizer = "nadam" if "nadam" in opt else ("sgd" if "sgd" in opt else "adam")
+        self.use_graph = bool(graph) and not dp and engine.optimizer in ("adam", "lamb")
         self._graphs, self._g_in = {}, None
         # With a side stream in the engine (overlap_wgrad) the optimizer also leaves the critical path: Adam runs bucket by
         # bucket on a third stream as soon as a bucket's gradients are final (and, data-parallel, all-reduced), while the
@@ -390,6 +400,7 @@ class CheckpointManager:
             "dropout_step": int(eng._shared["dropout_step"]),
             "dropout_seed": int((eng.dropout_seed - (self.trainer.rank if getattr(eng, "_seed_offset_by_rank", False) else 0)) & 0xFFFFFFFF),
             "optimizer": eng.optimizer, "m_schedule": float(eng._shared.get("m_schedule", 1.0)),
+            "lamb": eng._shared["lamb"]["opt"].get_config() if eng.optimizer == "lamb" else None,
             "layout": [(k, tuple(s_.shape), int(s_.offset)) for k, s_ in eng.specs.items()],
             "theta": eng.theta.detach().cpu(), "adam_m": eng.adam_m.detach().cpu(), "adam_v": eng.adam_v.detach().cpu(),
             "moving": {k: v.detach().cpu() for k, v in eng.moving.items()},
