@@ -566,6 +566,40 @@ int unetrir_relu1_loss_ex_bf16(const float* logits, int ldl, const float* target
 int unetrir_relu1_nchw_f32(const float* logits, int ldl, int B, int H, int W, float* pred, unetrir_stream_t stream);
 int unetrir_relu1_bwd_f32(const float* pred, const float* dpred, int B, int H, int W, float* dlogits, unetrir_stream_t stream);
 int unetrir_relu1_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits, unetrir_stream_t stream);
+/* The linear output of the phase-difference models, `Conv2D(2, (1, 1), activation='linear')` (dl_models/diff_u_net.py:247) and
+ * `Activation("linear")` (dl_models/diff_vae.py:385), in place of the sigmoid: pred = logit, dL/dlogit = dL/dpred - a phase
+ * difference lies in [-1, 1], which neither bounded output can reach.  unetrir_linear_loss_ex_*: arguments, loss_out layout,
+ * phase_ref / phase_weight, alpha, inv_norm, workspace and the fixed-order sums of unetrir_relu1_loss_ex_*;
+ * unetrir_linear_nchw_f32: inference (the NHWC -> NCHW copy); unetrir_linear_bwd_*: the autograd bridge (`pred` is not read). */
+int unetrir_linear_loss_ex_f32(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                               int B, int H, int W, float alpha, float inv_norm, float* pred, float* dlogits, float* loss_out,
+                               void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_linear_loss_ex_bf16(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                                int B, int H, int W, float alpha, float inv_norm, float* pred, unetrir_bf16* dlogits, float* loss_out,
+                                void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_linear_nchw_f32(const float* logits, int ldl, int B, int H, int W, float* pred, unetrir_stream_t stream);
+int unetrir_linear_bwd_f32(const float* pred, const float* dpred, int B, int H, int W, float* dlogits, unetrir_stream_t stream);
+int unetrir_linear_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits, unetrir_stream_t stream);
+/* ---- output head Conv2D(2, (1, 1), activation='linear') of DiffUNet (dl_models/diff_u_net.py:247) on a bf16 trunk: streaming
+ *      kernels, one pass over the activations forward and one for the whole backward pass (head1x1.hip).
+ *      unetrir_head1x1_supported: mask of the passes served for C input channels - 1 forward, 2 backward; 0 unless C % 8 == 0 and
+ *      8 <= C <= 256.  The caller runs the other passes on unetrir_conv2d_*_bf16 / unetrir_colsum_bf16 with the padded kernel.
+ *      fwd: x bf16 [B*H*W][ldx], ldx >= C, ldx % 8 == 0; w the fp32 [>=2][C] kernel, rounded to bf16 on load (as
+ *      unetrir_head6x6_fwd_bf16 does); bias fp32 [>=2]; y fp32 logits [B*H*W][ldy], ldy >= 4: channels 0, 1 written, 2, 3 zeroed,
+ *      further ones untouched.  fp32 accumulation.
+ *      bwd: dy bf16 [B*H*W][lddy], lddy >= 8, channels 0, 1 read.  dx[p][c] = dy[p][0] w[0][c] + dy[p][1] w[1][c], formed in fp32,
+ *      rounded once, written (no addend); dw[j][c] = sum_p dy[p][j] x[p][c] and dbias[j] = sum_p dy[p][j] for j < 2 in fp32 (further
+ *      rows / entries of a padded gradient are left untouched).  No atomics: one slab of partial sums per workgroup in ws
+ *      (>= unetrir_head1x1_bwd_ws_bytes), summed by a second launch in a fixed order (64 runs of consecutive slabs in index order, then the run sums in run order);
+ *      the slab count depends on (B, H, W, C) alone.
+ *      Every pointer 16-byte aligned; UNETRIR_EINVAL otherwise, before the device is touched. */
+int unetrir_head1x1_supported(int C);
+int unetrir_head1x1_fwd_bf16(const unetrir_bf16* x, int ldx, int B, int H, int W, int C, const float* w, const float* bias,
+                             float* y, int ldy, unetrir_stream_t stream);
+size_t unetrir_head1x1_bwd_ws_bytes(int B, int H, int W, int C);
+int unetrir_head1x1_bwd_bf16(const unetrir_bf16* x, int ldx, const unetrir_bf16* dy, int lddy, int B, int H, int W, int C,
+                             const float* w, unetrir_bf16* dx, int lddx, float* dw, float* dbias, void* ws, size_t ws_bytes,
+                             unetrir_stream_t stream);
 /* glue between the bf16 trunk and the fp32 information-vector branch: y = a + b (Add(), dl_models/u_net.py:229);
  * fp32 copy of a bf16 gradient.  n is a multiple of 4. */
 int unetrir_add_f32_to_bf16(const unetrir_bf16* a, const float* b, unetrir_bf16* y, long long n,

@@ -9,7 +9,7 @@
 --load         a folder written by `UNet.save` / `ResAE.save` / `Autoencoder.save` / `VAE.save` / `VQVAE.save` (--arch picks the class)
 --checkpoint   a `CheckpointManager` directory; the latest checkpoint is restored into a U-Net built from --filters / --kernels
                (--arch vae: into the VAE of rir_generation.py:78-87, latent size --latent; --arch vqvae: into the VQ-VAE of
-               dl_models/vqvae.py:522-531)
+               dl_models/vqvae.py:522-531; --arch aenet / diffunet: from --filters; --arch diffvae: the model of diff_vae.py:476-485)
 --data         a directory of .npz files, one test batch each: spec_in, spec_out fp32 [B, H, W, 2] (or [B, 2, H, W]), emb int
                [B, 2, 16], wav_true fp32 [B, T], room = B room names (or indices into evaluate.ROOMS)
 --dataset      the impulse-response tree DIR/NAME/Room/ZoneX/...Array/*.wav itself: the test partition of `unet_rir_amd.Dataset`
@@ -32,11 +32,15 @@ from unet_rir_amd.features import PostProcess
 
 
 def build_model(a, dev):
-    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder, "vae": U.VAE, "vqvae": U.VQVAE, "aenet": U.AENet}[a.arch]
+    cls = {"unet": U.UNet, "resae": U.ResAE, "ae": U.Autoencoder, "vae": U.VAE, "vqvae": U.VQVAE, "aenet": U.AENet,
+           "diffunet": U.DiffUNet, "diffvae": U.DiffVAE}[a.arch]
     if a.load:
         return cls.load(a.load, batch_size=a.batch, device=dev)
-    if a.arch in ("vae", "vqvae"):
-        if a.arch == "vae":    # as rir_generation.py:78-87 builds it (latent 32 there, 64 in main_training.py:143-152: --latent)
+    if a.arch in ("vae", "vqvae", "diffvae"):
+        if a.arch == "diffvae":    # the model of dl_models/diff_vae.py's own __main__ block (:476-485); score it with --diff-gen
+            m = U.DiffVAE((a.height, a.width, 2), (2, 16), conv_filters=(32, 64, 128, 256), conv_kernels=(3, 3, 3, 3),
+                          conv_strides=(2, 2, 2, 2), latent_space_dim=16, n_neurons=20 * 64, batch_size=a.batch, device=dev, dropout=False)
+        elif a.arch == "vae":    # as rir_generation.py:78-87 builds it (latent 32 there, 64 in main_training.py:143-152: --latent)
             m = U.VAE((a.height, a.width, 2), (2, 16), conv_filters=(64, 128, 256, 512), conv_kernels=(3, 3, 3, 3),
                       conv_strides=(2, 2, 2, 2), latent_space_dim=a.latent, n_neurons=32 * 64, name=a.name, batch_size=a.batch, device=dev,
                       dropout=False)
@@ -51,9 +55,12 @@ def build_model(a, dev):
             mgr.restore()
             print("restored", mgr.latest_checkpoint)
         return m
-    if a.arch not in ("unet", "aenet"):
-        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net, an AENet, a VAE or a VQ-VAE; use --load for the other autoencoders")
-    if a.arch == "aenet":
+    if a.arch not in ("unet", "aenet", "diffunet"):
+        raise SystemExit("--checkpoint and --synthetic without --load build a U-Net, an AENet, a DiffUNet, a VAE, a DiffVAE or a VQ-VAE; "
+                         "use --load for the other autoencoders")
+    if a.arch == "diffunet":       # score it with --diff-gen (rir_generation.py:51-63)
+        m = U.DiffUNet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, batch_size=a.batch, device=dev, dropout=False)
+    elif a.arch == "aenet":
         m = U.AENet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, batch_size=a.batch, device=dev, dropout=False)
     else:
         m = U.UNet((a.height, a.width, 2), (2, 16), number_filters_0=a.filters, kernels=a.kernels, batch_size=a.batch, device=dev,
@@ -100,7 +107,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--load")
     ap.add_argument("--checkpoint")
-    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae", "vqvae", "aenet"), default="unet")
+    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae", "vqvae", "aenet", "diffunet", "diffvae"), default="unet")
     ap.add_argument("--latent", type=int, default=32, help="latent_space_dim of --arch vae built without --load")
     ap.add_argument("--filters", type=int, default=32)
     ap.add_argument("--kernels", type=int, default=3)

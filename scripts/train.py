@@ -37,6 +37,11 @@ def build_model(a, dev):
                        latent_space_dim=16, n_neurons=320, name=a.name, **common)
     if a.name == "aenet":      # dl_models/ae_net.py with its defaults (rir_generation.py:6 imports it; main_training.py has no branch)
         return U.AENet(shape, (2, 16), number_filters_0=a.filters, name="AENet", **common)
+    if a.name == "diffunet":   # dl_models/diff_u_net.py with its defaults (rir_generation.py:51-63: the 'unet_diff_full' model); add --diff-loss
+        return U.DiffUNet(shape, (2, 16), number_filters_0=a.filters, name="U-Net", **common)
+    if a.name == "diffvae":    # the model of dl_models/diff_vae.py's own __main__ block (:476-485); add --diff-loss
+        return U.DiffVAE(shape, (2, 16), conv_filters=(32, 64, 128, 256), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
+                         latent_space_dim=16, n_neurons=20 * 64, name="Diff_VAE", **common)
     return U.UNet(shape, (2, 16), mode=0, number_filters_0=a.filters, kernels=a.kernels, name="U-Net", **common)
 
 
@@ -49,7 +54,7 @@ def main():
     ap.add_argument("--arrays", nargs="+", default=["PlanarMicrophoneArray", "CircularMicrophoneArray"])
     ap.add_argument("--no-debug", action="store_true", help="load the whole tree (main_training.py runs with debug = True)")
     ap.add_argument("--extract", action="store_true", help="unpack the zone archives first")
-    ap.add_argument("--name", choices=("ae", "resae", "vae", "vqvae", "aenet", "unet"), default="unet")
+    ap.add_argument("--name", choices=("ae", "resae", "vae", "vqvae", "aenet", "diffunet", "diffvae", "unet"), default="unet")
     ap.add_argument("--filters", type=int, default=32, help="number_filters_0 of the U-Net")
     ap.add_argument("--kernels", type=int, default=3)
     ap.add_argument("--height", type=int, default=144)
@@ -80,7 +85,9 @@ def main():
         model = build_model(a, dev)
         trainer = U.Trainer(model, lr=a.lr, alpha=a.alpha, sigmoid_loss=a.sigmoid_loss, diff_loss=a.diff_loss, beta=a.beta,
                             optimizer=a.optimizer)
-        history = U.fit(trainer, lambda epoch: batches, a.epochs, None, lr0=a.lr, lr_exp_decay=(not a.no_lr_decay, a.decay_from))
+        manager = U.CheckpointManager(trainer, a.out, max_to_keep=2)          # every second epoch, as with a data set
+        history = U.fit(trainer, lambda epoch: batches, a.epochs, None, manager=manager, lr0=a.lr,
+                        lr_exp_decay=(not a.no_lr_decay, a.decay_from))
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "history.json"), "w") as f:
             json.dump(history, f, indent=1)

@@ -57,6 +57,17 @@ class AEFamilyEngine(GraphEngine):
             vec = self._dropout(vec, dropout)
         return self._concat(x, vec)
 
+    def _join_vector_per_position(self, x: Node, name, vocab, dim):
+        """concatenate([Flatten(x), Flatten(y)]) with y = Embedding(vocab, dim) -> Dense(n_neurons) `name` on the UNFLATTENED
+        [B, *inf_vector_shape, dim] tensor, i.e. per position: a 1x1 convolution over the positions with a Dense layer's Keras
+        layout; no Dropout; Flatten at the join (vqvae.py:445-455, :505; diff_vae.py:416-417, :463-465)."""
+        self.shape_before_bottleneck = (x.a.H, x.a.W, x.a.C)
+        e = self._reshape(self._embedding(self.n_idx, vocab=vocab, dim=dim), 1, self.n_idx, dim)
+        v = self._conv(e, name, self.n_neurons, 1, 1, followed_by_bn=False, l2=False)
+        (kspec,) = [s_ for s_ in self.specs_fwd if s_.name == name + ".kernel"]
+        kspec.kind, kspec.keras_shape = "dense", (dim, self.n_neurons)
+        return self._concat(x, self._reshape(v, 1, 1, self.n_idx * self.n_neurons))
+
     def _decoder_entry(self, z: Node):
         """model.encoder ends at `z`; the decoder opens with Dense -> Dropout -> Reshape (autoencoder.py:245-265, res_ae.py:247-268,
         vae.py:294-313)."""

@@ -458,10 +458,13 @@ __global__ void nchw_to_nhwc_pad_kernel(const float* __restrict__ x, int B, int 
 __device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 // The output activation of the loss / inference / bridge kernels below.  ACT 0: sigmoid (dl_models/u_net.py:249).  ACT 1: the clipped
 // ReLU relu(out, max_value=1) of dl_models/ae_net.py:249: pred = min(max(z, 0), 1), d pred / d z = 1 where 0 < z < 1, else 0 - which
-// the stored prediction tells as well (0 < pred < 1), so the bridge kernel needs no logits.
-template <int ACT> __device__ __forceinline__ float out_act(float z) { return ACT ? fminf(fmaxf(z, 0.f), 1.f) : sigmoidf_(z); }
+// the stored prediction tells as well (0 < pred < 1), so the bridge kernel needs no logits.  ACT 2: the linear output of the
+// phase-difference models (dl_models/diff_u_net.py:247, diff_vae.py:385): pred = z, d pred / d z = 1.
+template <int ACT> __device__ __forceinline__ float out_act(float z) { return ACT == 2 ? z : ACT ? fminf(fmaxf(z, 0.f), 1.f) : sigmoidf_(z); }
 // g * d pred / d logit, the sigmoid's product in the order it always had: (g * p) * (1 - p)
-template <int ACT> __device__ __forceinline__ float out_dact(float g, float p) { return ACT ? ((p > 0.f && p < 1.f) ? g : 0.f) : g * p * (1.f - p); }
+template <int ACT> __device__ __forceinline__ float out_dact(float g, float p) {
+    return ACT == 2 ? g : ACT ? ((p > 0.f && p < 1.f) ? g : 0.f) : g * p * (1.f - p);
+}
 
 // phase_ref (nullable): the network INPUT, NCHW - the `diff_loss` switch of main_training.py:214-217 (phase target = phase_true -
 // phase_x).  phase_w (nullable): [W] column weights of the phase term - the `sigmoid_loss` switch (:221-222, preprocess.py:116-121).
@@ -1189,6 +1192,42 @@ int unetrir_relu1_bwd_f32(const float* pred, const float* dpred, int B, int H, i
 int unetrir_relu1_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits, unetrir_stream_t stream) {
     if (!pred || !dpred || !dlogits || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
     hipLaunchKernelGGL((sigmoid_bwd_kernel<__bf16, 1>), dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
+                       dpred, B, H, W, (__bf16*)dlogits, 8);
+    return (int)hipGetLastError();
+}
+
+/* the linear output of dl_models/diff_u_net.py:247 and diff_vae.py:385: the three kernels above with ACT = 2 */
+int unetrir_linear_loss_ex_f32(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                              int B, int H, int W, float alpha, float inv_norm, float* pred, float* dlogits, float* loss_out,
+                              void* ws, size_t ws_bytes, unetrir_stream_t stream) {
+    return sigmoid_loss_impl<float, 2>(logits, ldl, target, B, H, W, alpha, inv_norm, pred, dlogits, 4, loss_out, ws, ws_bytes,
+                                       (hipStream_t)stream, phase_ref, phase_weight);
+}
+
+int unetrir_linear_loss_ex_bf16(const float* logits, int ldl, const float* target, const float* phase_ref, const float* phase_weight,
+                               int B, int H, int W, float alpha, float inv_norm, float* pred, unetrir_bf16* dlogits, float* loss_out,
+                               void* ws, size_t ws_bytes, unetrir_stream_t stream) {
+    return sigmoid_loss_impl<__bf16, 2>(logits, ldl, target, B, H, W, alpha, inv_norm, pred, (__bf16*)dlogits, 8, loss_out, ws, ws_bytes,
+                                        (hipStream_t)stream, phase_ref, phase_weight);
+}
+
+int unetrir_linear_nchw_f32(const float* logits, int ldl, int B, int H, int W, float* pred, unetrir_stream_t stream) {
+    if (!logits || ldl < 2 || !pred || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL(sigmoid_only_kernel<2>, dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, logits,
+                       ldl, B, H, W, pred);
+    return (int)hipGetLastError();
+}
+
+int unetrir_linear_bwd_f32(const float* pred, const float* dpred, int B, int H, int W, float* dlogits, unetrir_stream_t stream) {
+    if (!pred || !dpred || !dlogits || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL((sigmoid_bwd_kernel<float, 2>), dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
+                       dpred, B, H, W, dlogits, 4);
+    return (int)hipGetLastError();
+}
+
+int unetrir_linear_bwd_bf16(const float* pred, const float* dpred, int B, int H, int W, unetrir_bf16* dlogits, unetrir_stream_t stream) {
+    if (!pred || !dpred || !dlogits || B <= 0 || H <= 0 || W <= 0) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL((sigmoid_bwd_kernel<__bf16, 2>), dim3(grid_for((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, pred,
                        dpred, B, H, W, (__bf16*)dlogits, 8);
     return (int)hipGetLastError();
 }

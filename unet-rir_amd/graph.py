@@ -34,7 +34,14 @@ class Node:
 
 class GraphEngine(EngineBase):
     mask_on_side_stream = False      # the dropout masks are consumed by nodes of the main stream (trainer.Trainer._make_mask)
-    output_act = "sigmoid"           # the output activation fused into the loss kernel: "sigmoid" | "relu1" (dl_models/ae_net.py:249)
+    # the output activation fused into the loss kernel: "sigmoid" | "relu1" (dl_models/ae_net.py:249) | "linear" (diff_u_net.py:247)
+    output_act = "sigmoid"
+
+    def _out_op(self, what):
+        """ops.<output_act>_<what>: the loss kernel, the inference form or the autograd bridge of this engine's output activation."""
+        if self.output_act not in ("sigmoid", "relu1", "linear"):
+            raise ValueError(f"unknown output activation {self.output_act!r}")
+        return getattr(ops, f"{self.output_act}_{what}")
 
     def __init__(self, B, device="cuda:0", n_replicas=1, runtime=None, share=None, dtype="f32", overlap_wgrad=False):
         """dtype: storage type of the trunk ("f32" or "bf16").
@@ -46,6 +53,7 @@ class GraphEngine(EngineBase):
         super().__init__(device, n_replicas, dtype, runtime, share)
         self._h_kernels = []                           # kernels of the convolutions that run in bf16 (work copies needed)
         self.c22_passes = {}                           # layer name -> passes served by the 2x2 stride-2 kernels (_conv2x2)
+        self.head_passes = 0                           # passes of a 1x1 head served by csrc/head1x1.hip (_head1x1)
         self._s2_kernels = []                          # 3x3 stride-2 kernels among them
         self._share = share
         self.include_reg = True       # backward adds d/dw of the l2 terms (False: the caller differentiates them itself)
@@ -280,6 +288,50 @@ class GraphEngine(EngineBase):
         self._push(fwd, bwd)
         return y
 
+    def _head1x1(self, x: Node, name, generic=False):
+        """Conv2D(2, (1, 1), activation='linear') (dl_models/diff_u_net.py:247).  fp32 trunk: an ordinary conv node with the 2 output
+        channels padded to 4.  bf16 trunk: the passes ops.head1x1_supported offers run on csrc/head1x1.hip - bf16 activations in,
+        fp32 logits [.., 4] out; bf16 dL/dlogits [.., 8] back, the whole backward pass in one sweep - and the others (generic=True:
+        all of them) on the tap-table kernels with the padded kernel, whose forward pass stores bf16 logits [.., 8]."""
+        if x.a.sfx == "f32":
+            return self._conv(x, name, 2, 1, 1, followed_by_bn=False, pad_out=4, l2=False)
+        B, H, W, c, PAD = self.B, x.a.H, x.a.W, x.a.C, self.PAD
+        m = 0 if generic else ops.head1x1_supported(c)
+        self.head_passes = m
+        kname, bname = name + ".kernel", name + ".bias"
+        self._param(kname, (PAD, 1, 1, c), "conv_padout", (1, 1, c, 2))
+        self._param(bname, (PAD,), "bias_pad", (2,))
+        self._h_kernels.append(kname)
+        ya = ops.new_act(B, H, W, 4, self.device) if m & ops.H1_FWD else ops.new_act(B, H, W, PAD, self.device, dtype=self.adt)
+        y = self._reg(Node(ya, True, ops.new_act(B, H, W, PAD, self.device, dtype=self.adt)))
+        g = ops.geom(B, H, W, c, PAD, 1, 1)
+        if m & ops.H1_BWD:
+            # one sweep writes dx (no addend) together with dw and dbias: the head must be the first writer of a gradient that exists
+            if not x.needs_grad or x.children:
+                raise ValueError("the 1x1 head's backward kernel writes its input's whole gradient: the input must need one and have no views")
+            self.ws.reserve(ops.head1x1_bwd_ws_bytes(B, H, W, c))
+
+        def fwd():
+            if m & ops.H1_FWD:
+                ops.head1x1_fwd(x.a, self.p[kname], self.p[bname], y.a)
+            else:
+                ops.conv2d_fwd(g, x.a, self.ph[kname], self.p[bname], y.a)
+
+        def bwd():
+            if m & ops.H1_BWD:
+                # one sweep writes dx, dw and dbias: on the main stream, which the data gradient is on anyway
+                if x.g_set:
+                    raise NotImplementedError("the 1x1 head is the only consumer of its input")
+                ops.head1x1_bwd(x.a, y.g, self.p[kname], x.g, self.g[kname], self.g[bname], self.ws)
+                x.g_set = True
+                return
+            with self._wg() as ws_:
+                ops.conv2d_wgrad(g, x.a, y.g, self.g[kname], ws_, w=self.p[kname], defer=self._rb if self.park_reduces else None)
+                ops.colsum(y.g, self.g[bname], ws_)
+            self._emit(x, lambda dst, add: ops.conv2d_dgrad(g, y.g, self.pth[kname], dst, addend=add))
+        self._push(fwd, bwd)
+        return y
+
     def _bn_act(self, x: Node, name, act, addend: Node = None, out: Node = None, batchnorm=True):
         """BatchNormalization (+ Add) (+ activation).  x must have this op as its only consumer."""
         c = x.a.C
@@ -456,7 +508,7 @@ class GraphEngine(EngineBase):
         self.include_reg = include_reg
         if dpred is not None:
             self._check_batch(dpred, "dpred")
-            (ops.relu1_bwd if self.output_act == "relu1" else ops.sigmoid_bwd)(self.pred, dpred, self.logits.g)
+            self._out_op("bwd")(self.pred, dpred, self.logits.g)
             self.logits.g_set = True
         for (_, bwd), end in zip(reversed(self.ops), reversed(self._op_ends)):
             bwd()
@@ -479,9 +531,9 @@ class GraphEngine(EngineBase):
             la = self._logits32
         if target is not None:
             gb = self.B if global_batch is None else global_batch
-            (ops.relu1_loss if self.output_act == "relu1" else ops.sigmoid_loss)(
+            self._out_op("loss")(
                 la, target, alpha, 1.0 / (2.0 * self.H * self.W * gb), self.pred, logits.g, self.loss_out, self.ws, **self._loss_extras())
             logits.g_set = True
         else:
-            (ops.relu1_nchw if self.output_act == "relu1" else ops.sigmoid_nchw)(la, self.pred)
+            self._out_op("nchw")(la, self.pred)
         return self.pred

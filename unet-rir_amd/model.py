@@ -39,6 +39,8 @@ from . import ops
 from .device import HipRuntime
 from .ae import AutoencoderEngine
 from .aenet import AENetEngine
+from .diffunet import DiffUNetEngine
+from .diffvae import DiffVAEEngine
 from .engine import L2_COEF, UNetEngine
 from .resae import ResAEEngine
 from .unet_graph import UNetGraphEngine
@@ -416,6 +418,26 @@ class AENet(UNet):
         return ue
 
 
+class DiffUNet(AENet):
+    """DiffUNet of the reference (dl_models/diff_u_net.py:34-62), the generator that predicts a phase difference: AENet's skeleton
+    with the U-Net's `Add` join of a Dense information vector, Dropout(.5) and a LINEAR two-channel 1x1 output, on
+    diffunet.DiffUNetEngine.  Constructor arguments keep the reference's names, order and defaults (:40-45; it has no `kernels`); the
+    additions are AENet's.  `compile_and_fit` (:82-83: MSE through the autograd bridge), `get_callbacks`, `summary`, `save` / `load` /
+    `load_weights`, `predict_stft` are the shared ones; `parameters.pkl` is the list of :179-186 followed by the dtype.
+    The model does not switch `diff_loss` / `diff_gen` on by itself: Trainer(diff_loss=True), Evaluator(diff_gen=True)."""
+
+    def __init__(self, input_shape, inf_vector_shape, learning_rate=1e-5, mode=0, number_filters_0=32, BatchNorm=True,
+                 resize_factor_0=None, res_factor=None, name="U-Net", batch_size=None, device="cuda:0", n_replicas=1, dropout=True,
+                 dtype="f32", overlap=False, fold_l2=True, runtime=None):
+        super().__init__(input_shape, inf_vector_shape, learning_rate, mode, number_filters_0, BatchNorm, resize_factor_0, res_factor,
+                         name, batch_size, device, n_replicas, dropout, dtype, overlap, fold_l2, runtime)
+
+    def _new_engine(self, B, share):
+        return DiffUNetEngine(self.H, self.W, B, F0=self.number_filters_0, mode=self.mode, batchnorm=self.BatchNorm,
+                              inf_vector_shape=self.inf_vector_shape, device=self._device, n_replicas=self.n_replicas, runtime=self._rt,
+                              share=share, dtype=self.dtype_name, overlap_wgrad=self.overlap)
+
+
 class _SubModel:
     """``model.encoder`` / ``model.decoder`` of the autoencoder family (dl_models/res_ae.py:62-64, main_training.py:258-259)."""
 
@@ -550,6 +572,20 @@ class VAE(_AEFamily):
         is not implemented, and fitting plain MSE under its name would be a different model."""
         raise NotImplementedError("VAE.compile_and_fit (the legacy Keras recipe with its combined loss) is not implemented: "
                                   "use Trainer / fit, the train step of main_training.py")
+
+
+class DiffVAE(VAE):
+    """DiffVAE of the reference (dl_models/diff_vae.py:42-78; its own size is the __main__ block's, :476-485: filters (32,64,128,256),
+    kernels 3, strides 2, latent_space_dim 16, n_neurons 1280), the VAE that predicts a phase difference: Embedding(1500, 128) ->
+    Dense per position on the information vector and a LINEAR output, on diffvae.DiffVAEEngine.  The surface is VAE's:
+    ``model.encoder`` returns ``(z, mean, log_var)``, ``reconstruction_loss_weight`` is kept, ``compile_and_fit`` (the combined-loss
+    Keras recipe, :99-137, :184-218) and autograd through the module raise NotImplementedError."""
+    ENGINE = DiffVAEEngine
+
+    def __init__(self, input_shape, inf_vector_shape, conv_filters, conv_kernels, conv_strides, latent_space_dim, n_neurons,
+                 name="Diff_VAE", **kw):
+        super().__init__(input_shape, inf_vector_shape, conv_filters, conv_kernels, conv_strides, latent_space_dim, n_neurons,
+                         name, **kw)
 
 
 class VQVAE(_AEFamily):

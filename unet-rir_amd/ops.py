@@ -511,6 +511,32 @@ def head6x6_wgrad(x: Act, dy: Act, dw, ws: Workspace):
                                                _stream()), "head6x6_wgrad")
 
 
+H1_FWD, H1_BWD = 1, 2       # passes in the mask head1x1_supported returns
+
+
+def head1x1_supported(C_):
+    """Passes of a Conv2D(2, (1, 1)) head with C_ input channels (bf16 trunk) that csrc/head1x1.hip serves: H1_FWD | H1_BWD."""
+    return int(_lib.lib().unetrir_head1x1_supported(int(C_)))
+
+
+def head1x1_fwd(x: Act, w, bias, y: Act):
+    """Conv2D(2, (1, 1), activation='linear') (dl_models/diff_u_net.py:247): bf16 activations in, fp32 logits [.., >=4] out; w is
+    the fp32 [>=2][C] kernel."""
+    check(_lib.lib().unetrir_head1x1_fwd_bf16(_p(x), x.ld, x.B, x.H, x.W, x.C, _p(w), _p(bias), _p(y), y.ld, _stream()), "head1x1_fwd")
+
+
+def head1x1_bwd_ws_bytes(B, H, W, C_):
+    return int(_lib.lib().unetrir_head1x1_bwd_ws_bytes(int(B), int(H), int(W), int(C_)))
+
+
+def head1x1_bwd(x: Act, dy: Act, w, dx: Act, dw, dbias, ws: Workspace):
+    """The whole backward pass of head1x1_fwd in one sweep: dx (bf16, written, no addend), rows 0, 1 of dw and entries 0, 1 of
+    dbias (fp32; the rest of the padded gradients is left as it is)."""
+    ws.reserve(head1x1_bwd_ws_bytes(x.B, x.H, x.W, x.C))
+    check(_lib.lib().unetrir_head1x1_bwd_bf16(_p(x), x.ld, _p(dy), dy.ld, x.B, x.H, x.W, x.C, _p(w), _p(dx), dx.ld, _p(dw), _p(dbias),
+                                              ws.ptr, ws.nbytes, _stream()), "head1x1_bwd")
+
+
 def head6x6_dgrad_supported(W_, C_):
     return bool(_lib.lib().unetrir_head6x6_dgrad_supported(W_, C_))
 
@@ -742,6 +768,25 @@ def relu1_nchw(logits: Act, pred):
 def relu1_bwd(pred, dpred, dlogits: Act):
     B, _, H, W = pred.shape
     check(_fn("relu1_bwd", dlogits.sfx)(_p(pred), _p(dpred), B, H, W, _p(dlogits), _stream()), "relu1_bwd")
+
+
+def linear_loss(logits: Act, target, alpha, inv_norm, pred, dlogits: Act, loss_out, ws: Workspace, phase_ref=None, phase_weight=None):
+    """Linear output (dl_models/diff_u_net.py:247, diff_vae.py:385) + compute_loss + dL/dlogits: sigmoid_loss with pred = logit
+    (same arguments, same loss_out)."""
+    B, _, H, W = target.shape
+    ws.reserve(_lib.lib().unetrir_loss_ws_bytes(B * H * W))
+    check(_fn("linear_loss_ex", dlogits.sfx)(_p(logits), logits.ld, _p(target), _p(phase_ref), _p(phase_weight), B, H, W, alpha,
+                                             inv_norm, _p(pred), _p(dlogits), _p(loss_out), ws.ptr, ws.nbytes, _stream()), "linear_loss_ex")
+
+
+def linear_nchw(logits: Act, pred):
+    B, _, H, W = pred.shape
+    check(_lib.lib().unetrir_linear_nchw_f32(_p(logits), logits.ld, B, H, W, _p(pred), _stream()), "linear_nchw")
+
+
+def linear_bwd(pred, dpred, dlogits: Act):
+    B, _, H, W = pred.shape
+    check(_fn("linear_bwd", dlogits.sfx)(_p(pred), _p(dpred), B, H, W, _p(dlogits), _stream()), "linear_bwd")
 
 
 # ---- information vector ----------------------------------------------------------------------

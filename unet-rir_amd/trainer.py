@@ -8,6 +8,7 @@ holds the full model, BatchNorm statistics stay per replica, the loss is normali
 gradients are SUM-reduced.  The collective is RCCL (torch.distributed backend "nccl") over xGMI, issued per
 bucket while the backward pass is still running.
 """
+import gc
 import os
 
 import torch
@@ -325,8 +326,21 @@ class Trainer:
             self._restore(snap)
             rt.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._step_body(*self._g_in, None, with_reg)
+            # No cyclic garbage collection inside the capture.  A trainer whose optimizer runs on its own stream is a reference cycle
+            # (trainer -> bucketer -> on_bucket, a bound method of the trainer), so a dropped one - and the CUDAGraph objects it holds
+            # - is freed whenever the collector runs.  torch's ~CUDAGraph synchronises the device on ROCm under a throwing check, a
+            # synchronisation is not permitted on a capturing thread, and an exception out of a destructor ends the process
+            # (SIGABRT, no message).  torch.cuda.graph no longer collects before a capture by itself
+            # (torch.compiler.config.force_cudagraph_gc is off), so: collect here, outside, and hold the collector until the capture ends.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    self._step_body(*self._g_in, None, with_reg)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             # the capture pass advanced the host mirrors as a step does, but ran nothing: undo it on the host only
             eng.adam_t = snap["adam_t"]
             eng._shared["dropout_step"] = snap["dropout_step"]

@@ -41,13 +41,9 @@ class VQVAEEngine(AEFamilyEngine):
             raise ValueError("the quantiser needs conv_filters[-1] % latent_space_dim == 0, 4 <= latent_space_dim <= 64, conv_filters[-1] <= 512")
         if (h * w * 2) % 4:
             raise ValueError("the bottleneck Dense(h * w * 2) needs an even number of bottleneck pixels")
-        # information vector (:445-455): Embedding -> Dense on the UNFLATTENED [B, 2, 16, 128] tensor, i.e. per position: a 1x1
-        # convolution over the positions, with a Dense layer's Keras layout; no Dropout; Flatten at the join (:505)
-        e = self._reshape(self._embedding(self.n_idx, vocab=VQ_VOCAB, dim=VQ_EMB_DIM), 1, self.n_idx, VQ_EMB_DIM)
-        v = self._conv(e, "encoder_inf_dense", self.n_neurons, 1, 1, followed_by_bn=False, l2=False)
-        (kspec,) = [s_ for s_ in self.specs_fwd if s_.name == "encoder_inf_dense.kernel"]
-        kspec.kind, kspec.keras_shape = "dense", (VQ_EMB_DIM, self.n_neurons)
-        cat = self._concat(x, self._reshape(v, 1, 1, self.n_idx * self.n_neurons))
+        # information vector (:445-455): Embedding -> Dense on the UNFLATTENED [B, 2, 16, 128] tensor, i.e. per position; no Dropout;
+        # Flatten at the join (:505)
+        cat = self._join_vector_per_position(x, "encoder_inf_dense", VQ_VOCAB, VQ_EMB_DIM)
         d = self._dropout(self._dense(cat, "dense", h * w * 2), self.MASKS[0])        # Dense(prod(shape)) -> Dropout(.3) (:508-511)
         q = self._vq(self._conv(self._pad2(d, h, w), "conv2d", c, 1, 1, followed_by_bn=False, pad_in=4, l2=False), K, D)   # (:512-518)
         self._latent, self._n_enc_ops = q, len(self.ops)                     # model.encoder ends at the quantiser's output (:434)
