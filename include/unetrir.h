@@ -656,6 +656,38 @@ int unetrir_eval_metrics_f32(const float* pred, const float* target, const float
                              const float* wav_pred, const float* wav_true, int T, int n50, double* out, unetrir_stream_t stream);
 int unetrir_eval_accumulate(const double* out, const int* group, int B, int G, double* acc, unetrir_stream_t stream);
 
+/* ---- room-acoustic figures of impulse responses: arrival of the direct sound, direct / reverberant and early / late balance, centre
+ *      time and early decay time of the predicted and the true waveform, and their errors folded per room - on the device and
+ *      without a read-back.  The waveforms are the reference's 0.2 s window (T = 9600 at 48 kHz): where a room's decay outlasts it,
+ *      c50, ts and edt are figures of the truncated response - like for like between prediction and truth, not ISO 3382 values.
+ *
+ * unetrir_acoustic_figures_f32: wav_a fp32 [B][T], wav_b nullable fp32 [B][T] (the pair predicted / true in ONE launch),
+ * fig fp64 [B][2][10], or [B][1][10] when wav_b is null.  With e = h*h in fp64, n0 = argmax |h| (lowest index on ties, |h| compared
+ * as fp32), s = max(0, n0 - n_pre) and S[n] = sum_{k >= n} e[k] (the Schroeder backward integral), a row of fig is
+ *   0 n0      1 E_tot = S[s]      2 E_dir = sum e, s <= n <= min(T-1, n0 + n_dir)      3 E_early = sum e, s <= n < min(T, s + n_early)
+ *   4 M1 = sum_{n >= s} (n - s) e[n]      5 N_fit = #{n >= s : 10 S[n] >= E_tot} (the 0 .. -10 dB stretch, contiguous from s)
+ *   6 drr = 10 log10(E_dir / (E_tot - E_dir)) dB      7 c50 = 10 log10(E_early / (E_tot - E_early)) dB
+ *   8 ts = M1 / E_tot / fs * 1e3 ms      9 edt = -60 / slope s, slope = (N SkL - Sk SL) / (N Sk2 - Sk^2) * fs the least-squares line
+ *   through L[k] = 10 log10(S[s+k] / E_tot), k = 0..N_fit-1 (Sk, Sk2 in closed form); NaN when N_fit < 2.
+ * Degenerate rows follow IEEE arithmetic: an all-zero row gives NaN, no late energy +inf dB, a flat decay curve edt = -inf.
+ * One workgroup per waveform, fp64 accumulation in a fixed order, no atomics, no workspace, one code path for every T >= 1: the same
+ * bits in every run, and a waveform's row does not depend on its batch or its place in it.
+ *
+ * unetrir_acoustic_accumulate: the errors of the B (pred = fig[b][0], true = fig[b][1]) pairs,
+ *   0 toa_ms = |n0_p - n0_t| / fs * 1e3   1 drr_db = |drr_p - drr_t|   2 c50_db = |c50_p - c50_t|   3 ts_ms = |ts_p - ts_t|
+ *   4 edt_pct = 100 |edt_p - edt_t| / edt_t,
+ * into err fp64 [B][5] (nullable; the IEEE value whether it counts or not) and folded into acc fp64 [(G+1)][20] (in/out; row 0
+ * global, rows 1..G the groups; per figure four columns: sum of errors, sum of pred values, sum of true values, count; for toa the
+ * values are n0 / fs * 1e3).  A figure of a pair counts only when both sides are finite - edt: and both > 0 - and the other figures
+ * of that pair still count.  group int32 [B]: 0..G-1; any other value counts in the global row only.  One workgroup, batch walked
+ * in index order.
+ *
+ * UNETRIR_EINVAL before the device is touched: a null required pointer, B <= 0, T <= 0, a negative window, fs <= 0, G < 0. */
+int unetrir_acoustic_figures_f32(const float* wav_a, const float* wav_b, int B, int T, int n_pre, int n_dir, int n_early, double fs,
+                                 double* fig, unetrir_stream_t stream);
+int unetrir_acoustic_accumulate(const double* fig, const int* group, int B, int G, double fs, double* err, double* acc,
+                                unetrir_stream_t stream);
+
 /* ---- glue that would otherwise be framework kernels inside the step.
  * bn_inference_affine: BatchNormalization with training=False (rir_generation.py:165): scale = gamma * rsqrt(moving_var + eps),
  *   shift = beta - moving_mean * scale into affine[2*C] (gamma / beta NULL = 1 / 0), consumed by unetrir_bn_apply_*.

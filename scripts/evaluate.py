@@ -17,6 +17,8 @@
 --synthetic N  N batches of `synthetic_batches`, which yields no waveforms: wav_true is the reconstruction of spec_out
 --algorithm    ph (default): reconstruct from the predicted phase; gl: Griffin-Lim from the predicted magnitude
                (rir_generation.py:62, :137; --gl-iters, --gl-momentum, --gl-seed)
+--acoustics    also score the room-acoustic figures (arrival of the direct sound, direct-to-reverberant ratio, C50, centre time,
+               early decay time) of predicted against true waveform and write a fourth file, NAME_acoustics.csv
 """
 import argparse
 import glob
@@ -124,6 +126,7 @@ def main():
     ap.add_argument("--gl-iters", type=int, default=32)
     ap.add_argument("--gl-momentum", type=float, default=0.99)
     ap.add_argument("--gl-seed", type=int, default=0)
+    ap.add_argument("--acoustics", action="store_true")
     ap.add_argument("--out", required=True)
     ap.add_argument("--name", default="unet")
     a = ap.parse_args()
@@ -134,13 +137,15 @@ def main():
     dev = torch.device("cuda:0")
     model = build_model(a, dev)
     ev = U.Evaluator(model, diff_gen=a.diff_gen, algorithm=a.algorithm, gl_iters=a.gl_iters, gl_momentum=a.gl_momentum,
-                     gl_seed=a.gl_seed)
+                     gl_seed=a.gl_seed, acoustics=a.acoustics)
     for batch in (file_batches(a.data, dev) if a.data else dataset_batches(a, dev) if a.dataset else synthetic(a, dev)):
         ev.update(*batch)
     res = ev.result()
     for p in U.write_report(res, a.out, a.name):
         print("wrote", p)
     print("samples", res["n"][0], " ".join(f"{m}={res[m][0]:.6g}" for m in U.evaluate.METRICS))
+    if a.acoustics:
+        print("acoustics", " ".join(f"{m}={v['err'][0]:.6g} (n={v['n'][0]})" for m, v in res["acoustics"].items()))
 
 
 if __name__ == "__main__":

@@ -17,9 +17,9 @@ from .unet_graph import UNetGraphEngine  # noqa: F401
 from .vae import VAEEngine  # noqa: F401
 from .vqvae import VQVAEEngine  # noqa: F401
 from .data import DeviceBatchPipeline, synthetic_batches  # noqa: F401
-from .evaluate import Evaluator, score, write_report  # noqa: F401
+from .evaluate import Evaluator, acoustics, score, write_report  # noqa: F401
 from .dataset import DataGenerator, Dataset, read_wav  # noqa: F401
 from .lamb import LAMB  # noqa: F401
 from .trainer import CheckpointManager, GradBucketer, Trainer, fit, lr_schedule  # noqa: F401
 
-__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "DiffUNet", "DiffUNetEngine", "DiffVAE", "DiffVAEEngine", "HipRuntime", "Trainer", "LAMB", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "write_report", "Dataset", "DataGenerator", "read_wav"]
+__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "DiffUNet", "DiffUNetEngine", "DiffVAE", "DiffVAEEngine", "HipRuntime", "Trainer", "LAMB", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "acoustics", "write_report", "Dataset", "DataGenerator", "read_wav"]

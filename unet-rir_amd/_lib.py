@@ -188,6 +188,10 @@ _SIGS = {
     "unetrir_eval_metrics_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int,
                                            C.c_void_p, c_stream]),
     "unetrir_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
+    # room-acoustic figures (acoustics.hip)
+    "unetrir_acoustic_figures_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                               c_stream]),
+    "unetrir_acoustic_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, c_stream]),
     "unetrir_head6x6_dgrad_supported": (C.c_int, [C.c_int, C.c_int]),
     "unetrir_head6x6_dgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int,
                                              c_stream]),

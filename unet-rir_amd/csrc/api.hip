@@ -1003,6 +1003,19 @@ int unetrir_eval_accumulate(const double* out, const int* group, int B, int G, d
     return launch_eval_accumulate(out, group, B, G, acc, (hipStream_t)stream);
 }
 
+// ---- room-acoustic figures of impulse responses (acoustics.hip): every argument is checked before the device is touched
+int unetrir_acoustic_figures_f32(const float* wav_a, const float* wav_b, int B, int T, int n_pre, int n_dir, int n_early, double fs,
+                                 double* fig, unetrir_stream_t stream) {
+    if (!wav_a || !fig || B <= 0 || T <= 0 || n_pre < 0 || n_dir < 0 || n_early < 0 || !(fs > 0.0)) return UNETRIR_EINVAL;
+    return launch_acoustic_figures(wav_a, wav_b, B, T, n_pre, n_dir, n_early, fs, fig, (hipStream_t)stream);
+}
+
+int unetrir_acoustic_accumulate(const double* fig, const int* group, int B, int G, double fs, double* err, double* acc,
+                                unetrir_stream_t stream) {
+    if (!fig || !group || !acc || B <= 0 || G < 0 || G > 0x7fffffff / 20 - 1 || !(fs > 0.0)) return UNETRIR_EINVAL;
+    return launch_acoustic_accumulate(fig, group, B, G, fs, err, acc, (hipStream_t)stream);
+}
+
 int unetrir_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_on = on != 0;

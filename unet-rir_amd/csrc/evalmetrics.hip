@@ -35,20 +35,6 @@ constexpr int EVAL_THREADS = 1024;
 constexpr int EVAL_WAVES = EVAL_THREADS / 64;
 constexpr int EVAL_NSUM = 7;
 
-// four consecutive floats from element i of a row of n: one 128-bit load when allowed, bounds-checked scalars otherwise (zeros
-// past the end; the callers mask those lanes out)
-__device__ __forceinline__ float4 ld_group(const float* __restrict__ p, long long i, long long n, bool vec) {
-    if (vec && i + 4 <= n) return *reinterpret_cast<const float4*>(p + i);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i + 0 < n) v.x = p[i + 0];
-    if (i + 1 < n) v.y = p[i + 1];
-    if (i + 2 < n) v.z = p[i + 2];
-    if (i + 3 < n) v.w = p[i + 3];
-    return v;
-}
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 __global__ __launch_bounds__(EVAL_THREADS) void eval_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                                     const float* __restrict__ phase_ref, int H, int W,
                                                                     const float* __restrict__ wav_pred,

@@ -250,7 +250,27 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
     return z ^ (z >> 31);
 }
 
+// the row fetch of the scoring kernels (evalmetrics.hip, acoustics.hip):
+// four consecutive floats from element i of a row of n: one 128-bit load when allowed, bounds-checked scalars otherwise (zeros
+// past the end; the callers mask those lanes out)
+__device__ __forceinline__ float4 ld_group(const float* __restrict__ p, long long i, long long n, bool vec) {
+    if (vec && i + 4 <= n) return *reinterpret_cast<const float4*>(p + i);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i + 0 < n) v.x = p[i + 0];
+    if (i + 1 < n) v.y = p[i + 1];
+    if (i + 2 < n) v.z = p[i + 2];
+    if (i + 3 < n) v.w = p[i + 3];
+    return v;
+}
+
+__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // scoring of generated impulse responses (evalmetrics.hip); arguments are validated by the entry points in api.hip
 int launch_eval_metrics(const float* pred, const float* target, const float* phase_ref, int B, int H, int W, const float* wav_pred,
                         const float* wav_true, int T, int n50, double* out, hipStream_t s);
 int launch_eval_accumulate(const double* out, const int* group, int B, int G, double* acc, hipStream_t s);
+
+// room-acoustic figures of impulse responses (acoustics.hip); arguments are validated by the entry points in api.hip
+int launch_acoustic_figures(const float* wav_a, const float* wav_b, int B, int T, int n_pre, int n_dir, int n_early, double fs,
+                            double* fig, hipStream_t s);
+int launch_acoustic_accumulate(const double* fig, const int* group, int B, int G, double fs, double* err, double* acc, hipStream_t s);

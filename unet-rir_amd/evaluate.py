@@ -17,6 +17,14 @@ produces them (the rule of `PostProcess.post_process`); waveforms are fp32 `[B, 
 the GPU or the calls raise `ValueError`.  `algorithm` selects the reconstruction that is scored, as the reference's argument of
 that name does (rir_generation.py:62, :137): 'ph' from the predicted phase (`features.PostProcess`), 'gl' by Griffin-Lim from
 the predicted magnitude alone (`features.GriffinLim`).
+
+Opt-in, `Evaluator(acoustics=True)` adds what a listener asks of a generated response: does the direct sound arrive on time, is the
+direct / reverberant and the early / late balance right, does the energy decay at the room's rate.  `ops.acoustic_figures` takes
+the figures of `ACOUSTIC_FIGURES` from the predicted and the true waveform in one launch, `ops.acoustic_accumulate` folds the
+errors of `ACOUSTIC_ERRORS` per room next to the other running sums; `result()` gains the key "acoustics" and `write_report` a
+fourth file.  The waveforms are the reference's 0.2 s window: where a room's decay outlasts it, `c50`, `ts` and `edt` are figures
+of the truncated response - like for like between prediction and truth, not ISO 3382 values (which is also why there is no
+T20 / T30).
 """
 import csv
 import os
@@ -27,10 +35,17 @@ import torch
 
 from . import ops
 from .features import HOP_LENGTH, N_FFT, STFT_SHAPE, WIN_LENGTH, GriffinLim, PostProcess
+from .rooms import UTS_ROOMS
 
 ROOMS = ("HemiAnechoicRoom", "LargeMeetingRoom", "MediumMeetingRoom", "ShoeBoxRoom", "SmallMeetingRoom")
 METRICS = ("mse_spec", "mse_amp", "phase", "mis_amp", "mse_wav", "mse_wav50", "mis_wav")
+# a row of `acoustics`: the peak index, four energy sums and the length of the 0 .. -10 dB stretch (the "raw" columns), then
+# direct-to-reverberant ratio and clarity in dB, centre time in ms, early decay time in s
+ACOUSTIC_FIGURES = ("n0", "e_tot", "e_dir", "e_early", "m1", "n_fit", "drr", "c50", "ts", "edt")
+# errors of a (pred, true) pair: time of arrival in ms, drr and c50 in dB, centre time in ms, early decay time in percent of the truth
+ACOUSTIC_ERRORS = ("toa_ms", "drr_db", "c50_db", "ts_ms", "edt_pct")
 
+# (pinned by tests/test_evaluate.py; `acoustics` and its two name tuples are imported by name)
 __all__ = ["ROOMS", "METRICS", "score", "Evaluator", "write_report"]
 
 
@@ -76,6 +91,21 @@ def score(pred, target, wav_pred=None, wav_true=None, phase_ref=None, n50=2400, 
     return out
 
 
+def acoustics(wav_pred, wav_true=None, n_pre=120, n_dir=120, n_early=2400, fs=48000):
+    """The room-acoustic figures of every waveform of a batch -> fp64 [B, 2, 10] on the device (pred, true), or [B, 1, 10] without
+    `wav_true`; columns in the order of `ACOUSTIC_FIGURES`.  With e = h*h in fp64: n0 = argmax |h| (the direct sound), s = max(0, n0 -
+    n_pre), S[n] = sum_{k >= n} e[k] (the Schroeder backward integral), E_tot = S[s], E_dir over s .. n0 + n_dir, E_early over s ..
+    s + n_early - 1, M1 = sum (n - s) e[n], N_fit = #{n >= s: 10 S[n] >= E_tot}; drr = 10 log10(E_dir / (E_tot - E_dir)), c50 the same
+    of E_early, ts = M1 / E_tot / fs in ms, edt = -60 / (slope of the least-squares line through 10 log10(S[s+k] / E_tot), k <
+    N_fit, in dB/s).  The defaults are 2.5 ms, 2.5 ms and 50 ms at 48 kHz.  Degenerate rows follow IEEE arithmetic (an all-zero
+    row gives NaN, no late energy +inf dB).  Nothing is read back."""
+    wp = _dense(_wav(wav_pred, "wav_pred"))
+    wt = None if wav_true is None else _dense(_wav(wav_true, "wav_true"))
+    fig = torch.empty((wp.shape[0], 1 if wt is None else 2, len(ACOUSTIC_FIGURES)), dtype=torch.float64, device=wp.device)
+    ops.acoustic_figures(wp, wt, fig, n_pre, n_dir, n_early, fs)
+    return fig
+
+
 class Evaluator:
     """The loop body of rir_generation.py:160-293 for whole batches, with the per-room lists (:143-153) replaced by running
     sums on the device.
@@ -86,13 +116,17 @@ class Evaluator:
     of `rooms` or an integer tensor of indices into it, on the device; anything else counts in the global figures only.
     `algorithm` 'gl' (:176-178 with algorithm='gl'): the waveform comes from `GriffinLim(gl_iters, gl_momentum, seed=gl_seed)` on
     the predicted magnitude; the phase plane - and `diff_gen`'s sum - still feed the phase figure but not the waveform.
+    `acoustics=True` adds the room-acoustic errors of `ACOUSTIC_ERRORS` (windows `n_pre`, `n_dir`, `n_early` in samples at `fs`, see
+    `acoustics`) of every batch that comes with its waveform pair: two more launches behind the accumulation, inside the scoring
+    stage's time, and their running sums share the one read-back.
 
     Between construction and `result()` nothing waits for the device.  The running sums, the [B, 7] figures, the waveform
     buffer and the layout staging buffers are allocated for the first batch and reused while the batch size holds.  Stage
     times come from HIP events recorded on the stream and are read in `result()`."""
 
     def __init__(self, model, diff_gen=False, rooms=ROOMS, n50=2400, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH,
-                 hop_length=HOP_LENGTH, algorithm="ph", gl_iters=32, gl_momentum=0.99, gl_seed=0):
+                 hop_length=HOP_LENGTH, algorithm="ph", gl_iters=32, gl_momentum=0.99, gl_seed=0, acoustics=False, n_pre=120, n_dir=120,
+                 n_early=2400, fs=48000):
         self.model, self.diff_gen, self.rooms, self.n50 = model, bool(diff_gen), tuple(rooms), int(n50)
         if not self.rooms:
             raise ValueError("at least one room")
@@ -102,7 +136,12 @@ class Evaluator:
         self.des_shape, self.n_fft, self.win_length, self.hop_length = tuple(des_shape), n_fft, win_length, hop_length
         self._index = {r: i for i, r in enumerate(self.rooms)}
         self._post = PostProcess(algorithm="ph") if algorithm == "ph" else GriffinLim(gl_iters, gl_momentum, seed=gl_seed)
+        self.acoustics, self.n_pre, self.n_dir, self.n_early, self.fs = bool(acoustics), int(n_pre), int(n_dir), int(n_early), float(fs)
+        if min(self.n_pre, self.n_dir, self.n_early) < 0 or not self.fs > 0:
+            raise ValueError("n_pre, n_dir and n_early are sample counts >= 0 and fs is positive")
         self._acc = None
+        self._sums = None           # with acoustics: the running sums of both kinds in one buffer, so that one copy reads them back
+        self._aacc = None
         self._buf = {}              # name -> kept device buffer
         self._pinned = []           # [pinned int32 buffer, event of the last copy out of it]
         self._events = []           # per batch: (B, start, after inference, after reconstruction, after scoring); None = not run
@@ -197,9 +236,19 @@ class Evaluator:
         g = self._group(room, B, dev)
         out = self._kept("out", (B, 7), torch.float64, dev)
         if self._acc is None:
-            self._acc = torch.zeros((len(self.rooms) + 1, 8), dtype=torch.float64, device=dev)
+            if self.acoustics:
+                rows = len(self.rooms) + 1
+                self._sums = torch.zeros((rows * (8 + 4 * len(ACOUSTIC_ERRORS)),), dtype=torch.float64, device=dev)
+                self._acc = self._sums[:rows * 8].view(rows, 8)
+                self._aacc = self._sums[rows * 8:].view(rows, 4 * len(ACOUSTIC_ERRORS))
+            else:
+                self._acc = torch.zeros((len(self.rooms) + 1, 8), dtype=torch.float64, device=dev)
         ops.eval_metrics(p, t, out, wp, wt, r, self.n50)
         ops.eval_accumulate(out, g, self._acc)
+        if self.acoustics and wp is not None:
+            fig = self._kept("fig", (B, 2, len(ACOUSTIC_FIGURES)), torch.float64, dev)
+            ops.acoustic_figures(wp, wt, fig, self.n_pre, self.n_dir, self.n_early, self.fs)
+            ops.acoustic_accumulate(fig, g, self._aacc, self.fs)
         ev[3].record()
         self._events.append((B, ev))
 
@@ -208,10 +257,17 @@ class Evaluator:
         """{"rooms": names, "n": [global, room0, ...], <metric>: [global, room0, ...] for each of `METRICS`, "timing": {...}}.
         Means are Python floats; a room without samples gives NaN, as np.mean([]) does in the reference (:319-357).  Stage times
         are seconds: inference per batch, reconstruction and scoring per sample (the reference's units, :164-181, :292-293),
-        each averaged without the first batch (:359-361); NaN for a stage that never ran or ran once."""
+        each averaged without the first batch (:359-361); NaN for a stage that never ran or ran once.  With `acoustics=True` also
+        "acoustics": {<error>: {"err": [...], "pred": [...], "true": [...], "n": [...]} for each of `ACOUSTIC_ERRORS`}, each list
+        [global, room0, ...]: the mean error, the mean predicted and true value of the figure, and the number of pairs in which the
+        figure counted (both sides finite; edt: and positive) - NaN means where that is 0."""
         G = len(self.rooms)
+        aacc = np.zeros((G + 1, 4 * len(ACOUSTIC_ERRORS)))
         if self._acc is None:
             acc = np.zeros((G + 1, 8))
+        elif self._sums is not None:
+            sums = self._sums.cpu().numpy()                    # the one synchronising copy
+            acc, aacc = sums[:(G + 1) * 8].reshape(G + 1, 8), sums[(G + 1) * 8:].reshape(G + 1, -1)
         else:
             acc = self._acc.cpu().numpy()                      # the one synchronising copy
         total = time.perf_counter() - self._t0 if self._t0 is not None else 0.0
@@ -221,6 +277,14 @@ class Evaluator:
         res = {"rooms": list(self.rooms), "n": [int(v) for v in n]}
         for k, name in enumerate(METRICS):
             res[name] = [float(v) for v in mean[:, k]]
+        if self.acoustics:
+            res["acoustics"] = {}
+            for k, name in enumerate(ACOUSTIC_ERRORS):
+                cnt = aacc[:, 4 * k + 3]
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    m = aacc[:, 4 * k:4 * k + 3] / cnt[:, None]
+                res["acoustics"][name] = {"err": [float(v) for v in m[:, 0]], "pred": [float(v) for v in m[:, 1]],
+                                          "true": [float(v) for v in m[:, 2]], "n": [int(v) for v in cnt]}
 
         def stage(i, per_sample):
             v = [e[i].elapsed_time(e[i + 1]) * 1e-3 / (B if per_sample else 1)
@@ -255,7 +319,10 @@ def _sec(v):
 
 def write_report(result, folder, name):
     """`{name}_losses.csv`, `{name}_infer_time.csv` and `{name}_results_inference.txt` in `folder`, from `Evaluator.result()`:
-    the column headers, row labels and number formats of the reference's files (:363-425).  Needs no device."""
+    the column headers, row labels and number formats of the reference's files (:363-425).  Needs no device.  A result with the key
+    "acoustics" also gives `{name}_acoustics.csv`: one row per (room, figure of `ACOUSTIC_ERRORS`) with the mean error, the mean
+    predicted and true value, the count and - for the rooms `rooms.UTS_ROOMS` knows - the room's RT60 in ms, the decay the figures
+    of that room are to be read against; numbers in full precision (`repr`)."""
     os.makedirs(folder, exist_ok=True)
     labels = ["Global"] + [_LABELS.get(r, r) for r in result["rooms"]]
     n = result["n"]
@@ -291,4 +358,15 @@ def write_report(result, folder, name):
             f.write(f"Misalignment loss (amplitude): {v['mis_amp']} (dB)\t|\t Misalignment loss (wav): {v['mis_wav']} (dB)\n")
             if i + 1 < len(labels):
                 f.write("\n")
+
+    if "acoustics" in result:
+        paths.append(os.path.join(folder, f"{name}_acoustics.csv"))
+        rt60 = [""] + [UTS_ROOMS[r][-1] if r in UTS_ROOMS else "" for r in result["rooms"]]
+        with open(paths[3], "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(["room", "figure", "mean error", "mean pred", "mean true", "n samples", "rt60 ms"])
+            for i, label in enumerate(labels):
+                for fig, v in result["acoustics"].items():
+                    w.writerow([label, fig, repr(float(v["err"][i])), repr(float(v["pred"][i])), repr(float(v["true"][i])), v["n"][i],
+                                rt60[i]])
     return paths

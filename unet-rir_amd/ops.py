@@ -663,6 +663,42 @@ def eval_accumulate(out, group, acc):
     check(_lib.lib().unetrir_eval_accumulate(_p(out), _p(group), B, acc.shape[0] - 1, _p(acc), _stream()), "eval_accumulate")
 
 
+def acoustic_figures(wav_a, wav_b, fig, n_pre=120, n_dir=120, n_early=2400, fs=48000.0):
+    """wav_a fp32 [B, T] (+ wav_b, its partner, scored in the same launch) -> fig fp64 [B, 2, 10], or [B, 1, 10] without wav_b: the
+    room-acoustic figures of each waveform (n0, E_tot, E_dir, E_early, M1, N_fit, drr, c50, ts, edt; include/unetrir.h)."""
+    if not isinstance(wav_a, torch.Tensor) or not wav_a.is_cuda or wav_a.dim() != 2:
+        raise ValueError("acoustic_figures: wav_a must be a CUDA tensor [B, T]")
+    B, T = wav_a.shape
+    _f32c(wav_a, (B, T), "wav_a", wav_a)
+    if wav_b is not None:
+        _f32c(wav_b, (B, T), "wav_b", wav_a)
+    nw = 1 if wav_b is None else 2
+    if fig.dtype != torch.float64 or not fig.is_contiguous() or tuple(fig.shape) != (B, nw, 10) or fig.device != wav_a.device:
+        raise ValueError(f"acoustic_figures: fig must be a contiguous float64 [{B}, {nw}, 10] tensor on {wav_a.device}")
+    check(_lib.lib().unetrir_acoustic_figures_f32(_p(wav_a), _p(wav_b), B, T, int(n_pre), int(n_dir), int(n_early), float(fs), _p(fig),
+                                                  _stream()), "acoustic_figures")
+
+
+def acoustic_accumulate(fig, group, acc, fs=48000.0, err=None):
+    """Fold the errors of the (pred, true) pairs fig fp64 [B, 2, 10] into the running sums acc fp64 [G + 1, 20] (row 0 global, rows
+    1..G the groups; per figure: sum of errors, of pred values, of true values, count); group int32 [B], values outside 0..G-1
+    count in the global row only.  err fp64 [B, 5], optional, receives the errors of each pair (include/unetrir.h)."""
+    if not isinstance(fig, torch.Tensor) or not fig.is_cuda or fig.dtype != torch.float64 or fig.dim() != 3 or \
+            tuple(fig.shape[1:]) != (2, 10) or not fig.is_contiguous():
+        raise ValueError("acoustic_accumulate: fig must be a contiguous float64 CUDA tensor [B, 2, 10]")
+    B = fig.shape[0]
+    if group.dtype != torch.int32 or tuple(group.shape) != (B,) or not group.is_contiguous() or group.device != fig.device:
+        raise ValueError(f"acoustic_accumulate: group must be a contiguous int32 [{B}] tensor on {fig.device}")
+    if acc.dtype != torch.float64 or acc.dim() != 2 or acc.shape[0] < 1 or acc.shape[1] != 20 or not acc.is_contiguous() or \
+            acc.device != fig.device:
+        raise ValueError(f"acoustic_accumulate: acc must be a contiguous float64 [G + 1, 20] tensor on {fig.device}")
+    if err is not None and (err.dtype != torch.float64 or tuple(err.shape) != (B, 5) or not err.is_contiguous() or
+                            err.device != fig.device):
+        raise ValueError(f"acoustic_accumulate: err must be a contiguous float64 [{B}, 5] tensor on {fig.device}")
+    check(_lib.lib().unetrir_acoustic_accumulate(_p(fig), _p(group), B, acc.shape[0] - 1, float(fs), _p(err), _p(acc), _stream()),
+          "acoustic_accumulate")
+
+
 # ---- batches out of the device-resident data set ------------------------------------------------------
 
 def _bank(t, dtype, what, like=None, rows=None):
