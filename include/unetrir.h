@@ -843,6 +843,40 @@ int unetrir_griffinlim_f32(const float* feat, int B, int H, int W, int n_bins, i
                            unetrir_stream_t stream);
 int unetrir_uniform_f32(float* out, long long n, unsigned long long seed, unsigned long long step, unetrir_stream_t stream);
 
+/* ---- output head behind UpSampling2D((2, 2)) (dl_models/u_net.py:247-248, resize_factor_0 = [2, 2]) without the up-sampled tensor
+ *      (head_up2.hip): nearest-neighbour x2 followed by Conv2D(2, (6,6), 'same') is a 4x4 'same' convolution (pad 1 before, 2 after)
+ *      with 8 output channels (o, a, b) on the coarse grid [B][h][w][C] followed by depth-to-space:
+ *          logit[o][2i+a][2j+b] = bias[o] + sum_{u,v,c} K'[(o,a,b)][u][v][c] * x[i+u-1][j+v-1][c]
+ *          K'[(o,a,b)][u][v][c] = sum_{dh: (a+dh)>>1 == u} sum_{dw: (b+dw)>>1 == v} K[o][dh][dw][c]      (dh outer, dw inner, ascending)
+ *      h, w are the COARSE sizes; the fine grid is [B][2h][2w].  C % 8 == 0.  fp32 accumulation, no atomics.
+ *      unetrir_head_up2_supported_*: mask of the passes served for C input channels - 1 forward, 2 data gradient, 4 weight gradient.
+ *      fold: w the fp32 master [>=2][6][6][C] (rows 0, 1 read) -> wf fp32 [8][4][4][C], summed in fp32 in the order above; round_bf16 != 0
+ *      (the work copy of a bf16 trunk): each sum rounded to bf16 once and stored as that value.
+ *      fwd: x [B*h*w][ldx]; wf the folded copy; bias fp32 [>=2] or NULL; y fp32 logits [B*2h*2w][ldy] exactly as unetrir_head6x6_fwd_*
+ *      writes them (ldy >= 2; with ldy >= 4 channels 2, 3 zeroed, further ones untouched): the depth-to-space is in the store.
+ *      dgrad: dy [B*2h*2w][lddy >= 2] (channels 0, 1 read) -> dx [B*h*w][lddx], columns [0, C) written (rounded once for bf16), no addend.
+ *      wgrad: dw[0..1][6][6][C] in the layout of the master (unfold, the transpose of fold, included: a outer, b inner); further rows of a
+ *      padded kernel gradient are left untouched.  One slab of partial sums per workgroup in ws (>= unetrir_head_up2_wgrad_ws_bytes,
+ *      0 for unsupported arguments), reduced in slab order by a second launch, unfolded by a third; the slab count depends on
+ *      (B, h, w, C) alone.  The bias gradient is unetrir_colsum_* of the fine dlogits.
+ *      x, wf, dx, dw, ws 16-byte aligned; UNETRIR_EINVAL otherwise, before the device is touched. */
+int unetrir_head_up2_supported_f32(int C);
+int unetrir_head_up2_supported_bf16(int C);
+int unetrir_head_up2_fold(const float* w, int C, float* wf, int round_bf16, unetrir_stream_t stream);
+int unetrir_head_up2_fwd_f32(const float* x, int ldx, int B, int h, int w, int C, const float* wf, const float* bias, float* y, int ldy,
+                             unetrir_stream_t stream);
+int unetrir_head_up2_fwd_bf16(const unetrir_bf16* x, int ldx, int B, int h, int w, int C, const float* wf, const float* bias, float* y,
+                              int ldy, unetrir_stream_t stream);
+int unetrir_head_up2_dgrad_f32(const float* dy, int lddy, int B, int h, int w, const float* wf, int C, float* dx, int lddx,
+                               unetrir_stream_t stream);
+int unetrir_head_up2_dgrad_bf16(const unetrir_bf16* dy, int lddy, int B, int h, int w, const float* wf, int C, unetrir_bf16* dx, int lddx,
+                                unetrir_stream_t stream);
+size_t unetrir_head_up2_wgrad_ws_bytes(int B, int h, int w, int C);
+int unetrir_head_up2_wgrad_f32(const float* x, int ldx, int B, int h, int w, int C, const float* dy, int lddy, float* dw, void* ws,
+                               size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_head_up2_wgrad_bf16(const unetrir_bf16* x, int ldx, int B, int h, int w, int C, const unetrir_bf16* dy, int lddy, float* dw,
+                                void* ws, size_t ws_bytes, unetrir_stream_t stream);
+
 /* ---- profiling hooks used by bench.py: when enabled every conv launch is bracketed by HIP
  *      events on its own stream; collect() synchronises those events and returns, per kernel
  *      family, launch count, total milliseconds and total algorithmic FLOPs.  Process-global

@@ -42,7 +42,8 @@ def build_model(a, dev):
     if a.name == "diffvae":    # the model of dl_models/diff_vae.py's own __main__ block (:476-485); add --diff-loss
         return U.DiffVAE(shape, (2, 16), conv_filters=(32, 64, 128, 256), conv_kernels=(3, 3, 3, 3), conv_strides=(2, 2, 2, 2),
                          latent_space_dim=16, n_neurons=20 * 64, name="Diff_VAE", **common)
-    return U.UNet(shape, (2, 16), mode=0, number_filters_0=a.filters, kernels=a.kernels, name="U-Net", **common)
+    return U.UNet(shape, (2, 16), mode=0, number_filters_0=a.filters, kernels=a.kernels, name="U-Net",
+                  resize_factor_0=[a.resize_factor_0] * 2, **common)
 
 
 def main():
@@ -57,6 +58,8 @@ def main():
     ap.add_argument("--name", choices=("ae", "resae", "vae", "vqvae", "aenet", "diffunet", "diffvae", "unet"), default="unet")
     ap.add_argument("--filters", type=int, default=32, help="number_filters_0 of the U-Net")
     ap.add_argument("--kernels", type=int, default=3)
+    ap.add_argument("--resize-factor-0", type=int, choices=(1, 2), default=1,
+                    help="U-Net only: 2 runs the network at half resolution (first convolution stride 2, up-sampling folded into the head)")
     ap.add_argument("--height", type=int, default=144)
     ap.add_argument("--width", type=int, default=160)
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")

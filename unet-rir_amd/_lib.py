@@ -235,6 +235,19 @@ _SIGS = {
     "unetrir_head1x1_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "unetrir_head1x1_bwd_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int,
                                            c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    # UpSampling2D((2, 2)) -> Conv2D(2, (6, 6)) head of the half-resolution U-Net, folded to the coarse grid (head_up2.hip)
+    "unetrir_head_up2_supported_f32": (C.c_int, [C.c_int]),
+    "unetrir_head_up2_supported_bf16": (C.c_int, [C.c_int]),
+    "unetrir_head_up2_fold": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_head_up2_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_stream]),
+    "unetrir_head_up2_fwd_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_stream]),
+    "unetrir_head_up2_dgrad_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_head_up2_dgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_head_up2_wgrad_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "unetrir_head_up2_wgrad_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_void_p,
+                                             C.c_size_t, c_stream]),
+    "unetrir_head_up2_wgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_void_p,
+                                              C.c_size_t, c_stream]),
     "unetrir_sgd_f32": (C.c_int, [c_f32p, c_f32p, C.c_longlong, C.c_float, C.c_float, c_stream]),
     "unetrir_nadam_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     C.c_float, C.c_float, C.c_float, c_stream]),

@@ -76,8 +76,11 @@ class UNetEngine(EngineBase):
                  device="cuda:0", n_replicas=1, dtype="f32", overlap_wgrad=False, runtime=None, share=None):
         """runtime, share: see EngineBase (share: a UNetEngine of the same configuration)."""
         super().__init__(device, n_replicas, dtype, runtime, share)
-        if s0 != 1 or s != 2:
-            raise NotImplementedError("HIP path implements resize_factor_0=[1,1], res_factor=[2,2] (the reference defaults)")
+        # s0 = resize_factor_0 (dl_models/u_net.py:213, :272): 2 = the first encoder convolution has stride 2, every level runs on
+        # (H/2, W/2) / 2^l and UpSampling2D((2, 2)) in front of the head (:247-248) is folded into it (csrc/head_up2.hip)
+        if s0 not in (1, 2) or s != 2:
+            raise NotImplementedError("HIP path implements resize_factor_0=[1,1] or [2,2] and res_factor=[2,2]")
+        self.s0 = s0
         self._cst_rows, self._cst_buf, self._cst_gen = {}, None, ops.config_generation()
         if F0 % self.PAD:
             raise ValueError(f"number_filters_0 must be a multiple of {self.PAD} for dtype {dtype}")
@@ -90,19 +93,22 @@ class UNetEngine(EngineBase):
         self.inf_vector_shape = tuple(inf_vector_shape)
         self.L = depth + 1
         self.ch = [F0 * 2 ** l for l in range(self.L)]
-        self.hw = [(H, W)]
+        self.hw = [(same_out(H, s0), same_out(W, s0))]
         for _ in range(depth):
             h, w = self.hw[-1]
             self.hw.append((same_out(h, 2), same_out(w, 2)))
         for l in range(depth):
             if self.hw[l][0] != 2 * self.hw[l + 1][0] or self.hw[l][1] != 2 * self.hw[l + 1][1]:
-                raise ValueError("spatial size must halve exactly at every level that feeds a skip concat")
+                raise ValueError("spatial size must halve exactly at every level that feeds a skip concat: H and W must be multiples "
+                                 f"of resize_factor_0 * 2^depth = {s0 * 2 ** depth}")
+        if (s0 * self.hw[0][0], s0 * self.hw[0][1]) != (H, W):
+            raise ValueError(f"spatial size must halve exactly: H and W must be multiples of resize_factor_0 * 2^depth = {s0 * 2 ** depth}")
         self.h5, self.w5 = self.hw[-1]
         self.n_idx = int(math.prod(self.inf_vector_shape))
         self.vec_in = self.n_idx * EMB_DIM
         self.vec_dim = self.h5 * self.w5 * VEC_CH
-        if share is not None and (share.H, share.W, share.F0, share.k, share.depth, share.batchnorm, share.dtype, share.inf_vector_shape) != \
-                (H, W, F0, k, depth, batchnorm, dtype, self.inf_vector_shape):
+        if share is not None and (share.H, share.W, share.F0, share.k, share.depth, share.batchnorm, share.dtype, share.inf_vector_shape,
+                                  share.s0) != (H, W, F0, k, depth, batchnorm, dtype, self.inf_vector_shape, s0):
             raise ValueError("share= needs an engine of the same configuration (only the batch size may differ)")
         self._build_params(share)
         self._alloc()
@@ -118,7 +124,14 @@ class UNetEngine(EngineBase):
         # Infinity Cache (parking them measured 0.06-0.09 ms per step slower)
         self._init_side_stream(share, overlap_wgrad, 96 << 20, park_max_bytes=16 << 20)
         self.head_direct = ops.head6x6_supported(self.ch[0])
-        if self.head_direct:
+        if s0 == 2:      # the folded head: its own kernels in both storage types, reading the folded work copy of head.kernel
+            if ops.head_up2_supported(self.ch[0], self.dtype) != (ops.UP2_FWD | ops.UP2_DGRAD | ops.UP2_WGRAD):
+                raise ValueError("the head behind resize_factor_0=[2,2] needs number_filters_0 % 8 == 0")
+            self._fold_copy("head.kernel", self.ch[0], share)
+            need = ops.head_up2_wgrad_ws_bytes(self.B, *self.hw[0], self.ch[0])
+            self.ws.reserve(need)
+            self.ws_w.reserve(need)
+        elif self.head_direct:
             self.ws.reserve(512 * 2 * 36 * self.ch[0] * 4)
             self.ws_w.reserve(512 * 2 * 36 * self.ch[0] * 4)
         elif self.dtype == "bf16":
@@ -242,7 +255,7 @@ class UNetEngine(EngineBase):
             h, w = hw[l - 1]
             c = ch[l - 1]
             if l == 1:
-                self.geo["enc1.down"] = G(B, h, w, PAD, c, k, 1)
+                self.geo["enc1.down"] = G(B, self.H, self.W, PAD, c, k, self.s0)
             else:
                 hi, wi = hw[l - 2]
                 self.geo[f"enc{l}.down"] = G(B, hi, wi, ch[l - 2], c, k, 2)
@@ -256,7 +269,8 @@ class UNetEngine(EngineBase):
             self.geo[f"dec{l}.up"] = G(B, hl, wl, ch[l], c, k, 2)
             self.geo[f"dec{l}.cb1a"] = G(B, h, w, 2 * c, c, k, 1)
             self.geo[f"dec{l}.cb1b"] = G(B, h, w, c, c, 3, 1)
-        self.geo["head"] = G(B, self.H, self.W, ch[0], PAD, 6, 1)
+        if self.s0 == 1:      # s0 = 2: the head runs on its own kernels alone and has no tap-table geometry
+            self.geo["head"] = G(B, self.H, self.W, ch[0], PAD, 6, 1)
 
     def _reserve_workspace(self):
         need = 1 << 16
@@ -265,7 +279,7 @@ class UNetEngine(EngineBase):
                 need = max(need, ops.conv2d_transpose_wgrad_ws_bytes(g))
             else:
                 need = max(need, ops.conv2d_wgrad_ws_bytes(g))
-        P0 = self.B * self.H * self.W
+        P0 = self.B * self.hw[0][0] * self.hw[0][1]
         need = max(need, ops.bn_ws_bytes(P0, max(self.ch[0], 4)), ops.bn_ws_bytes(self.B * self.h5 * self.w5, self.ch[-1]),
                    ops.bn_ws_bytes(self.B, self.vec_dim))
         for l in range(1, self.L + 1):
@@ -402,7 +416,9 @@ class UNetEngine(EngineBase):
             self._conv_bn_relu_fwd(f"dec{l}.cb1a", self.cat[l], self.ya[l], self.aa[l])
             self._conv_bn_relu_fwd(f"dec{l}.cb1b", self.aa[l], self.yb[l], self.ab[l])
             cur = self.ab[l]
-        if self.head_direct:
+        if self.s0 == 2:
+            ops.head_up2_fwd(cur, self.pf["head.kernel"], p["head.bias"], self.logits)
+        elif self.head_direct:
             ops.head6x6_fwd(cur, p["head.kernel"], p["head.bias"], self.logits)
         else:
             ops.conv2d_fwd(self.geo["head"], cur, p["head.kernel"], p["head.bias"], self.logits)
@@ -435,7 +451,10 @@ class UNetEngine(EngineBase):
                 self._ready(on_ready, self.specs[name].end)
 
         gl = self.g_logits
-        if self.head_direct:
+        if self.s0 == 2:
+            with self._wg() as ws_:
+                ops.head_up2_wgrad(self.ab[1] if D >= 1 else self.a[1], gl, g["head.kernel"], ws_)  # rows 2.. of the padded kernel stay 0
+        elif self.head_direct:
             with self._wg() as ws_:
                 ops.head6x6_wgrad(self.ab[1] if D >= 1 else self.a[1], gl, g["head.kernel"], ws_)   # rows 2,3 of the padded kernel stay 0
         else:
@@ -445,7 +464,9 @@ class UNetEngine(EngineBase):
             ops.colsum(gl, g["head.bias"], ws_)
         top = self.ab[1] if D >= 1 else self.a[1]
         g_cur = self.g_ab[1] if D >= 1 else self.g_z
-        if self.head_direct and self.dtype == "bf16" and ops.head6x6_dgrad_supported(self.W, self.ch[0]):
+        if self.s0 == 2:
+            ops.head_up2_dgrad(gl, self.pf["head.kernel"], g_cur)
+        elif self.head_direct and self.dtype == "bf16" and ops.head6x6_dgrad_supported(self.W, self.ch[0]):
             ops.head6x6_dgrad(gl, self.p["head.kernel"], g_cur)         # reads the fp32 master kernel: before ready()
         else:
             ops.conv2d_dgrad(self.geo["head"], gl, self.wb("head.kernel"), g_cur)

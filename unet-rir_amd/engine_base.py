@@ -258,6 +258,7 @@ class EngineBase(DeviceCounters):
         self.dropout_seed = share.dropout_seed if share is not None else (torch.initial_seed() & 0xFFFFFFFF)
         self._mask_bufs = {}
         self._pending_ready = []
+        self.pf = {}                   # folded work copies of a head behind UpSampling2D((2, 2)) (_fold_copy)
 
     def _init_side_stream(self, share, overlap_wgrad, arena_bytes, park_max_bytes=None):
         """The weight-gradient and optimizer streams (share's when it has them), the side stream's own scratch buffer (as large as
@@ -327,6 +328,13 @@ class EngineBase(DeviceCounters):
                 if ne:
                     self.ppk[n] = torch.zeros(ne, dtype=torch.bfloat16, device=self.device)
 
+    def _fold_copy(self, kname, c, share=None):
+        """The folded work copy [8][4][4][c] of the 6x6 head kernel `kname` behind UpSampling2D((2, 2)) (csrc/head_up2.hip): fp32, on
+        a bf16 trunk every tap rounded to bf16 once.  Refreshed with the other work copies; share: alias that engine's."""
+        self.pf[kname] = share.pf[kname] if share is not None else \
+            torch.zeros(ops.head_up2_folded_elems(c), dtype=torch.float32, device=self.device)
+        return self.pf[kname]
+
     def refresh_transposed(self):
         """Work copies from the fp32 masters: Conv2D / Dense kernels -> [Cin][T][Cout] for dgrad, Conv2DTranspose kernels ->
         [Cout][T][Cin] for forward; the bf16 kernels' copies (both orientations, packed) in one batched launch."""
@@ -345,6 +353,8 @@ class EngineBase(DeviceCounters):
                     ent.append((self.p[n], self.ph[n], self.pth[n], N, T, C_, C_, N, self.ppk.get(n)))
                 self._cast_table = ops.make_cast_table(ent, self.device)
             ops.cast_weights_batched(self._cast_table)
+        for n, wf in self.pf.items():
+            ops.head_up2_fold(self.p[n], wf, self.specs[n].shape[-1], self.dtype == "bf16")
         self.t_dirty = False
 
     def reset_parameters(self, generator=None):

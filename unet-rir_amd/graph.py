@@ -288,6 +288,39 @@ class GraphEngine(EngineBase):
         self._push(fwd, bwd)
         return y
 
+    def _head6x6_up2(self, x: Node, name):
+        """UpSampling2D((2, 2)) -> Conv2D(2, (6,6), 'same') in front of the sigmoid (dl_models/u_net.py:247-248, resize_factor_0 =
+        [2, 2]) on the folded kernels of csrc/head_up2.hip, both storage types: x is the coarse [B,h,w,c] node, the result the fine
+        fp32 logits [B,2h,2w,4] with dL/dlogits [.., PAD] in the trunk's storage type.  The up-sampled tensor does not exist.  The
+        parameter is the 6x6 kernel, as in _head6x6; its folded work copy (EngineBase._fold_copy) is what the kernels read."""
+        B, h, w, c, PAD = self.B, x.a.H, x.a.W, x.a.C, self.PAD
+        if ops.head_up2_supported(c, x.a.sfx) != (ops.UP2_FWD | ops.UP2_DGRAD | ops.UP2_WGRAD):
+            raise ValueError("the head behind resize_factor_0=[2,2] needs number_filters_0 % 8 == 0")
+        kname, bname = name + ".kernel", name + ".bias"
+        self._param(kname, (PAD, 6, 6, c), "conv_padout", (6, 6, c, 2))
+        self._param(bname, (PAD,), "bias_pad", (2,))
+        wf = self._fold_copy(kname, c, self._share)
+        y = self._reg(Node(ops.new_act(B, 2 * h, 2 * w, 4, self.device), True, ops.new_act(B, 2 * h, 2 * w, PAD, self.device, dtype=self.adt)))
+        need = ops.head_up2_wgrad_ws_bytes(B, h, w, c)
+        self.ws.reserve(need)
+        self.ws_w.reserve(need)
+
+        def fwd():
+            ops.head_up2_fwd(x.a, wf, self.p[bname], y.a)
+
+        def dgrad(dst, add):
+            if add is not None:
+                raise NotImplementedError("the folded head is the only consumer of its input")
+            ops.head_up2_dgrad(y.g, wf, dst)
+
+        def bwd():
+            with self._wg() as ws_:
+                ops.head_up2_wgrad(x.a, y.g, self.g[kname], ws_)         # rows 2.. of the padded kernel gradient stay 0
+                ops.colsum(y.g, self.g[bname], ws_)
+            self._emit(x, dgrad)
+        self._push(fwd, bwd)
+        return y
+
     def _head1x1(self, x: Node, name, generic=False):
         """Conv2D(2, (1, 1), activation='linear') (dl_models/diff_u_net.py:247).  fp32 trunk: an ordinary conv node with the 2 output
         channels padded to 4.  bf16 trunk: the passes ops.head1x1_supported offers run on csrc/head1x1.hip - bf16 activations in,

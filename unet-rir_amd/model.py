@@ -327,6 +327,10 @@ class UNet(_EngineModule):
     ``forward(spec[B,2,H,W] float32 NCHW, emb[B,2,16] int) -> [B,2,H,W]``.
     """
 
+    # resize_factor_0 = [2, 2] (dl_models/u_net.py:213, :247-248): first encoder convolution with stride 2, the U-Net at half resolution,
+    # UpSampling2D((2, 2)) in front of the head folded into it (csrc/head_up2.hip); H and W must be multiples of 2 * 2^depth
+    _resize_factors_0 = ([1, 1], [2, 2])
+
     def __init__(self, input_shape, inf_vector_shape, learning_rate=1e-5, mode=0, number_filters_0=32, kernels=6,
                  BatchNorm=True, resize_factor_0=None, res_factor=None, name="U-Net", depth=4, batch_size=None,
                  device="cuda:0", n_replicas=1, dropout=True, dtype="f32", overlap=False, fold_l2=True, runtime=None):
@@ -336,8 +340,9 @@ class UNet(_EngineModule):
         self.resize_factor_0 = [1, 1] if resize_factor_0 is None else list(resize_factor_0)
         if mode not in (0, 1, 2, 3):
             raise ValueError("mode must be 0..3 (dl_models/u_net.py:280-287)")
-        if self.res_factor != [2, 2] or self.resize_factor_0 != [1, 1]:
-            raise NotImplementedError("only res_factor=[2,2], resize_factor_0=[1,1] are implemented")
+        if self.res_factor != [2, 2] or self.resize_factor_0 not in self._resize_factors_0:
+            raise NotImplementedError(f"{type(self).__name__} implements resize_factor_0 in {self._resize_factors_0} with "
+                                      f"res_factor=[2, 2], not resize_factor_0={self.resize_factor_0}, res_factor={self.res_factor}")
         shp = tuple(input_shape)
         if len(shp) != 3 or 2 not in (shp[0], shp[2]):
             raise ValueError("input_shape must be (H, W, 2) or (2, H, W)")
@@ -361,20 +366,21 @@ class UNet(_EngineModule):
 
     def _new_engine(self, B, share):
         if self.mode == 0:
-            return UNetEngine(self.H, self.W, B, F0=self.number_filters_0, k=self.kernels, depth=self.depth,
+            return UNetEngine(self.H, self.W, B, F0=self.number_filters_0, k=self.kernels, depth=self.depth, s0=self.resize_factor_0[0],
                               batchnorm=self.BatchNorm, inf_vector_shape=self.inf_vector_shape, device=self._device,
                               n_replicas=self.n_replicas, dtype=self.dtype_name, overlap_wgrad=self.overlap, runtime=self._rt,
                               share=share)
         return UNetGraphEngine(self.H, self.W, B, F0=self.number_filters_0, k=self.kernels, depth=self.depth, mode=self.mode,
                                batchnorm=self.BatchNorm, inf_vector_shape=self.inf_vector_shape, device=self._device,
                                n_replicas=self.n_replicas, runtime=self._rt, share=share, dtype=self.dtype_name,
-                               overlap_wgrad=self.overlap)
+                               overlap_wgrad=self.overlap, s0=self.resize_factor_0[0])
 
-    # `parameters.pkl` holds the reference's list (u_net.py:180-187) followed by the arguments it forgets (kernels, depth, and
-    # this build's dtype) - `UNet.load` of the reference feeds BatchNorm into the `kernels` slot because of that omission.
+    # `parameters.pkl` holds the reference's list (u_net.py:180-187) followed by the arguments it forgets (kernels, depth, this
+    # build's dtype, and resize_factor_0; a file without the last loads as [1, 1]) - `UNet.load` of the reference feeds BatchNorm
+    # into the `kernels` slot because of that omission.
     def _ctor_parameters(self):
         return [self.input_shape, self.inf_vector_shape, self.learning_rate, self.mode, self.number_filters_0,
-                self.BatchNorm, self.kernels, self.depth, self.dtype_name]
+                self.BatchNorm, self.kernels, self.depth, self.dtype_name, list(self.resize_factor_0)]
 
     @classmethod
     def load(cls, save_folder=".", batch_size=1, device="cuda:0", **kw):
@@ -382,8 +388,8 @@ class UNet(_EngineModule):
             prm = pickle.load(f)
         input_shape, inf_vector_shape, lr, mode, f0, bn, kernels, depth = prm[:8]
         dtype = prm[8] if len(prm) > 8 else "f32"
-        ue = cls(input_shape, inf_vector_shape, lr, mode, f0, kernels, bn, depth=depth, batch_size=batch_size, device=device,
-                 dtype=dtype, **kw)
+        ue = cls(input_shape, inf_vector_shape, lr, mode, f0, kernels, bn, resize_factor_0=prm[9] if len(prm) > 9 else [1, 1],
+                 depth=depth, batch_size=batch_size, device=device, dtype=dtype, **kw)
         ue.load_weights(os.path.join(save_folder, "weights.npz"))
         return ue
 
@@ -393,6 +399,8 @@ class AENet(UNet):
     bottleneck with Dropout(.5) and a clipped-ReLU output, on aenet.AENetEngine.  Constructor arguments keep the reference's names,
     order and defaults (it has no `kernels`); the additions are UNet's.  `compile_and_fit`, `get_callbacks`, `summary`, `save` /
     `load` / `load_weights`, `predict_stft` and `model.model.trainable_variables` / `.losses` are the shared ones."""
+
+    _resize_factors_0 = ([1, 1],)          # the first level and the head are other layers here (2x2 stride-2, dl_models/ae_net.py)
 
     def __init__(self, input_shape, inf_vector_shape, learning_rate=1e-5, mode=0, number_filters_0=32, BatchNorm=True,
                  resize_factor_0=None, res_factor=None, name="AENet", batch_size=None, device="cuda:0", n_replicas=1, dropout=True,

@@ -549,6 +549,54 @@ def head6x6_dgrad(dy: Act, w, dx: Act):
           "head6x6_dgrad")
 
 
+# UpSampling2D((2, 2)) -> Conv2D(2, (6, 6), 'same') (dl_models/u_net.py:247-248) folded to a 4x4 convolution with 8 output channels on
+# the coarse grid (csrc/head_up2.hip).  x / dx are the coarse [B,h,w,C] tensors, y / dy the fine [B,2h,2w,..] logits / dlogits.
+UP2_FWD, UP2_DGRAD, UP2_WGRAD = 1, 2, 4       # passes in the mask head_up2_supported returns
+
+
+def head_up2_supported(C_, storage="f32"):
+    """Passes of the folded head with C_ input channels that csrc/head_up2.hip serves in this storage type."""
+    return int(_fn("head_up2_supported", storage)(int(C_)))
+
+
+def head_up2_folded_elems(C_):
+    return 8 * 4 * 4 * int(C_)
+
+
+def head_up2_fold(w, wf, C_, round_bf16=False):
+    """Master head kernel [PAD][6][6][C] -> folded work copy [8][4][4][C] (fp32; round_bf16: every tap rounded to bf16 once)."""
+    if wf.numel() < head_up2_folded_elems(C_) or w.numel() < 2 * 36 * C_:
+        raise ValueError("head_up2_fold: buffer too small")
+    check(_lib.lib().unetrir_head_up2_fold(_p(w), int(C_), _p(wf), int(bool(round_bf16)), _stream()), "head_up2_fold")
+
+
+def head_up2_fwd(x: Act, wf, bias, y: Act):
+    """Coarse activations in, fp32 logits of the fine grid out, in the layout head6x6_fwd writes."""
+    if (y.H, y.W) != (2 * x.H, 2 * x.W) or y.B != x.B or y.sfx != "f32":
+        raise ValueError("head_up2_fwd: y must be the fp32 [B,2h,2w,..] logits")
+    check(_fn("head_up2_fwd", x.sfx)(_p(x), x.ld, x.B, x.H, x.W, x.C, _p(wf), _p(bias), _p(y), y.ld, _stream()), "head_up2_fwd")
+
+
+def head_up2_dgrad(dy: Act, wf, dx: Act):
+    """Adjoint of head_up2_fwd: fine dlogits (channels 0, 1) -> coarse dx, written (no addend)."""
+    if (dy.H, dy.W) != (2 * dx.H, 2 * dx.W) or dy.B != dx.B or dy.sfx != dx.sfx:
+        raise ValueError("head_up2_dgrad: dy must be the fine grid of dx, in its storage type")
+    check(_fn("head_up2_dgrad", dx.sfx)(_p(dy), dy.ld, dx.B, dx.H, dx.W, _p(wf), dx.C, _p(dx), dx.ld, _stream()), "head_up2_dgrad")
+
+
+def head_up2_wgrad_ws_bytes(B, h, w, C_):
+    return int(_lib.lib().unetrir_head_up2_wgrad_ws_bytes(int(B), int(h), int(w), int(C_)))
+
+
+def head_up2_wgrad(x: Act, dy: Act, dw, ws: Workspace):
+    """Rows 0, 1 of the [PAD][6][6][C] master kernel's gradient (the rest is left as it is) from the coarse x and the fine dlogits."""
+    if (dy.H, dy.W) != (2 * x.H, 2 * x.W) or dy.B != x.B or dy.sfx != x.sfx:
+        raise ValueError("head_up2_wgrad: dy must be the fine grid of x, in its storage type")
+    ws.reserve(head_up2_wgrad_ws_bytes(x.B, x.H, x.W, x.C))
+    check(_fn("head_up2_wgrad", x.sfx)(_p(x), x.ld, x.B, x.H, x.W, x.C, _p(dy), dy.ld, _p(dw), ws.ptr, ws.nbytes, _stream()),
+          "head_up2_wgrad")
+
+
 # ---- waveform <-> feature transforms ----------------------------------------------------------------
 
 PAD_MODES = {"reflect": 0, "constant": 1}

@@ -13,10 +13,18 @@ from .graph import GraphEngine, RELU
 
 class UNetGraphEngine(GraphEngine):
     def __init__(self, H, W, B, F0=32, k=3, depth=4, mode=0, batchnorm=True, inf_vector_shape=(2, 16), device="cuda:0",
-                 n_replicas=1, runtime=None, share=None, dtype="f32", overlap_wgrad=False):
+                 n_replicas=1, runtime=None, share=None, dtype="f32", overlap_wgrad=False, s0=1):
+        """s0: resize_factor_0 (dl_models/u_net.py:213, :272) - 1, or 2: the first encoder convolution has stride 2, the whole U-Net
+        runs on (H/2, W/2) and UpSampling2D((2, 2)) in front of the head (:247-248) brings the output back to (H, W)."""
         super().__init__(B, device, n_replicas, runtime, share, dtype, overlap_wgrad)
         if mode not in (0, 1, 2, 3):
             raise ValueError("mode must be 0..3")
+        if s0 not in (1, 2):
+            raise NotImplementedError("resize_factor_0 must be [1, 1] or [2, 2]")
+        if s0 == 2 and (H % (s0 * 2 ** depth) or W % (s0 * 2 ** depth)):
+            raise ValueError(f"spatial size must halve exactly at every level: H and W must be multiples of {s0 * 2 ** depth} "
+                             f"(resize_factor_0 * 2^depth)")
+        self.s0 = s0
         if F0 % self.PAD:
             raise ValueError(f"number_filters_0 must be a multiple of {self.PAD} for dtype {dtype}")
         self.H, self.W, self.F0, self.k, self.depth, self.mode, self.batchnorm = H, W, F0, k, depth, mode, batchnorm
@@ -56,7 +64,7 @@ class UNetGraphEngine(GraphEngine):
         skips, cats = [], []
         for l in range(1, D + 2):
             c = ch[l - 1]
-            stride = 1 if l == 1 else 2
+            stride = self.s0 if l == 1 else 2
             d = self._conv(x, f"enc{l}.down", c, k, stride, followed_by_bn=False, pad_in=self.PAD if l == 1 else 0, l2=True)
             h, w = d.a.H, d.a.W
             if l <= D:         # the block output is the skip: written straight into the lower half of the concat buffer
@@ -80,7 +88,7 @@ class UNetGraphEngine(GraphEngine):
             self._conv(x, f"dec{l}.up", c, k, 2, transpose=True, followed_by_bn=False, out=up, l2=True)
             a = self._conv_bn_relu(cat, f"dec{l}.cb1a", c, k)
             x = self._feature_block(a, f"dec{l}")
-        self.logits = self._head6x6(x, "head")
+        self.logits = self._head6x6(x, "head") if self.s0 == 1 else self._head6x6_up2(x, "head")
         self.vec_dim = h5 * w5 * VEC_CH      # l2(0.001) sits only on the strided and the transposed convs (:274, :302)
 
     def forward(self, spec, emb, dropout_mask=None, target=None, global_batch=None, alpha=0.9):
