@@ -877,6 +877,50 @@ int unetrir_head_up2_wgrad_f32(const float* x, int ldx, int B, int h, int w, int
 int unetrir_head_up2_wgrad_bf16(const unetrir_bf16* x, int ldx, int B, int h, int w, int C, const unetrir_bf16* dy, int lddy, float* dw,
                                 void* ws, size_t ws_bytes, unetrir_stream_t stream);
 
+/* ---- the room classifier deep_CNN (dl_models/cnn_clas.py:19-53; cnn_clas.hip), fp32 storage, direct arithmetic, no atomics.
+ *      Conv2D(3x3, strides 1, padding='valid', activation='relu') (cnn_clas.py:25, :31, :37).  g->H, g->W are the INPUT size (>= 3),
+ *      the output is (H - 2) x (W - 2); g->k = 3, g->stride = 1; g->Cin in {4, 16, 32} (4: the two input channels zero-padded as
+ *      unetrir_nchw_to_nhwc_pad_f32 writes them), g->Cout in {16, 32, 64}.
+ *      fwd:   y = conv(x, w) + bias, max(., 0) when relu != 0; w [Cout][3][3][Cin].
+ *      dgrad: dx = the adjoint applied to dy, or to dy * [y > 0] when relu != 0 (y = the stored forward output, may be NULL
+ *             otherwise); wt [Cin][3][3][Cout]; ALL of dx [B*H*W][lddx] is written, the two border rings included.
+ *      wgrad: dw [Cout][3][3][Cin] and dbias [Cout] from the same (masked) dy.  Partial sums over slabs of whole output rows go to ws
+ *             (>= unetrir_conv3x3_valid_wgrad_ws_bytes, 0 for an unsupported geometry) and are added in a fixed order; the split
+ *             depends on g alone: with R = B (H - 2) output rows, slabs of ceil(R / min(R, 524288 / (Cin Cout))) rows, each holding
+ *             [Cout][3][3][Cin] + [Cout] floats.  Zero input channels (the padding of the first layer) get a zero gradient.
+ *      AveragePooling2D(2x2, strides 2, 'valid') (cnn_clas.py:28, :34) of x [B][H][W][C] -> y [B][H/2][W/2][C], H, W >= 2, C % 4 == 0.
+ *      affine (nullable): the [2 C] scale / shift unetrir_bn_stats_f32 writes - y = pool(x) * scale + shift, which equals the pooled
+ *      BatchNormalization output because the affine is per channel.  bwd: dx [B][H][W][C] = dy / 4 in every pixel of a cell and
+ *      exactly 0 in a trailing odd row or column; with BatchNormalization in front, unetrir_bn_bwd_f32 (relu = 0) follows on dx.
+ *      GlobalAveragePooling2D (cnn_clas.py:40): y [B][C] = sum over the h w pixels in a fixed order, times 1 / (h w), with the
+ *      same optional affine; C <= 1024.  bwd: dx = dy / (h w) in every pixel.
+ *      Dense(classes, softmax) + categorical_crossentropy (cnn_clas.py:49, :63) on logits [B][ldl >= classes], 1 <= classes <= 1024:
+ *      ce:  probs [B][classes] = softmax; with CE_b = -sum_c y_c log p_c taken as the log-softmax of the max-subtracted logits
+ *           (no clipping of p), loss_out[0] = inv_norm sum_b CE_b, loss_out[1] = sum_b CE_b, loss_out[2] = 0; dlogits [B][ldd] =
+ *           (p_c sum_k y_k - y_c) inv_norm, columns [classes, ldd) zero; acc_out[0] = rows with argmax(logits) == argmax(target), the
+ *           lowest index on ties on both sides, as fp32.  target [B][classes]: one-hot or soft rows.  One workgroup, fp64 row sums.
+ *      fwd: probs only.  bwd: dlogits = p_c (dprobs_c - sum_k dprobs_k p_k) from an upstream gradient on the probabilities.
+ *      UNETRIR_EINVAL before the device is touched: geometry outside the above, a null required pointer, a pixel stride smaller than
+ *      its channel count or no multiple of 4, a pointer of a 16-byte access that is not 16-byte aligned, a workspace too small. */
+int unetrir_conv3x3_valid_fwd_f32(const unetrir_conv_geom* g, const float* x, int ldx, const float* w, const float* bias, int relu,
+                                  float* y, int ldy, unetrir_stream_t stream);
+int unetrir_conv3x3_valid_dgrad_f32(const unetrir_conv_geom* g, const float* dy, int lddy, const float* y, int ldy, int relu,
+                                    const float* wt, float* dx, int lddx, unetrir_stream_t stream);
+size_t unetrir_conv3x3_valid_wgrad_ws_bytes(const unetrir_conv_geom* g);
+int unetrir_conv3x3_valid_wgrad_f32(const unetrir_conv_geom* g, const float* x, int ldx, const float* dy, int lddy, const float* y,
+                                    int ldy, int relu, float* dw, float* dbias, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+int unetrir_avgpool2_fwd_f32(const float* x, int ldx, int B, int H, int W, int C, const float* affine, float* y, int ldy,
+                             unetrir_stream_t stream);
+int unetrir_avgpool2_bwd_f32(const float* dy, int lddy, int B, int H, int W, int C, float* dx, int lddx, unetrir_stream_t stream);
+int unetrir_gap_fwd_f32(const float* x, int ldx, int B, int H, int W, int C, const float* affine, float* y, int ldy,
+                        unetrir_stream_t stream);
+int unetrir_gap_bwd_f32(const float* dy, int lddy, int B, int H, int W, int C, float* dx, int lddx, unetrir_stream_t stream);
+int unetrir_softmax_ce_f32(const float* logits, int ldl, const float* target, int B, int classes, float inv_norm, float* probs,
+                           float* dlogits, int ldd, float* loss_out, float* acc_out, unetrir_stream_t stream);
+int unetrir_softmax_fwd_f32(const float* logits, int ldl, int B, int classes, float* probs, unetrir_stream_t stream);
+int unetrir_softmax_bwd_f32(const float* probs, const float* dprobs, int B, int classes, float* dlogits, int ldd,
+                            unetrir_stream_t stream);
+
 /* ---- profiling hooks used by bench.py: when enabled every conv launch is bracketed by HIP
  *      events on its own stream; collect() synchronises those events and returns, per kernel
  *      family, launch count, total milliseconds and total algorithmic FLOPs.  Process-global

@@ -9,6 +9,7 @@ from .engine import UNetEngine  # noqa: F401
 from .device import HipRuntime  # noqa: F401
 from .ae import AutoencoderEngine  # noqa: F401
 from .aenet import AENetEngine  # noqa: F401
+from .cnn_clas import DeepCNNEngine, deep_CNN  # noqa: F401
 from .diffunet import DiffUNetEngine  # noqa: F401
 from .diffvae import DiffVAEEngine  # noqa: F401
 from .model import VAE, VQVAE, AENet, Autoencoder, DiffUNet, DiffVAE, ResAE, UNet  # noqa: F401
@@ -22,4 +23,4 @@ from .dataset import DataGenerator, Dataset, read_wav  # noqa: F401
 from .lamb import LAMB  # noqa: F401
 from .trainer import CheckpointManager, GradBucketer, Trainer, fit, lr_schedule  # noqa: F401
 
-__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "DiffUNet", "DiffUNetEngine", "DiffVAE", "DiffVAEEngine", "HipRuntime", "Trainer", "LAMB", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "acoustics", "write_report", "Dataset", "DataGenerator", "read_wav"]
+__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "DiffUNet", "DiffUNetEngine", "DiffVAE", "DiffVAEEngine", "deep_CNN", "DeepCNNEngine", "HipRuntime", "Trainer", "LAMB", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "acoustics", "write_report", "Dataset", "DataGenerator", "read_wav"]

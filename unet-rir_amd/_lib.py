@@ -282,6 +282,21 @@ _SIGS = {
                                    C.c_void_p, C.c_size_t, c_stream]),
     "unetrir_lamb_dev_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(LambSeg), C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
                                        C.c_longlong, C.c_float, C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    # the room classifier deep_CNN (cnn_clas.hip): 'valid' 3x3 convolution, average / global pooling, softmax + cross-entropy
+    "unetrir_conv3x3_valid_fwd_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_conv3x3_valid_dgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int,
+                                                  c_stream]),
+    "unetrir_conv3x3_valid_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
+    "unetrir_conv3x3_valid_wgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p,
+                                                  c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "unetrir_avgpool2_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_stream]),
+    "unetrir_avgpool2_bwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_gap_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_stream]),
+    "unetrir_gap_bwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_stream]),
+    "unetrir_softmax_ce_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, C.c_int, c_f32p, c_f32p,
+                                         c_stream]),
+    "unetrir_softmax_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
+    "unetrir_softmax_bwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, c_f32p, C.c_int, c_stream]),
     "unetrir_prof_enable": (C.c_int, [C.c_int]),
     "unetrir_prof_collect": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }

@@ -377,6 +377,8 @@ class EngineBase(DeviceCounters):
                         w[..., 2:] = 0
                     if s_.kind == "conv_padout":
                         w[2:] = 0
+                    if s_.kind == "dense":             # output units padded to a multiple of 4 (cnn_clas.DeepCNNEngine): zero rows
+                        w[ks[1]:] = 0
                     t.copy_(w)
                 elif s_.kind == "gamma":
                     t.fill_(1.0)
@@ -403,10 +405,12 @@ class EngineBase(DeviceCounters):
                     t.zero_(); t[..., :2].copy_(a.permute(3, 0, 1, 2).to(self.device))
                 elif s_.kind == "conv_padout":
                     t.zero_(); t[:2].copy_(a.permute(3, 0, 1, 2).to(self.device))
-                elif s_.kind == "dense":
+                elif s_.kind == "dense" and a.shape[1] == t.shape[0]:
                     t.copy_(a.t().reshape(t.shape).to(self.device))
+                elif s_.kind == "dense":               # output units zero-padded to a multiple of 4
+                    t.zero_(); t.view(t.shape[0], -1)[:a.shape[1]].copy_(a.t().to(self.device))
                 elif s_.kind == "bias_pad":
-                    t.zero_(); t[:2].copy_(a.to(self.device))
+                    t.zero_(); t[:a.shape[0]].copy_(a.to(self.device))
                 else:
                     t.copy_(a.to(self.device))
         self.t_dirty = True
@@ -422,9 +426,9 @@ class EngineBase(DeviceCounters):
             elif s_.kind == "conv_padout":
                 a = t[:2].permute(1, 2, 3, 0)
             elif s_.kind == "dense":
-                a = t.reshape(t.shape[0], -1).t()
+                a = t.reshape(t.shape[0], -1)[:s_.keras_shape[1]].t()
             elif s_.kind == "bias_pad":
-                a = t[:2]
+                a = t[:s_.keras_shape[0]]
             else:
                 a = t
             out[n] = a.contiguous().cpu()

@@ -1144,3 +1144,65 @@ def prof_collect():
     fl = (C.c_double * n)()
     _lib.lib().unetrir_prof_collect(counts, ms, fl)
     return list(counts), list(ms), list(fl)
+
+
+# ---- the room classifier deep_CNN (dl_models/cnn_clas.py:19-53; csrc/cnn_clas.hip), fp32 storage -------------------------------
+
+def conv3x3_valid_fwd(g, x: Act, w, bias, y: Act, relu=True):
+    """Conv2D(3x3, strides 1, padding='valid', activation='relu') (cnn_clas.py:25, :31, :37): y [B,H-2,W-2,Cout]; w [Cout][3][3][Cin]."""
+    check(_lib.lib().unetrir_conv3x3_valid_fwd_f32(C.byref(g), _p(x), x.ld, _p(w), _p(bias), int(bool(relu)), _p(y), y.ld, _stream()),
+          "conv3x3_valid_fwd")
+
+
+def conv3x3_valid_dgrad(g, dy: Act, y: Act, wt, dx: Act, relu=True):
+    """Its data gradient from dy * [y > 0] (relu; y the stored forward output) - all of dx is written; wt [Cin][3][3][Cout]."""
+    check(_lib.lib().unetrir_conv3x3_valid_dgrad_f32(C.byref(g), _p(dy), dy.ld, _p(y) if relu else None, y.ld if relu else 0,
+                                                     int(bool(relu)), _p(wt), _p(dx), dx.ld, _stream()), "conv3x3_valid_dgrad")
+
+
+def conv3x3_valid_wgrad_ws_bytes(g):
+    return int(_lib.lib().unetrir_conv3x3_valid_wgrad_ws_bytes(C.byref(g)))
+
+
+def conv3x3_valid_wgrad(g, x: Act, dy: Act, y: Act, dw, dbias, ws: Workspace, relu=True):
+    """Its weight gradient dw [Cout][3][3][Cin] and bias gradient from the same masked dy."""
+    ws.reserve(conv3x3_valid_wgrad_ws_bytes(g))
+    check(_lib.lib().unetrir_conv3x3_valid_wgrad_f32(C.byref(g), _p(x), x.ld, _p(dy), dy.ld, _p(y) if relu else None, y.ld if relu else 0,
+                                                     int(bool(relu)), _p(dw), _p(dbias), ws.ptr, ws.nbytes, _stream()),
+          "conv3x3_valid_wgrad")
+
+
+def avgpool2_fwd(x: Act, affine, y: Act):
+    """AveragePooling2D(2x2, strides 2, 'valid') (cnn_clas.py:28, :34) of x * scale + shift (affine [2C] of bn_stats, or None)."""
+    check(_lib.lib().unetrir_avgpool2_fwd_f32(_p(x), x.ld, x.B, x.H, x.W, x.C, _p(affine), _p(y), y.ld, _stream()), "avgpool2_fwd")
+
+
+def avgpool2_bwd(dy: Act, dx: Act):
+    """dx = dy / 4 per cell pixel, 0 in a dropped trailing row / column; dx has the un-pooled size."""
+    check(_lib.lib().unetrir_avgpool2_bwd_f32(_p(dy), dy.ld, dx.B, dx.H, dx.W, dx.C, _p(dx), dx.ld, _stream()), "avgpool2_bwd")
+
+
+def gap_fwd(x: Act, affine, y: Act):
+    """GlobalAveragePooling2D (cnn_clas.py:40) of x * scale + shift: [B,h,w,C] -> [B,1,1,C]."""
+    check(_lib.lib().unetrir_gap_fwd_f32(_p(x), x.ld, x.B, x.H, x.W, x.C, _p(affine), _p(y), y.ld, _stream()), "gap_fwd")
+
+
+def gap_bwd(dy: Act, dx: Act):
+    check(_lib.lib().unetrir_gap_bwd_f32(_p(dy), dy.ld, dx.B, dx.H, dx.W, dx.C, _p(dx), dx.ld, _stream()), "gap_bwd")
+
+
+def softmax_ce(logits: Act, classes, target, inv_norm, probs, dlogits: Act, loss_out, acc_out):
+    """Dense(classes, softmax) output + categorical_crossentropy (cnn_clas.py:49, :63) + accuracy count in one launch: probs
+    [B, classes], dlogits, loss_out[0:3], acc_out[0] (include/unetrir.h)."""
+    check(_lib.lib().unetrir_softmax_ce_f32(_p(logits), logits.ld, _p(target), logits.P, int(classes), float(inv_norm), _p(probs),
+                                            _p(dlogits), dlogits.ld, _p(loss_out), _p(acc_out), _stream()), "softmax_ce")
+
+
+def softmax_fwd(logits: Act, classes, probs):
+    check(_lib.lib().unetrir_softmax_fwd_f32(_p(logits), logits.ld, logits.P, int(classes), _p(probs), _stream()), "softmax_fwd")
+
+
+def softmax_bwd(probs, dprobs, classes, dlogits: Act):
+    """dlogits from an upstream gradient on the probabilities."""
+    check(_lib.lib().unetrir_softmax_bwd_f32(_p(probs), _p(dprobs), dlogits.P, int(classes), _p(dlogits), dlogits.ld, _stream()),
+          "softmax_bwd")

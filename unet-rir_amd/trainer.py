@@ -308,13 +308,17 @@ class Trainer:
         eng, rt = self.engine, self.rt
         eng.use_device_counters(True)          # (re-)synchronises the device counters when another path ran in between
         if self._g_in is None:
-            if emb.dtype not in (torch.int32, torch.int64):
+            if emb is not None and emb.dtype not in (torch.int32, torch.int64):
                 emb = emb.to(torch.int64)
-            self._g_in = (spec_in.to(eng.device, torch.float32).contiguous().clone(), emb.to(eng.device).contiguous().clone(),
+            self._g_in = (spec_in.to(eng.device, torch.float32).contiguous().clone(),
+                          None if emb is None else emb.to(eng.device).contiguous().clone(),      # None: an engine without an information vector
                           spec_out.to(eng.device, torch.float32).contiguous().clone())
         for dst, src in zip(self._g_in, (spec_in, emb, spec_out)):
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError(f"graph step: input shape {tuple(src.shape)} differs from the captured {tuple(dst.shape)}")
+            if dst is None and src is None:
+                continue
+            if dst is None or src is None or tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"graph step: input shape {None if src is None else tuple(src.shape)} differs from the captured "
+                                 f"{None if dst is None else tuple(dst.shape)}")
             if src.data_ptr() != dst.data_ptr():
                 dst.copy_(src, non_blocking=True)
         eng.set_step_cfg(self._lr_now)
@@ -465,10 +469,16 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
     `*_amp` / `*_phase` = tf.keras.metrics.Mean over every (b, h, w) element of (a - a^)^2 and 1 - cos(...) across steps and
     replicas (main_training.py:239-244, :279-284).  The validation pass calls the model with training=True as the reference's
     test_step does (main_training.py:297-300): batch statistics, dropout active - and, as in Keras, the BatchNorm moving
-    statistics move during it (`val_updates_moving=False` keeps them at their post-training values instead)."""
+    statistics move during it (`val_updates_moving=False` keeps them at their post-training values instead).
+
+    An engine with a device counter `acc_out` (cnn_clas.DeepCNNEngine, a classifier: batches are (x, None, one-hot target)) adds
+    `train_acc` / `val_acc` = correct rows over rows seen, across steps and replicas (History.train_acc_history of the legacy
+    trainer.py:230), accumulated on the device and read back once per epoch.  For such an engine `train_amp` / `val_amp` carry the
+    mean cross-entropy per row and `train_phase` / `val_phase` are 0."""
     eng = trainer.engine
     lr0 = trainer.lr if lr0 is None else lr0
-    per_elem = 1.0 / (eng.H * eng.W * eng.B * trainer.world_size)       # loss_out[1:3] are raw per-replica sums of the two terms
+    has_acc = hasattr(eng, "acc_out")          # a classifier: loss_out[1] is the raw cross-entropy sum over the rows
+    per_elem = 1.0 / ((1 if has_acc else eng.H * eng.W) * eng.B * trainer.world_size)       # loss_out[1:3] are raw per-replica sums of the two terms
     history = []
 
     def reduce_(t):
@@ -484,6 +494,7 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         ktot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_kl else None      # raw KL sums: training, validation
         has_vq = hasattr(eng, "vq_out")           # VQ-VAE: the quantiser's S = sum (q - x)^2 of every step (dl_models/vqvae.py:79-80)
         qtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_vq else None
+        atot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_acc else None       # correct rows: training, validation
         eng.reg_loss()
         reg0 = eng.reg_out[0].double()           # l2 terms on the weights the first step of the epoch sees
         for spec_in, emb, spec_out in train_batches(epoch):
@@ -493,6 +504,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 ktot[0] += eng.kl_out[1].double()
             if has_vq:
                 qtot[0] += eng.vq_out[1].double()
+            if has_acc:
+                atot[0] += eng.acc_out[0].double()
             nb += 1
         # the l2 terms drift over an epoch (Adam moves every weight by ~lr per step whatever the gradient's scale): the reported
         # mean takes the trapezoid of their value before the first and after the last step instead of nine reductions per step
@@ -508,6 +521,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         if has_vq:         # mean((q - x)^2) over every element, across steps and replicas
             per_vq = 1.0 / (eng.vq_elems * trainer.world_size)
             rec["train_vq"] = float(reduce_(qtot[0:1].clone())[0]) * per_vq / n
+        if has_acc and val_batches is None:        # with a validation pass: both counts in one read-back behind it
+            rec["train_acc"] = float(reduce_(atot.clone())[0]) / (n * eng.B * trainer.world_size)
         if val_batches is not None:
             vt = torch.zeros(3, dtype=torch.float64, device=eng.device)
             vb = 0
@@ -522,6 +537,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                     ktot[1] += eng.kl_out[1].double()
                 if has_vq:
                     qtot[1] += eng.vq_out[1].double()
+                if has_acc:
+                    atot[1] += eng.acc_out[0].double()
                 vb += 1
             if saved_moving is not None:
                 for k, v in saved_moving.items():
@@ -533,6 +550,10 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 rec["val_kl"] = float(reduce_(ktot[1:2].clone())[0]) * per_kl / m
             if has_vq:
                 rec["val_vq"] = float(reduce_(qtot[1:2].clone())[0]) * per_vq / m
+            if has_acc:
+                acc = reduce_(atot.clone())
+                rec["train_acc"] = float(acc[0]) / (n * eng.B * trainer.world_size)
+                rec["val_acc"] = float(acc[1]) / (m * eng.B * trainer.world_size)
         if manager is not None and epoch % 2 == 0:
             rec["checkpoint"] = manager.save(epoch=epoch)
         history.append(rec)
