@@ -636,6 +636,30 @@ int unetrir_stft_features_f32(const float* wav, int B, int T, int n_fft, int win
 int unetrir_istft_features_f32(const float* feat, int B, int H, int W, int n_bins, int n_frames, int n_fft, int win_length,
                                int hop_length, int denormalize, float* wav, unetrir_stream_t stream);
 
+/* ---- a loss on the reconstructed waveform and its gradient on the prediction (waveloss.hip; the derivation is in its header).
+ *
+ * unetrir_wave_loss_f32: pred fp32 NCHW [B][2][H][W]; y^_b = the waveform unetrir_istft_features_f32(denormalize = 1) makes of pred_b
+ * (phase_ref nullable [B][2][H][W] = the network INPUT: the reconstructed phase plane is pred + phase_ref, plane 1 of each, summed
+ * in fp32); wav_true fp32 [B][T], T = hop_length (n_frames - 1); time_weight nullable fp32 [T] (null: ones).
+ *   E_b = sum_t w[t] (y^_b[t] - y_b[t])^2;   D_b = T (norm 0) or sum_t w[t] y_b[t]^2 (norm 1);   a sample with D_b == 0 counts 0
+ *   wave_out fp64 [2] = (sum_b E_b / D_b, sum_b E_b);   loss_out nullable: loss_out[0] += weight inv_global_batch wave_out[0]
+ *   dpred nullable fp32 [B][2][H][W], every element written: d(weight inv_global_batch sum_b E_b / D_b) / d pred, exact zeros in rows
+ *   >= n_bins and columns >= n_frames - plus, with spec_target [B][2][H][W] (nullable), over all H x W the gradient on pred of the
+ *   spectrogram loss of unetrir_sigmoid_loss_ex_f32: -2 alpha inv_norm (t0 - p0) and -(1 - alpha) inv_norm 2 pi sin(ph) wgt with that
+ *   kernel's t1 -= phase_ref, wgt = phase_weight[column] (nullable [W]) and ph.  Without dpred the adjoint kernel is not launched.
+ *   wav_pred nullable fp32 [B][T]: y^, the bits of unetrir_istft_features_f32.
+ * fp64 inside, one rounding per fp32 output, fixed summation order, no atomics: two runs give the same bits and a sample's bits depend
+ * neither on B nor on its place in the batch (inv_global_batch is an argument).  ws: unetrir_wave_loss_ws_bytes(B, n_frames,
+ * hop_length) bytes, 8-byte aligned (0: a geometry the kernels do not take).
+ * UNETRIR_EINVAL before the device is touched: the geometry rules of unetrir_istft_features_f32, a null pred / wav_true / wave_out /
+ * ws, norm outside {0, 1}, a negative or non-finite weight, a non-positive or non-finite inv_global_batch, ws_bytes too small. */
+size_t unetrir_wave_loss_ws_bytes(int B, int n_frames, int hop_length);
+int unetrir_wave_loss_f32(const float* pred, const float* phase_ref, const float* wav_true, const float* time_weight, int B, int H,
+                          int W, int n_bins, int n_frames, int n_fft, int win_length, int hop_length, int norm, double weight,
+                          double inv_global_batch, const float* spec_target, const float* phase_weight, float alpha, float inv_norm,
+                          float* dpred, float* wav_pred, double* wave_out, float* loss_out, void* ws, size_t ws_bytes,
+                          unetrir_stream_t stream);
+
 /* ---- scoring of generated impulse responses: the loss block of the evaluation loop (rir_generation.py:185-225) and its per-room
  *      bookkeeping (:227-290, :311-357), on the device and without a read-back.
  *

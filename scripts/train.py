@@ -3,11 +3,13 @@
 
     python scripts/train.py --dataset ../datasets room_impulse --rooms LargeMeetingRoom --name unet --out ../results/unet
     python scripts/train.py --synthetic 8 --name vqvae --epochs 3 --lr 1e-4 --out ../results/vqvae       # no data set: 8 random batches
+    python scripts/train.py --dataset ../datasets room_impulse --wave-loss 0.1 --wave-loss-norm energy --out ../results/unet_wave
 
 The defaults are main_training.py's (:27-47): target size (144, 160, 2), LargeMeetingRoom, both arrays, debug data set, U-Net,
 alpha 0.9, no sigmoid / diff loss, 500 epochs, lr 5e-7 with the exponential decay from epoch 80, batch 16, Adam.  A run continues
 from the latest checkpoint in --out when there is one (checkpoints are written every second epoch, :363-364).  The features of
-the whole data set live on the device (unet_rir_amd.Dataset); a batch is one kernel launch.
+the whole data set live on the device (unet_rir_amd.Dataset); a batch is one kernel launch.  --wave-loss WEIGHT adds the loss on the
+reconstructed waveform (unet_rir_amd.WaveLoss): the data set then keeps the waveforms and the generators hand them out.
 """
 import argparse
 import json
@@ -67,6 +69,10 @@ def main():
     ap.add_argument("--sigmoid-loss", action="store_true")
     ap.add_argument("--diff-loss", action="store_true")
     ap.add_argument("--beta", type=float, default=0.5)
+    ap.add_argument("--wave-loss", type=float, default=None, metavar="WEIGHT",
+                    help="add WEIGHT / batch * sum_b E_b / D_b on the reconstructed waveform to the loss (needs --dataset; not for vae / vqvae / diffvae)")
+    ap.add_argument("--wave-loss-norm", choices=("mse", "energy"), default="mse",
+                    help="D_b: the number of samples (mse) or the target's energy (energy: the squared misalignment ratio)")
     ap.add_argument("--epochs", type=int, default=500)
     ap.add_argument("--lr", type=float, default=5e-7)
     ap.add_argument("--no-lr-decay", action="store_true")
@@ -83,6 +89,9 @@ def main():
     dev = torch.device("cuda:0")
     if bool(a.synthetic) == bool(a.dataset):
         raise SystemExit("give either --dataset DIR NAME or --synthetic N")
+    if a.wave_loss is not None and not a.dataset:
+        raise SystemExit("--wave-loss needs the target waveforms: give --dataset DIR NAME")
+    wave = None if a.wave_loss is None else U.WaveLoss(weight=a.wave_loss, norm=a.wave_loss_norm)
     if a.synthetic:
         batches = list(U.synthetic_batches(a.synthetic, a.batch, a.height, a.width, dev))
         model = build_model(a, dev)
@@ -97,18 +106,19 @@ def main():
         return
 
     dataset = U.Dataset(a.dataset[0], a.dataset[1], normalization=True, debugging=not a.no_debug, extract=a.extract,
-                        room=["All"] if a.rooms == ["All"] else a.rooms, array=a.arrays, device=dev, input_shape=(a.height, a.width))
+                        room=["All"] if a.rooms == ["All"] else a.rooms, array=a.arrays, device=dev, input_shape=(a.height, a.width),
+                        keep_waveforms=wave is not None)
     # shuffle=True as main_training.py:78-79 passes it - and, as there, without effect: nothing calls on_epoch_end() (fit does
     # not either), so every epoch visits the batches in the order the seeded shuffle of the constructor gave them
-    train = U.DataGenerator(dataset, batch_size=a.batch, partition="train", shuffle=True)
-    val = U.DataGenerator(dataset, batch_size=a.batch, partition="val", shuffle=True)
+    train = U.DataGenerator(dataset, batch_size=a.batch, partition="train", shuffle=True, characteristics=wave is not None)
+    val = U.DataGenerator(dataset, batch_size=a.batch, partition="val", shuffle=True, characteristics=wave is not None)
     print(f"{len(dataset)} files, {len(dataset.index_in)} pairs: {len(train)} training and {len(val)} validation batches of {a.batch}")
     if len(train) == 0:
         raise SystemExit("the training partition holds less than one batch")
 
     model = build_model(a, dev)
     trainer = U.Trainer(model, lr=a.lr, alpha=a.alpha, sigmoid_loss=a.sigmoid_loss, diff_loss=a.diff_loss, beta=a.beta,
-                        optimizer=a.optimizer)
+                        optimizer=a.optimizer, wave_loss=wave)
     manager = U.CheckpointManager(trainer, a.out, max_to_keep=2)
     start = 0
     if manager.latest_checkpoint is not None:

@@ -185,6 +185,11 @@ _SIGS = {
                                             c_f32p, C.c_int, C.c_int, c_stream]),
     "unetrir_istft_features_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, c_f32p, c_stream]),
+    # waveform-domain loss and its gradient on the prediction (waveloss.hip)
+    "unetrir_wave_loss_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unetrir_wave_loss_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_double, C.c_double, c_f32p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p,
+                                        C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "unetrir_eval_metrics_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int,
                                            C.c_void_p, c_stream]),
     "unetrir_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),

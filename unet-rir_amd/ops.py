@@ -633,6 +633,50 @@ def istft_features(feat, wav, n_bins, n_frames, n_fft=256, win_length=128, hop_l
                                                 int(denormalize), _p(wav), _stream()), "istft_features")
 
 
+WAVE_NORMS = {"mse": 0, "energy": 1}
+
+
+def wave_loss_ws_bytes(B, n_frames, hop_length):
+    """Bytes of fp64 state `wave_loss` keeps in its workspace (0: a geometry the kernels do not take)."""
+    return int(_lib.lib().unetrir_wave_loss_ws_bytes(int(B), int(n_frames), int(hop_length)))
+
+
+def wave_loss(pred, wav_true, wave_out, ws: Workspace, n_bins, n_frames, n_fft=256, win_length=128, hop_length=64, norm="mse",
+              weight=1.0, global_batch=None, time_weight=None, phase_ref=None, spec_target=None, alpha=0.9, inv_norm=None,
+              phase_weight=None, dpred=None, wav_pred=None, loss_out=None):
+    """The loss on the waveform PostProcess makes of pred fp32 [B, 2, H, W] against wav_true fp32 [B, hop (n_frames - 1)], and (with
+    dpred, fp32 like pred) its gradient on pred, plus (with spec_target) that of the spectrogram loss: wave_out fp64 [2] = (sum_b E_b /
+    D_b, sum_b E_b); loss_out[0] += weight / global_batch * wave_out[0]; wav_pred receives the waveform (include/unetrir.h)."""
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda or pred.dim() != 4 or pred.shape[1] != 2:
+        raise ValueError("wave_loss: pred must be a CUDA tensor [B, 2, H, W]")
+    if norm not in WAVE_NORMS:
+        raise ValueError(f"norm must be one of {sorted(WAVE_NORMS)}")
+    B, _, H, W = pred.shape
+    T = hop_length * (n_frames - 1)
+    _f32c(pred, pred.shape, "pred", pred)
+    _f32c(wav_true, (B, T), "wav_true", pred)
+    for t, shape, what in ((time_weight, (T,), "time_weight"), (phase_ref, pred.shape, "phase_ref"), (spec_target, pred.shape, "spec_target"),
+                           (phase_weight, (W,), "phase_weight"), (dpred, pred.shape, "dpred"), (wav_pred, (B, T), "wav_pred")):
+        if t is not None:
+            _f32c(t, shape, what, pred)
+    if wave_out.dtype != torch.float64 or not wave_out.is_contiguous() or tuple(wave_out.shape) != (2,) or wave_out.device != pred.device:
+        raise ValueError(f"wave_loss: wave_out must be a contiguous float64 [2] tensor on {pred.device}")
+    if loss_out is not None and (loss_out.dtype != torch.float32 or loss_out.dim() != 1 or loss_out.numel() < 1 or
+                                 not loss_out.is_contiguous() or loss_out.device != pred.device):
+        raise ValueError(f"wave_loss: loss_out must be a contiguous float32 vector on {pred.device}")
+    if spec_target is not None and inv_norm is None:
+        raise ValueError("wave_loss: the spectrogram term needs inv_norm (the loss kernel's 1 / (2 H W global_batch))")
+    gb = B if global_batch is None else global_batch
+    need = wave_loss_ws_bytes(B, n_frames, hop_length)
+    if need:
+        ws.reserve(need)
+    check(_lib.lib().unetrir_wave_loss_f32(_p(pred), _p(phase_ref), _p(wav_true), _p(time_weight), B, H, W, int(n_bins), int(n_frames),
+                                           int(n_fft), int(win_length), int(hop_length), WAVE_NORMS[norm], float(weight), 1.0 / gb,
+                                           _p(spec_target), _p(phase_weight), float(alpha), 0.0 if inv_norm is None else float(inv_norm),
+                                           _p(dpred), _p(wav_pred), _p(wave_out), _p(loss_out), ws.ptr, ws.nbytes, _stream()),
+          "wave_loss")
+
+
 def griffinlim_ws_bytes(B, n_bins, n_frames, n_fft):
     """Bytes of fp64 state `griffinlim` keeps in its workspace (0: a geometry the kernels do not take)."""
     return int(_lib.lib().unetrir_griffinlim_ws_bytes(int(B), int(n_bins), int(n_frames), int(n_fft)))

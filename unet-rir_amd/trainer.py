@@ -133,7 +133,7 @@ class Trainer:
     """
 
     def __init__(self, model, lr=None, alpha=0.9, world_size=1, group=None, bucket_bytes=32 << 20, dropout=True, force_dp=False,
-                 sigmoid_loss=False, diff_loss=False, beta=0.5, graph=False, dropout_seed=None, optimizer="adam"):
+                 sigmoid_loss=False, diff_loss=False, beta=0.5, graph=False, dropout_seed=None, optimizer="adam", wave_loss=None):
         """force_dp: run the bucketed all-reduce path even at world_size 1 (needs an initialised process group; rehearsal).
         sigmoid_loss / diff_loss / beta: the switches of compute_loss (main_training.py:38-40, :214-222; both False in the
         reference's live configuration): column weights sigmoid(beta, ...) of preprocess.py:116-121 on the phase term, and the
@@ -145,7 +145,11 @@ class Trainer:
         or a `unet_rir_amd.LAMB(...)` object: tfa.optimizers.LAMB of the legacy trainer (trainer.py:37-38).
         lr: the rate of every step that is not given one (`step(..., lr=)`).  Default 5e-7, or the LAMB object's learning_rate.
         dropout_seed: base seed of the Dropout streams; replica r draws from stream seed + r (independent masks per replica, as
-        under MirroredStrategy).  Default: the engine's own seed (torch.initial_seed())."""
+        under MirroredStrategy).  Default: the engine's own seed (torch.initial_seed()).
+        wave_loss: a `unet_rir_amd.WaveLoss` - every step then also minimises weight / global batch * sum_b E_b / D_b on the waveform
+        the prediction reconstructs to (`step(..., wav_true=)`): the loss kernel runs as before (loss_out[1:3] keep their meaning,
+        loss_out[0] grows by the term), and the backward pass starts from dL/dpred of both terms (csrc/waveloss.hip) instead of the
+        loss kernel's dL/dlogits.  Engines with a loss term or target of their own (VAE, VQ-VAE, the classifier) are refused."""
         self.module = None
         engine = model
         if not hasattr(model, "specs") and hasattr(model, "engine"):
@@ -155,6 +159,12 @@ class Trainer:
                 raise RuntimeError("build the model first (batch_size=...): the trainer drives the engine of one batch size")
         self.engine = engine
         self.rt = engine.rt
+        if wave_loss is not None:
+            own = [n for n in ("kl_out", "vq_out", "acc_out") if hasattr(engine, n)]
+            if own:
+                raise ValueError(f"wave_loss: {type(engine).__name__} has a loss term or target of its own ({own[0]}); the waveform loss "
+                                 "drives the spectrogram models only")
+        self.wave_loss = wave_loss
         if lr is None:
             lr = optimizer.learning_rate if isinstance(optimizer, LAMB) else 5e-7
         self.lr, self.alpha = lr, alpha
@@ -218,16 +228,17 @@ class Trainer:
             self.engine.adam_range(lo, hi, *self._adam_args)
 
     # ---- the three phases of a step after the forward pass
-    def _backward_and_reduce(self):
-        """tape.gradient + the cross-replica SUM (+ Adam of every bucket that is final, when the optimizer has its own stream)."""
+    def _backward_and_reduce(self, dpred=None):
+        """tape.gradient + the cross-replica SUM (+ Adam of every bucket that is final, when the optimizer has its own stream).
+        dpred: dL/dpred (NCHW) to start from instead of the loss kernel's dL/dlogits (the waveform loss)."""
         eng = self.engine
         if self.adam_stream is not None:
             self._adam_args = eng.adam_begin(self._lr_now)
         if self.bucketer is not None:
             self.bucketer.reset()
-            eng.backward(on_ready=self.bucketer.mark_ready)
+            eng.backward(on_ready=self.bucketer.mark_ready, dpred=dpred)
         else:
-            eng.backward()
+            eng.backward(dpred=dpred)
         self._pending = True
 
     def apply_gradients(self):
@@ -255,7 +266,7 @@ class Trainer:
                 return eng.make_dropout_mask()
         return eng.make_dropout_mask()
 
-    def _step_body(self, spec_in, emb, spec_out, dropout_mask, with_reg):
+    def _step_body(self, spec_in, emb, spec_out, dropout_mask, with_reg, wav_true=None):
         """The launches of one step (what a HIP graph captures)."""
         eng = self.engine
         # device counters only; an engine's own noise (VAE: eps of the sampling layer) is drawn whatever the Dropout setting
@@ -266,21 +277,32 @@ class Trainer:
         eng.forward(spec_in, emb, dropout_mask=dropout_mask, target=spec_out, global_batch=gb, alpha=self.alpha)
         if with_reg:
             eng.reg_loss()                      # on the pre-update weights, as compute_loss sees them
-        self._backward_and_reduce()
+        dpred = None
+        if self.wave_loss is not None:
+            # on the current stream, behind the loss kernel: dL/dpred of the waveform term and of the spectrogram term in one launch
+            dpred = self.wave_loss(eng.pred, wav_true, phase_ref=spec_in if eng.loss_diff else None, spec_target=spec_out, alpha=self.alpha,
+                                   inv_norm=1.0 / (2.0 * eng.H * eng.W * gb), phase_weight=eng.loss_phase_weight, global_batch=gb,
+                                   loss_out=eng.loss_out)
+        self._backward_and_reduce(dpred)
         self.apply_gradients()
 
-    def step(self, spec_in, emb, spec_out, dropout_mask=None, lr=None, return_loss=False):
-        """inputs as DataGenerator.__getitem__ yields them (datageneratorv2.py:101-102), NCHW, per-replica shard."""
+    def step(self, spec_in, emb, spec_out, dropout_mask=None, lr=None, return_loss=False, wav_true=None):
+        """inputs as DataGenerator.__getitem__ yields them (datageneratorv2.py:101-102), NCHW, per-replica shard.  wav_true fp32
+        [B, T]: the target waveforms, with a `wave_loss` (DataGenerator(characteristics=True) delivers them)."""
         eng = self.engine
+        if self.wave_loss is not None and wav_true is None:
+            raise ValueError("this trainer has a wave_loss: step(..., wav_true=) needs the target waveforms")
+        if self.wave_loss is None:
+            wav_true = None
         eng.training = True
         self._total_on_device = False
         self._lr_now = self.lr if lr is None else lr
         if self.use_graph and dropout_mask is None:
-            self._graph_step(spec_in, emb, spec_out, bool(return_loss))
+            self._graph_step(spec_in, emb, spec_out, bool(return_loss), wav_true)
         else:
             if self.use_graph:
                 eng.use_device_counters(False)     # e.g. an externally supplied mask: launch arguments from the host again
-            self._step_body(spec_in, emb, spec_out, dropout_mask, return_loss)
+            self._step_body(spec_in, emb, spec_out, dropout_mask, return_loss, wav_true)
         if return_loss:
             return self.last_loss()
         return None
@@ -301,7 +323,7 @@ class Trainer:
         eng.t_dirty = True
         eng.sync_device_counters()
 
-    def _graph_step(self, spec_in, emb, spec_out, with_reg):
+    def _graph_step(self, spec_in, emb, spec_out, with_reg, wav_true=None):
         """Replay the captured step on copies of the inputs.  First call (per variant: with / without the l2 terms of the reported
         loss): one ordinary step with the counters in device memory - every lazily created buffer, table and workspace then
         exists - undone from a snapshot, then the capture."""
@@ -312,8 +334,9 @@ class Trainer:
                 emb = emb.to(torch.int64)
             self._g_in = (spec_in.to(eng.device, torch.float32).contiguous().clone(),
                           None if emb is None else emb.to(eng.device).contiguous().clone(),      # None: an engine without an information vector
-                          spec_out.to(eng.device, torch.float32).contiguous().clone())
-        for dst, src in zip(self._g_in, (spec_in, emb, spec_out)):
+                          spec_out.to(eng.device, torch.float32).contiguous().clone(),
+                          None if wav_true is None else wav_true.to(eng.device, torch.float32).contiguous().clone())    # with a wave_loss
+        for dst, src in zip(self._g_in, (spec_in, emb, spec_out, wav_true)):
             if dst is None and src is None:
                 continue
             if dst is None or src is None or tuple(src.shape) != tuple(dst.shape):
@@ -325,7 +348,7 @@ class Trainer:
         g = self._graphs.get(with_reg)
         if g is None:
             snap = self._snapshot()
-            self._step_body(*self._g_in, None, with_reg)
+            self._step_body(*self._g_in[:3], None, with_reg, self._g_in[3])
             rt.synchronize()
             self._restore(snap)
             rt.synchronize()
@@ -341,7 +364,7 @@ class Trainer:
             gc.disable()
             try:
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._step_body(*self._g_in, None, with_reg)
+                    self._step_body(*self._g_in[:3], None, with_reg, self._g_in[3])
             finally:
                 if gc_was_on:
                     gc.enable()
@@ -474,8 +497,24 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
     An engine with a device counter `acc_out` (cnn_clas.DeepCNNEngine, a classifier: batches are (x, None, one-hot target)) adds
     `train_acc` / `val_acc` = correct rows over rows seen, across steps and replicas (History.train_acc_history of the legacy
     trainer.py:230), accumulated on the device and read back once per epoch.  For such an engine `train_amp` / `val_amp` carry the
-    mean cross-entropy per row and `train_phase` / `val_phase` are 0."""
+    mean cross-entropy per row and `train_phase` / `val_phase` are 0.
+
+    With `trainer.wave_loss` a batch is (spec_in, emb, spec_out, wav_true) or DataGenerator(characteristics=True)'s (spec_in, emb,
+    spec_out, (room, wav_true)), and the record gains `train_wave` / `val_wave`: the mean of E_b / D_b over samples, steps and
+    replicas, accumulated on the device and read back once per epoch (the validation pass runs the loss alone, without its gradient).
+    `train_loss` / `val_loss` carry the term."""
     eng = trainer.engine
+    wl = trainer.wave_loss
+
+    def unpack(batch):
+        """(spec_in, emb, spec_out, wav_true or None)"""
+        if wl is None:
+            spec_in, emb, spec_out = batch
+            return spec_in, emb, spec_out, None
+        if len(batch) != 4:
+            raise ValueError("a trainer with a wave_loss takes batches (spec_in, emb, spec_out, wav_true) or (..., (room, wav_true))")
+        spec_in, emb, spec_out, extra = batch
+        return spec_in, emb, spec_out, extra[1] if isinstance(extra, (tuple, list)) else extra
     lr0 = trainer.lr if lr0 is None else lr0
     has_acc = hasattr(eng, "acc_out")          # a classifier: loss_out[1] is the raw cross-entropy sum over the rows
     per_elem = 1.0 / ((1 if has_acc else eng.H * eng.W) * eng.B * trainer.world_size)       # loss_out[1:3] are raw per-replica sums of the two terms
@@ -495,10 +534,14 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         has_vq = hasattr(eng, "vq_out")           # VQ-VAE: the quantiser's S = sum (q - x)^2 of every step (dl_models/vqvae.py:79-80)
         qtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_vq else None
         atot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_acc else None       # correct rows: training, validation
+        wtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if wl is not None else None      # sum_b E_b / D_b: training, validation
         eng.reg_loss()
         reg0 = eng.reg_out[0].double()           # l2 terms on the weights the first step of the epoch sees
-        for spec_in, emb, spec_out in train_batches(epoch):
-            trainer.step(spec_in, emb, spec_out, lr=lr)
+        for batch in train_batches(epoch):
+            spec_in, emb, spec_out, wav_true = unpack(batch)
+            trainer.step(spec_in, emb, spec_out, lr=lr, wav_true=wav_true)
+            if wl is not None:
+                wtot[0] += wl.wave_out[0]
             tot[:3] += eng.loss_out[:3].double()     # total data loss, amplitude term, phase term of this step (raw sums ~1e5: fp64)
             if has_kl:
                 ktot[0] += eng.kl_out[1].double()
@@ -521,17 +564,24 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         if has_vq:         # mean((q - x)^2) over every element, across steps and replicas
             per_vq = 1.0 / (eng.vq_elems * trainer.world_size)
             rec["train_vq"] = float(reduce_(qtot[0:1].clone())[0]) * per_vq / n
+        if wl is not None and val_batches is None:        # with a validation pass: both sums in one read-back behind it
+            rec["train_wave"] = float(reduce_(wtot.clone())[0]) / (n * eng.B * trainer.world_size)
         if has_acc and val_batches is None:        # with a validation pass: both counts in one read-back behind it
             rec["train_acc"] = float(reduce_(atot.clone())[0]) / (n * eng.B * trainer.world_size)
         if val_batches is not None:
             vt = torch.zeros(3, dtype=torch.float64, device=eng.device)
             vb = 0
             saved_moving = None if val_updates_moving else {k: v.clone() for k, v in eng.moving.items()}
-            for spec_in, emb, spec_out in val_batches(epoch):
+            for batch in val_batches(epoch):
+                spec_in, emb, spec_out, wav_true = unpack(batch)
                 eng.training = True
                 eng.begin_step(lr, n_draws=(eng.n_dropout_draws if trainer.dropout else 0) + eng.n_noise_draws, forward_only=True)     # device counters only
                 mask = eng.make_dropout_mask() if trainer.dropout else None
                 eng.forward(spec_in, emb, dropout_mask=mask, target=spec_out, global_batch=eng.B * trainer.world_size, alpha=trainer.alpha)
+                if wl is not None:
+                    wl(eng.pred, wav_true, phase_ref=spec_in if eng.loss_diff else None, global_batch=eng.B * trainer.world_size,
+                       loss_out=eng.loss_out, backward=False)
+                    wtot[1] += wl.wave_out[0]
                 vt += eng.loss_out[:3].double()
                 if has_kl:
                     ktot[1] += eng.kl_out[1].double()
@@ -550,6 +600,10 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 rec["val_kl"] = float(reduce_(ktot[1:2].clone())[0]) * per_kl / m
             if has_vq:
                 rec["val_vq"] = float(reduce_(qtot[1:2].clone())[0]) * per_vq / m
+            if wl is not None:
+                wv = reduce_(wtot.clone())
+                rec["train_wave"] = float(wv[0]) / (n * eng.B * trainer.world_size)
+                rec["val_wave"] = float(wv[1]) / (m * eng.B * trainer.world_size)
             if has_acc:
                 acc = reduce_(atot.clone())
                 rec["train_acc"] = float(acc[0]) / (n * eng.B * trainer.world_size)
