@@ -660,6 +660,24 @@ int unetrir_wave_loss_f32(const float* pred, const float* phase_ref, const float
                           float* dpred, float* wav_pred, double* wave_out, float* loss_out, void* ws, size_t ws_bytes,
                           unetrir_stream_t stream);
 
+/* ---- auralization: dry audio rendered through impulse responses, y_b = h_b * x_b (auralize.hip; the formulation is in its header).
+ *
+ * unetrir_auralize_f32: rir fp32 [B][K] (h); dry fp32 [N] with dry_stride = 0 (one dry signal for all rows) or [B][dry_stride], dry_stride
+ * >= N (one per row); out fp32 [B][L], 1 <= L <= N + K - 1 - the first L samples of the full convolution:
+ *   out[b][n] = sum_{k=0}^{K-1} h_b[k] x_b[n - k],   x_b[m] = 0 outside 0 <= m < N.
+ * Direct form in ONE launch on v_mfma_f32_32x32x2_f32, no workspace, no atomics; every element of out written exactly once and nothing
+ * beyond it.  Summation order: fp32 throughout, one fma per tap in ascending k onto an accumulator that starts at +0,
+ *   out[b][n] = fma(h[K-1], x[n-K+1], ... fma(h[1], x[n-1], fma(h[0], x[n], +0)) ...)      (taps that fall outside x add exact zeros),
+ * so the bits of an element depend on (h_b, x_b, n) alone: not on B, the row's place in the batch, L (a truncated call returns the
+ * head of the full result), dry_stride (shared or per row) or the run; on integer data whose partial sums stay below 2^24 the result
+ * is exact.  Inputs are taken to be finite.  unetrir_auralize_supported(K): 1 for 1 <= K <= 16384 (h chunks and the x window of a
+ * workgroup share the 160 KB of LDS), else 0.
+ * UNETRIR_EINVAL before the device is touched: a null pointer, B, K or N < 1, K unsupported, L outside 1 ... N + K - 1, a dry_stride
+ * other than 0 or >= N (and a launch of more than 2^31 - 1 workgroups: B * ceil(L / 16384)). */
+int unetrir_auralize_supported(int K);
+int unetrir_auralize_f32(const float* rir, const float* dry, float* out, int B, int K, int N, long long dry_stride, int L,
+                         unetrir_stream_t stream);
+
 /* ---- scoring of generated impulse responses: the loss block of the evaluation loop (rir_generation.py:185-225) and its per-room
  *      bookkeeping (:227-290, :311-357), on the device and without a read-back.
  *

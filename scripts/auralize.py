@@ -1,0 +1,131 @@
+"""Render a dry recording through impulse responses, on the device: one .wav per position (unet_rir_amd.auralize).
+
+    python scripts/auralize.py --rirs RIR_DIR --dry speech.wav --out OUT_DIR
+    python scripts/auralize.py --checkpoint CKPT_DIR --filters 32 --kernels 3 --data BATCH_DIR --dry speech.wav --out OUT_DIR
+    python scripts/auralize.py --load SAVED_MODEL_DIR --arch aenet --synthetic 1 --dry speech.wav --out OUT_DIR [--diff-gen]
+
+--rirs         a directory of impulse-response .wav files (sorted by name), read by `read_wav`'s rules: --sr Hz, the first --duration
+               seconds, mean removed; no resampler
+--load / --checkpoint / --arch / --filters / --kernels / --latent / --height / --width
+               a model, as scripts/evaluate.py takes it; its responses are generated from --data (a directory of .npz batches with
+               spec_in and emb, as scripts/evaluate.py reads them) or --synthetic N batches, and reconstructed by PostProcess
+               (--diff-gen: the predicted phase is a difference to the input's)
+--dry          the dry recording: a .wav file at --sr, read whole by the same rules (channels averaged, mean removed)
+--length       full (default: N + K - 1 samples), same (N) or a number of samples
+--out          OUT_DIR/NAME.wav per position, 32-bit float at --sr: NAME is the response's file name, or b{batch}_{row} for generated ones
+--peak         scale every output file so that the loudest sample of the whole set is this (default: values as computed)
+"""
+import argparse
+import glob
+import os
+import struct
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import unet_rir_amd as U
+from unet_rir_amd.auralize import write_wav
+from unet_rir_amd.features import PostProcess
+
+
+def wav_frames(path):
+    """Frames in a RIFF/WAVE file, from its 'fmt ' and 'data' chunks."""
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise SystemExit(f"{path}: not a RIFF/WAVE file")
+        align = None
+        while True:
+            ck = f.read(8)
+            if len(ck) < 8:
+                raise SystemExit(f"{path}: no data chunk")
+            name, size = struct.unpack("<4sI", ck)
+            if name == b"fmt ":
+                align = struct.unpack("<HHIIHH", f.read(16))[4]
+                f.seek(size - 16 + (size & 1), 1)
+            elif name == b"data":
+                if not align:
+                    raise SystemExit(f"{path}: data before fmt")
+                return size // align
+            else:
+                f.seek(size + (size & 1), 1)
+
+
+def rir_batches(a, dev):
+    files = sorted(glob.glob(os.path.join(a.rirs, "*.wav")))
+    if not files:
+        raise SystemExit(f"no .wav files in {a.rirs}")
+    for i in range(0, len(files), a.batch):
+        part = files[i:i + a.batch]
+        wav = np.stack([U.read_wav(f, a.sr, a.duration) for f in part])
+        yield [os.path.splitext(os.path.basename(f))[0] for f in part], torch.from_numpy(wav).to(dev)
+
+
+def model_batches(a, dev):
+    import evaluate as E                                         # scripts/evaluate.py: the same model and batch sources
+    model = E.build_model(a, dev)
+    post = PostProcess()
+    for k, batch in enumerate(E.file_batches(a.data, dev) if a.data else E.synthetic(a, dev)):
+        spec_in, emb = batch[0], batch[1]
+        nhwc = spec_in if spec_in.shape[-1] == 2 else spec_in.permute(0, 2, 3, 1)
+        with torch.no_grad():
+            pred = model.model([nhwc, emb], training=False)      # NHWC
+        feat = pred.permute(0, 3, 1, 2).contiguous().float()
+        if a.diff_gen:
+            feat[:, 1] += nhwc.permute(0, 3, 1, 2)[:, 1]
+        wav = post.post_process(feat, nhwc=False)
+        yield [f"b{k:04d}_{j:02d}" for j in range(wav.shape[0])], wav
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rirs")
+    ap.add_argument("--load")
+    ap.add_argument("--checkpoint")
+    ap.add_argument("--arch", choices=("unet", "resae", "ae", "vae", "vqvae", "aenet", "diffunet", "diffvae"), default="unet")
+    ap.add_argument("--latent", type=int, default=32)
+    ap.add_argument("--filters", type=int, default=32)
+    ap.add_argument("--kernels", type=int, default=3)
+    ap.add_argument("--height", type=int, default=144)
+    ap.add_argument("--width", type=int, default=160)
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--data")
+    ap.add_argument("--synthetic", type=int, default=0)
+    ap.add_argument("--diff-gen", action="store_true")
+    ap.add_argument("--name", default="unet")
+    ap.add_argument("--dry", required=True)
+    ap.add_argument("--sr", type=int, default=48000)
+    ap.add_argument("--duration", type=float, default=0.2, help="seconds of every --rirs file that are used")
+    ap.add_argument("--length", default="full")
+    ap.add_argument("--peak", type=float, default=None)
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args()
+    generated = bool(a.load or a.checkpoint or a.data or a.synthetic)
+    if bool(a.rirs) == generated:
+        raise SystemExit("give either --rirs, or a model (--load / --checkpoint) with --data or --synthetic")
+    if generated and bool(a.data) == bool(a.synthetic):
+        raise SystemExit("a model needs exactly one of --data and --synthetic")
+    length = a.length if a.length in ("full", "same") else int(a.length)
+    if not torch.cuda.is_available():
+        raise SystemExit("auralization runs on the GPU; there is none here")
+    dev = torch.device("cuda:0")
+    frames = wav_frames(a.dry)
+    dry = torch.from_numpy(U.read_wav(a.dry, a.sr, (frames + 0.5) / a.sr)).to(dev)
+    os.makedirs(a.out, exist_ok=True)
+    rendered = []
+    for names, wav in (rir_batches(a, dev) if a.rirs else model_batches(a, dev)):
+        wet = U.auralize(wav, dry, length=length).cpu().numpy()
+        rendered += list(zip(names, wet))
+    gain = 1.0
+    if a.peak is not None:
+        top = max(float(np.abs(w).max()) for _, w in rendered)
+        gain = a.peak / top if top > 0 else 1.0
+    for name, w in rendered:
+        write_wav(os.path.join(a.out, name + ".wav"), w * np.float32(gain), a.sr)
+    print(f"wrote {len(rendered)} files of {rendered[0][1].shape[0]} samples to {a.out} (dry: {frames} samples, gain {gain:.6g})")
+
+
+if __name__ == "__main__":
+    main()

@@ -677,6 +677,39 @@ def wave_loss(pred, wav_true, wave_out, ws: Workspace, n_bins, n_frames, n_fft=2
           "wave_loss")
 
 
+def auralize_supported(K):
+    """Whether `auralize_f32` takes impulse responses of K taps (1 <= K <= 16384)."""
+    return bool(_lib.lib().unetrir_auralize_supported(int(K)))
+
+
+def auralize_f32(rir, dry, out):
+    """out fp32 [B, L] = the first L samples of rir fp32 [B, K] convolved with dry fp32 [N] (one dry signal heard through every row) or
+    [B, N] (one per row), 1 <= L <= N + K - 1: direct form on the fp32 matrix cores in one launch on the current stream, every element
+    an fp32 fma chain in ascending tap order (include/unetrir.h)."""
+    named = ((rir, "rir"), (dry, "dry"), (out, "out"))
+    if not all(isinstance(t, torch.Tensor) for t, _ in named):
+        raise ValueError("auralize: rir, dry and out must be tensors")
+    if rir.dim() != 2 or dry.dim() not in (1, 2) or out.dim() != 2:
+        raise ValueError("auralize: rir [B, K], dry [N] or [B, N], out [B, L]")
+    B, K = rir.shape
+    N, L = dry.shape[-1], out.shape[1]
+    if (dry.dim() == 2 and dry.shape[0] != B) or out.shape[0] != B:
+        raise ValueError(f"auralize: batch sizes differ: rir {tuple(rir.shape)}, dry {tuple(dry.shape)}, out {tuple(out.shape)}")
+    if B < 1 or K < 1 or N < 1 or not 1 <= L <= N + K - 1:
+        raise ValueError(f"auralize: empty input, or {L} output samples outside 1 ... N + K - 1 = {N + K - 1}")
+    for t, what in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"auralize: {what} must be float32, not {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"auralize: {what} must be contiguous")
+    for t, what in named:
+        if not t.is_cuda or t.device != rir.device:
+            raise ValueError(f"auralize: {what} must be a CUDA tensor on the device of rir (there is no CPU path)")
+    if not auralize_supported(K):
+        raise ValueError(f"auralize: impulse responses of {K} taps are not supported (1 ... 16384)")
+    check(_lib.lib().unetrir_auralize_f32(_p(rir), _p(dry), _p(out), B, K, N, 0 if dry.dim() == 1 else N, L, _stream()), "auralize")
+
+
 def griffinlim_ws_bytes(B, n_bins, n_frames, n_fft):
     """Bytes of fp64 state `griffinlim` keeps in its workspace (0: a geometry the kernels do not take)."""
     return int(_lib.lib().unetrir_griffinlim_ws_bytes(int(B), int(n_bins), int(n_frames), int(n_fft)))
