@@ -660,6 +660,42 @@ int unetrir_wave_loss_f32(const float* pred, const float* phase_ref, const float
                           float* dpred, float* wav_pred, double* wave_out, float* loss_out, void* ws, size_t ws_bytes,
                           unetrir_stream_t stream);
 
+/* ---- the vector-Jacobian product of PostProcess (istft_bwd.hip): the adjoint of unetrir_wave_loss_f32 as an entry point of its own.
+ *
+ * unetrir_istft_features_bwd_f32: pred fp32 NCHW [B][2][H][W], phase_ref nullable with the same layout (the phase plane is pred +
+ * phase_ref, plane 1 of each, summed in fp32), dwav fp32 [B][T], T = hop_length (n_frames - 1): a cotangent on the waveform y^_b that
+ * unetrir_istft_features_f32(denormalize = 1) makes of pred_b.  dpred[b] = (d y^_b / d pred_b)^T dwav_b: the math of waveloss.hip's
+ * header with u[t] = dwav[t] / env[t] where env[t] > tiny and 0 elsewhere, env recomputed from the frames that reach a sample in
+ * ascending order.  accumulate = 0: every element of dpred is written, exact zeros in rows >= n_bins and columns >= n_frames.
+ * accumulate = 1: dpred[i] = (float)((double)dpred[i] + g), rows >= n_bins and columns >= n_frames are left untouched.
+ * One launch, no workspace, no atomics, fp64 inside with one rounding per output; two runs give the same bits and a sample's bits
+ * depend neither on B nor on its place in the batch.
+ * UNETRIR_EINVAL before the device is touched: the geometry rules of unetrir_wave_loss_f32, a null pred / dwav / dpred. */
+int unetrir_istft_features_bwd_f32(const float* pred, const float* phase_ref, const float* dwav, int B, int H, int W, int n_bins,
+                                   int n_frames, int n_fft, int win_length, int hop_length, int accumulate, float* dpred,
+                                   unetrir_stream_t stream);
+
+/* ---- a loss on the energy decay curve of the waveform and its gradient on the waveform (decayloss.hip; the derivation is in its
+ *      header).
+ *
+ * unetrir_decay_loss_f32: wav_pred (y^), wav_true (y) fp32 [B][T]; fp64 arithmetic; per row
+ *   S_x[t] = sum_{s >= t} x[s]^2;  E0 = S_y[0];  delta = 10^(-floor_db / 10);  c_x[t] = 10 log10(S_x[t] / E0 + delta)
+ *   Q_b = (1 / T) sum_t (c_y^[t] - c_y[t])^2  (dB^2);  a row with E0 == 0 counts nothing
+ *   decay_out fp64 [2] = (sum_b Q_b, rows counted);   loss_out nullable: loss_out[0] += (float)(weight inv_global_batch decay_out[0])
+ *   dwav nullable fp32 [B][T], every element written (zeros in rows that are not counted):
+ *   dwav[b][s] = weight inv_global_batch 2 y^[s] sum_{t <= s} (2 / T) (c_y^[t] - c_y[t]) (10 / ln 10) / (S_y^[t] + delta E0)
+ * Two launches whatever B is, no atomics, every order fixed: two runs give the same bits and a row's bits depend neither on B nor on
+ * its place in the batch.  unetrir_decay_loss_supported(T): 1 for 1 <= T <= 16384 (a thread's run of the row stays in registers), else
+ * 0.  ws: unetrir_decay_loss_ws_bytes(B, T) bytes, 8-byte aligned (0: B <= 0 or an unsupported T).
+ * UNETRIR_EINVAL before the device is touched: a null wav_pred / wav_true / decay_out / ws, B <= 0, an unsupported T, floor_db not
+ * finite or outside (0, 200], a negative or non-finite weight, a non-positive or non-finite inv_global_batch, ws too small or
+ * misaligned. */
+size_t unetrir_decay_loss_ws_bytes(int B, int T);
+int unetrir_decay_loss_supported(int T);
+int unetrir_decay_loss_f32(const float* wav_pred, const float* wav_true, int B, int T, double floor_db, double weight,
+                           double inv_global_batch, float* dwav, double* decay_out, float* loss_out, void* ws, size_t ws_bytes,
+                           unetrir_stream_t stream);
+
 /* ---- auralization: dry audio rendered through impulse responses, y_b = h_b * x_b (auralize.hip; the formulation is in its header).
  *
  * unetrir_auralize_f32: rir fp32 [B][K] (h); dry fp32 [N] with dry_stride = 0 (one dry signal for all rows) or [B][dry_stride], dry_stride

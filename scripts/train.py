@@ -9,7 +9,8 @@ The defaults are main_training.py's (:27-47): target size (144, 160, 2), LargeMe
 alpha 0.9, no sigmoid / diff loss, 500 epochs, lr 5e-7 with the exponential decay from epoch 80, batch 16, Adam.  A run continues
 from the latest checkpoint in --out when there is one (checkpoints are written every second epoch, :363-364).  The features of
 the whole data set live on the device (unet_rir_amd.Dataset); a batch is one kernel launch.  --wave-loss WEIGHT adds the loss on the
-reconstructed waveform (unet_rir_amd.WaveLoss): the data set then keeps the waveforms and the generators hand them out.
+reconstructed waveform (unet_rir_amd.WaveLoss) and --decay-loss WEIGHT the loss on its energy decay curve (unet_rir_amd.DecayLoss): the
+data set then keeps the waveforms and the generators hand them out.
 """
 import argparse
 import json
@@ -73,6 +74,10 @@ def main():
                     help="add WEIGHT / batch * sum_b E_b / D_b on the reconstructed waveform to the loss (needs --dataset; not for vae / vqvae / diffvae)")
     ap.add_argument("--wave-loss-norm", choices=("mse", "energy"), default="mse",
                     help="D_b: the number of samples (mse) or the target's energy (energy: the squared misalignment ratio)")
+    ap.add_argument("--decay-loss", type=float, default=None, metavar="WEIGHT",
+                    help="add WEIGHT / batch * sum_b Q_b, the mean squared dB error of the energy decay curve of the reconstructed waveform, "
+                         "to the loss (needs --dataset; not for vae / vqvae / diffvae)")
+    ap.add_argument("--decay-floor-db", type=float, default=60.0, metavar="DB", help="the decay curves are floored DB below the target's energy")
     ap.add_argument("--epochs", type=int, default=500)
     ap.add_argument("--lr", type=float, default=5e-7)
     ap.add_argument("--no-lr-decay", action="store_true")
@@ -91,7 +96,11 @@ def main():
         raise SystemExit("give either --dataset DIR NAME or --synthetic N")
     if a.wave_loss is not None and not a.dataset:
         raise SystemExit("--wave-loss needs the target waveforms: give --dataset DIR NAME")
+    if a.decay_loss is not None and not a.dataset:
+        raise SystemExit("--decay-loss needs the target waveforms: give --dataset DIR NAME")
     wave = None if a.wave_loss is None else U.WaveLoss(weight=a.wave_loss, norm=a.wave_loss_norm)
+    decay = None if a.decay_loss is None else U.DecayLoss(weight=a.decay_loss, floor_db=a.decay_floor_db)
+    wavs = wave is not None or decay is not None
     if a.synthetic:
         batches = list(U.synthetic_batches(a.synthetic, a.batch, a.height, a.width, dev))
         model = build_model(a, dev)
@@ -107,18 +116,18 @@ def main():
 
     dataset = U.Dataset(a.dataset[0], a.dataset[1], normalization=True, debugging=not a.no_debug, extract=a.extract,
                         room=["All"] if a.rooms == ["All"] else a.rooms, array=a.arrays, device=dev, input_shape=(a.height, a.width),
-                        keep_waveforms=wave is not None)
+                        keep_waveforms=wavs)
     # shuffle=True as main_training.py:78-79 passes it - and, as there, without effect: nothing calls on_epoch_end() (fit does
     # not either), so every epoch visits the batches in the order the seeded shuffle of the constructor gave them
-    train = U.DataGenerator(dataset, batch_size=a.batch, partition="train", shuffle=True, characteristics=wave is not None)
-    val = U.DataGenerator(dataset, batch_size=a.batch, partition="val", shuffle=True, characteristics=wave is not None)
+    train = U.DataGenerator(dataset, batch_size=a.batch, partition="train", shuffle=True, characteristics=wavs)
+    val = U.DataGenerator(dataset, batch_size=a.batch, partition="val", shuffle=True, characteristics=wavs)
     print(f"{len(dataset)} files, {len(dataset.index_in)} pairs: {len(train)} training and {len(val)} validation batches of {a.batch}")
     if len(train) == 0:
         raise SystemExit("the training partition holds less than one batch")
 
     model = build_model(a, dev)
     trainer = U.Trainer(model, lr=a.lr, alpha=a.alpha, sigmoid_loss=a.sigmoid_loss, diff_loss=a.diff_loss, beta=a.beta,
-                        optimizer=a.optimizer, wave_loss=wave)
+                        optimizer=a.optimizer, wave_loss=wave, decay_loss=decay)
     manager = U.CheckpointManager(trainer, a.out, max_to_keep=2)
     start = 0
     if manager.latest_checkpoint is not None:

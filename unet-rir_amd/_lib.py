@@ -190,6 +190,13 @@ _SIGS = {
     "unetrir_wave_loss_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_int, C.c_double, C.c_double, c_f32p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p,
                                         C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    # the vector-Jacobian product of PostProcess (istft_bwd.hip) and the loss on the energy decay curve (decayloss.hip)
+    "unetrir_istft_features_bwd_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, c_f32p, c_stream]),
+    "unetrir_decay_loss_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "unetrir_decay_loss_supported": (C.c_int, [C.c_int]),
+    "unetrir_decay_loss_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, c_f32p, C.c_void_p,
+                                         c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     # y = h * x on the fp32 matrix cores (auralize.hip)
     "unetrir_auralize_supported": (C.c_int, [C.c_int]),
     "unetrir_auralize_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, c_stream]),

@@ -143,6 +143,42 @@ class PostProcess:
         self.waveform = wav[0] if single else wav
         return self.waveform
 
+    @staticmethod
+    def differentiable(pred, phase_ref=None, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH, hop_length=HOP_LENGTH):
+        """post_process as an autograd node: pred fp32 [B, 2, H, W] (a leaf that requires grad, e.g. a detached copy of an engine's
+        prediction) -> waveforms fp32 [B, T].  Any torch expression on the result then trains a model: its backward() leaves
+        dL/dpred in pred.grad (csrc/istft_bwd.hip) for an engine's backward(dpred=...).  phase_ref: the network input of a
+        phase-difference model (the phase plane is pred + phase_ref); it gets no gradient."""
+        return _PostProcessFunction.apply(pred, phase_ref, (int(des_shape[0]), int(des_shape[1])), int(n_fft), int(win_length), int(hop_length))
+
+
+class _PostProcessFunction(torch.autograd.Function):
+    """forward: ops.istft_features on pred (+ phase_ref on the phase plane, in fp32); backward: ops.istft_features_bwd."""
+
+    @staticmethod
+    def forward(ctx, pred, phase_ref, des_shape, n_fft, win_length, hop_length):
+        if not isinstance(pred, torch.Tensor) or not pred.is_cuda or pred.dim() != 4 or pred.shape[1] != 2:
+            raise ValueError("PostProcess.differentiable: pred must be a CUDA tensor [B, 2, H, W]")
+        p = pred.detach().contiguous().float()
+        r = None if phase_ref is None else phase_ref.detach().contiguous().float()
+        feat = p
+        if r is not None:
+            feat = p.clone()
+            feat[:, 1] += r[:, 1]
+        wav = torch.empty((p.shape[0], hop_length * (des_shape[1] - 1)), dtype=torch.float32, device=p.device)
+        ops.istft_features(feat, wav, des_shape[0], des_shape[1], n_fft, win_length, hop_length, denormalize=True)
+        ctx.save_for_backward(p, r)
+        ctx.geo = (des_shape, n_fft, win_length, hop_length)
+        return wav
+
+    @staticmethod
+    def backward(ctx, dwav):
+        p, r = ctx.saved_tensors
+        des_shape, n_fft, win_length, hop_length = ctx.geo
+        dpred = torch.empty_like(p)
+        ops.istft_features_bwd(p, dwav.contiguous().float(), dpred, des_shape[0], des_shape[1], n_fft, win_length, hop_length, phase_ref=r)
+        return dpred, None, None, None, None, None
+
 
 class GriffinLim:
     """PostProcess with algorithm='gl' (postprocess.py:47-50, :130-131): post_process(feature) -> waveform(s) from the magnitude

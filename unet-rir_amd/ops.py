@@ -677,6 +677,57 @@ def wave_loss(pred, wav_true, wave_out, ws: Workspace, n_bins, n_frames, n_fft=2
           "wave_loss")
 
 
+def istft_features_bwd(pred, dwav, dpred, n_bins, n_frames, n_fft=256, win_length=128, hop_length=64, phase_ref=None, accumulate=False):
+    """The vector-Jacobian product of `istft_features(denormalize=True)`: pred fp32 [B, 2, H, W] and a cotangent dwav fp32
+    [B, hop (n_frames - 1)] on the waveform -> dpred fp32 like pred, written (exact zeros in the padding) or, with accumulate, added
+    to (padding untouched).  One launch (include/unetrir.h)."""
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda or pred.dim() != 4 or pred.shape[1] != 2:
+        raise ValueError("istft_features_bwd: pred must be a CUDA tensor [B, 2, H, W]")
+    B, _, H, W = pred.shape
+    _f32c(pred, pred.shape, "pred", pred)
+    _f32c(dwav, (B, hop_length * (n_frames - 1)), "dwav", pred)
+    _f32c(dpred, pred.shape, "dpred", pred)
+    if phase_ref is not None:
+        _f32c(phase_ref, pred.shape, "phase_ref", pred)
+    check(_lib.lib().unetrir_istft_features_bwd_f32(_p(pred), _p(phase_ref), _p(dwav), B, H, W, int(n_bins), int(n_frames), int(n_fft),
+                                                    int(win_length), int(hop_length), int(bool(accumulate)), _p(dpred), _stream()),
+          "istft_features_bwd")
+
+
+def decay_loss_supported(T):
+    """Whether `decay_loss` takes waveforms of T samples (1 <= T <= 16384)."""
+    return bool(_lib.lib().unetrir_decay_loss_supported(int(T)))
+
+
+def decay_loss_ws_bytes(B, T):
+    """Bytes `decay_loss` keeps in its workspace (0: a shape the kernels do not take)."""
+    return int(_lib.lib().unetrir_decay_loss_ws_bytes(int(B), int(T)))
+
+
+def decay_loss(wav_pred, wav_true, decay_out, ws: Workspace, floor_db=60.0, weight=1.0, global_batch=None, dwav=None, loss_out=None):
+    """The loss on the energy decay curves (dB, both normalised by the target's energy, floored at -floor_db) of wav_pred against
+    wav_true, fp32 [B, T], and (with dwav, fp32 like them) its gradient on wav_pred: decay_out fp64 [2] = (sum_b Q_b, rows counted);
+    loss_out[0] += weight / global_batch * decay_out[0].  Two launches (include/unetrir.h)."""
+    if not isinstance(wav_pred, torch.Tensor) or not wav_pred.is_cuda or wav_pred.dim() != 2:
+        raise ValueError("decay_loss: wav_pred must be a CUDA tensor [B, T]")
+    B, T = wav_pred.shape
+    _f32c(wav_pred, (B, T), "wav_pred", wav_pred)
+    _f32c(wav_true, (B, T), "wav_true", wav_pred)
+    if dwav is not None:
+        _f32c(dwav, (B, T), "dwav", wav_pred)
+    if decay_out.dtype != torch.float64 or not decay_out.is_contiguous() or tuple(decay_out.shape) != (2,) or decay_out.device != wav_pred.device:
+        raise ValueError(f"decay_loss: decay_out must be a contiguous float64 [2] tensor on {wav_pred.device}")
+    if loss_out is not None and (loss_out.dtype != torch.float32 or loss_out.dim() != 1 or loss_out.numel() < 1 or
+                                 not loss_out.is_contiguous() or loss_out.device != wav_pred.device):
+        raise ValueError(f"decay_loss: loss_out must be a contiguous float32 vector on {wav_pred.device}")
+    gb = B if global_batch is None else global_batch
+    need = decay_loss_ws_bytes(B, T)
+    if need:
+        ws.reserve(need)
+    check(_lib.lib().unetrir_decay_loss_f32(_p(wav_pred), _p(wav_true), B, T, float(floor_db), float(weight), 1.0 / gb, _p(dwav),
+                                            _p(decay_out), _p(loss_out), ws.ptr, ws.nbytes, _stream()), "decay_loss")
+
+
 def auralize_supported(K):
     """Whether `auralize_f32` takes impulse responses of K taps (1 <= K <= 16384)."""
     return bool(_lib.lib().unetrir_auralize_supported(int(K)))

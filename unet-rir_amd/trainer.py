@@ -133,7 +133,7 @@ class Trainer:
     """
 
     def __init__(self, model, lr=None, alpha=0.9, world_size=1, group=None, bucket_bytes=32 << 20, dropout=True, force_dp=False,
-                 sigmoid_loss=False, diff_loss=False, beta=0.5, graph=False, dropout_seed=None, optimizer="adam", wave_loss=None):
+                 sigmoid_loss=False, diff_loss=False, beta=0.5, graph=False, dropout_seed=None, optimizer="adam", wave_loss=None, decay_loss=None):
         """force_dp: run the bucketed all-reduce path even at world_size 1 (needs an initialised process group; rehearsal).
         sigmoid_loss / diff_loss / beta: the switches of compute_loss (main_training.py:38-40, :214-222; both False in the
         reference's live configuration): column weights sigmoid(beta, ...) of preprocess.py:116-121 on the phase term, and the
@@ -149,7 +149,12 @@ class Trainer:
         wave_loss: a `unet_rir_amd.WaveLoss` - every step then also minimises weight / global batch * sum_b E_b / D_b on the waveform
         the prediction reconstructs to (`step(..., wav_true=)`): the loss kernel runs as before (loss_out[1:3] keep their meaning,
         loss_out[0] grows by the term), and the backward pass starts from dL/dpred of both terms (csrc/waveloss.hip) instead of the
-        loss kernel's dL/dlogits.  Engines with a loss term or target of their own (VAE, VQ-VAE, the classifier) are refused."""
+        loss kernel's dL/dlogits.  Engines with a loss term or target of their own (VAE, VQ-VAE, the classifier) are refused.
+        decay_loss: a `unet_rir_amd.DecayLoss` - every step then also minimises weight / global batch * sum_b Q_b on the energy decay
+        curve of that waveform (csrc/decayloss.hip): behind the wave-loss call, which also hands over the waveform, the term's
+        dL/dpred is added to that call's dpred (csrc/istft_bwd.hip) and loss_out[0] grows by the term.  Without a `wave_loss` the
+        trainer keeps one of weight 0 - an exact zero whose launch yields the waveform and the spectrogram loss's dL/dpred.  The same
+        engines are refused."""
         self.module = None
         engine = model
         if not hasattr(model, "specs") and hasattr(model, "engine"):
@@ -165,6 +170,22 @@ class Trainer:
                 raise ValueError(f"wave_loss: {type(engine).__name__} has a loss term or target of its own ({own[0]}); the waveform loss "
                                  "drives the spectrogram models only")
         self.wave_loss = wave_loss
+        self.decay_loss = decay_loss
+        self._wave = wave_loss              # the WaveLoss the step calls: the user's, or with a decay_loss alone one of weight 0
+        if decay_loss is not None:
+            own = [n for n in ("kl_out", "vq_out", "acc_out") if hasattr(engine, n)]
+            if own:
+                raise ValueError(f"decay_loss: {type(engine).__name__} has a loss term or target of its own ({own[0]}); the decay loss "
+                                 "drives the spectrogram models only")
+            geo = lambda o: (o.des_shape, o.n_fft, o.win_length, o.hop_length)
+            if wave_loss is None:
+                from .waveloss import WaveLoss
+                self._wave = WaveLoss(weight=0.0, des_shape=decay_loss.des_shape, n_fft=decay_loss.n_fft, win_length=decay_loss.win_length,
+                                      hop_length=decay_loss.hop_length)
+                self._wave.prepare(engine.device, engine.B)
+            elif geo(wave_loss) != geo(decay_loss):
+                raise ValueError(f"decay_loss: its geometry {geo(decay_loss)} differs from the wave_loss's {geo(wave_loss)}")
+            decay_loss.prepare(engine.device, engine.B)
         if lr is None:
             lr = optimizer.learning_rate if isinstance(optimizer, LAMB) else 5e-7
         self.lr, self.alpha = lr, alpha
@@ -278,11 +299,16 @@ class Trainer:
         if with_reg:
             eng.reg_loss()                      # on the pre-update weights, as compute_loss sees them
         dpred = None
-        if self.wave_loss is not None:
+        if self._wave is not None:
             # on the current stream, behind the loss kernel: dL/dpred of the waveform term and of the spectrogram term in one launch
-            dpred = self.wave_loss(eng.pred, wav_true, phase_ref=spec_in if eng.loss_diff else None, spec_target=spec_out, alpha=self.alpha,
-                                   inv_norm=1.0 / (2.0 * eng.H * eng.W * gb), phase_weight=eng.loss_phase_weight, global_batch=gb,
-                                   loss_out=eng.loss_out)
+            phase_ref = spec_in if eng.loss_diff else None
+            dpred = self._wave(eng.pred, wav_true, phase_ref=phase_ref, spec_target=spec_out, alpha=self.alpha,
+                               inv_norm=1.0 / (2.0 * eng.H * eng.W * gb), phase_weight=eng.loss_phase_weight, global_batch=gb,
+                               loss_out=eng.loss_out, want_wav=self.decay_loss is not None)
+            if self.decay_loss is not None:
+                # the call above also handed over the waveform; the decay term's dL/dpred goes on top of its dpred
+                self.decay_loss(self._wave.wav_pred, wav_true, pred=eng.pred, phase_ref=phase_ref, dpred=dpred, accumulate=True,
+                                global_batch=gb, loss_out=eng.loss_out)
         self._backward_and_reduce(dpred)
         self.apply_gradients()
 
@@ -292,7 +318,9 @@ class Trainer:
         eng = self.engine
         if self.wave_loss is not None and wav_true is None:
             raise ValueError("this trainer has a wave_loss: step(..., wav_true=) needs the target waveforms")
-        if self.wave_loss is None:
+        if self.decay_loss is not None and wav_true is None:
+            raise ValueError("this trainer has a decay_loss: step(..., wav_true=) needs the target waveforms")
+        if self._wave is None:
             wav_true = None
         eng.training = True
         self._total_on_device = False
@@ -502,17 +530,23 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
     With `trainer.wave_loss` a batch is (spec_in, emb, spec_out, wav_true) or DataGenerator(characteristics=True)'s (spec_in, emb,
     spec_out, (room, wav_true)), and the record gains `train_wave` / `val_wave`: the mean of E_b / D_b over samples, steps and
     replicas, accumulated on the device and read back once per epoch (the validation pass runs the loss alone, without its gradient).
-    `train_loss` / `val_loss` carry the term."""
+    `train_loss` / `val_loss` carry the term.
+
+    With `trainer.decay_loss` the batches are those four-tuples too, and the record gains `train_decay` / `val_decay`: the mean of Q_b
+    (dB^2) over the counted samples, steps and replicas, accumulated and read back the same way (the validation pass: the loss alone)."""
     eng = trainer.engine
     wl = trainer.wave_loss
+    dl = trainer.decay_loss
+    wave = trainer._wave                       # the WaveLoss the steps call (an internal one of weight 0 with a decay_loss alone)
 
     def unpack(batch):
         """(spec_in, emb, spec_out, wav_true or None)"""
-        if wl is None:
+        if wave is None:
             spec_in, emb, spec_out = batch
             return spec_in, emb, spec_out, None
         if len(batch) != 4:
-            raise ValueError("a trainer with a wave_loss takes batches (spec_in, emb, spec_out, wav_true) or (..., (room, wav_true))")
+            raise ValueError(f"a trainer with a {'wave_loss' if wl is not None else 'decay_loss'} takes batches (spec_in, emb, spec_out, "
+                             "wav_true) or (..., (room, wav_true))")
         spec_in, emb, spec_out, extra = batch
         return spec_in, emb, spec_out, extra[1] if isinstance(extra, (tuple, list)) else extra
     lr0 = trainer.lr if lr0 is None else lr0
@@ -535,6 +569,7 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         qtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_vq else None
         atot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_acc else None       # correct rows: training, validation
         wtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if wl is not None else None      # sum_b E_b / D_b: training, validation
+        dtot = torch.zeros(4, dtype=torch.float64, device=eng.device) if dl is not None else None      # (sum_b Q_b, samples counted): training, validation
         eng.reg_loss()
         reg0 = eng.reg_out[0].double()           # l2 terms on the weights the first step of the epoch sees
         for batch in train_batches(epoch):
@@ -542,6 +577,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
             trainer.step(spec_in, emb, spec_out, lr=lr, wav_true=wav_true)
             if wl is not None:
                 wtot[0] += wl.wave_out[0]
+            if dl is not None:
+                dtot[0:2] += dl.decay_out
             tot[:3] += eng.loss_out[:3].double()     # total data loss, amplitude term, phase term of this step (raw sums ~1e5: fp64)
             if has_kl:
                 ktot[0] += eng.kl_out[1].double()
@@ -566,6 +603,9 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
             rec["train_vq"] = float(reduce_(qtot[0:1].clone())[0]) * per_vq / n
         if wl is not None and val_batches is None:        # with a validation pass: both sums in one read-back behind it
             rec["train_wave"] = float(reduce_(wtot.clone())[0]) / (n * eng.B * trainer.world_size)
+        if dl is not None and val_batches is None:
+            dv = reduce_(dtot.clone())
+            rec["train_decay"] = float(dv[0]) / max(float(dv[1]), 1.0)
         if has_acc and val_batches is None:        # with a validation pass: both counts in one read-back behind it
             rec["train_acc"] = float(reduce_(atot.clone())[0]) / (n * eng.B * trainer.world_size)
         if val_batches is not None:
@@ -578,10 +618,14 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 eng.begin_step(lr, n_draws=(eng.n_dropout_draws if trainer.dropout else 0) + eng.n_noise_draws, forward_only=True)     # device counters only
                 mask = eng.make_dropout_mask() if trainer.dropout else None
                 eng.forward(spec_in, emb, dropout_mask=mask, target=spec_out, global_batch=eng.B * trainer.world_size, alpha=trainer.alpha)
+                if wave is not None:
+                    wave(eng.pred, wav_true, phase_ref=spec_in if eng.loss_diff else None, global_batch=eng.B * trainer.world_size,
+                         loss_out=eng.loss_out, backward=False, want_wav=dl is not None)
                 if wl is not None:
-                    wl(eng.pred, wav_true, phase_ref=spec_in if eng.loss_diff else None, global_batch=eng.B * trainer.world_size,
-                       loss_out=eng.loss_out, backward=False)
                     wtot[1] += wl.wave_out[0]
+                if dl is not None:
+                    dl(wave.wav_pred, wav_true, global_batch=eng.B * trainer.world_size, loss_out=eng.loss_out, backward=False)
+                    dtot[2:4] += dl.decay_out
                 vt += eng.loss_out[:3].double()
                 if has_kl:
                     ktot[1] += eng.kl_out[1].double()
@@ -604,6 +648,10 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 wv = reduce_(wtot.clone())
                 rec["train_wave"] = float(wv[0]) / (n * eng.B * trainer.world_size)
                 rec["val_wave"] = float(wv[1]) / (m * eng.B * trainer.world_size)
+            if dl is not None:
+                dv = reduce_(dtot.clone())
+                rec["train_decay"] = float(dv[0]) / max(float(dv[1]), 1.0)
+                rec["val_decay"] = float(dv[2]) / max(float(dv[3]), 1.0)
             if has_acc:
                 acc = reduce_(atot.clone())
                 rec["train_acc"] = float(acc[0]) / (n * eng.B * trainer.world_size)
