@@ -696,6 +696,37 @@ int unetrir_decay_loss_f32(const float* wav_pred, const float* wav_true, int B, 
                            double inv_global_batch, float* dwav, double* decay_out, float* loss_out, void* ws, size_t ws_bytes,
                            unetrir_stream_t stream);
 
+/* ---- the multi-resolution STFT loss on the waveform and its gradient on the waveform (spectralloss.hip; the derivation is in its
+ *      header).
+ *
+ * unetrir_spectral_loss_f32: wav_pred (y^), wav_true (y) fp32 [B][T]; res: R triples (n_fft N, win_length, hop_length h) in HOST memory,
+ * 1 <= R <= 8.  The transform of each is the analysis transform of features.hip: periodic Hann of win_length samples centred in N zeros
+ * (left pad (N - win) / 2), centred frames with reflect padding of N / 2 each side, F = 1 + T / h frames, one-sided bins K = N / 2 + 1,
+ * no mean removal, no normalisation.  fp64 arithmetic; per row b and resolution r
+ *   E0_b = sum_t y_b[t]^2 (a row with E0 == 0 counts nothing: zeros in its gradient, nothing in any sum)
+ *   P0 = (sum_n w_r[n]^2) E0_b / T;  delta = 10^(-floor_db / 10);  M_x[f,k] = sqrt(|X[f,k]|^2 + delta P0)
+ *   SC_{b,r} = sum_{f,k} (M_y^ - M_y)^2 / sum_{f,k} M_y^2;   LM_{b,r} = (1 / (F K)) sum_{f,k} (ln M_y^ - ln M_y)^2
+ *   Q_b = (1 / R) sum_r (sc_weight SC_{b,r} + log_weight LM_{b,r});   L = weight inv_global_batch sum_b Q_b
+ *   spectral_out fp64 [3] = (sum_b mean_r SC, sum_b mean_r LM, rows counted);  loss_out nullable: loss_out[0] += (float) L
+ *   dwav nullable fp32 [B][T]: every element written, or with accumulate every element dwav[i] = (float)((double)dwav[i] + g):
+ *   g[f,k] = (weight inv_global_batch / R) [sc_weight 2 (M_y^ - M_y) / sum M_y^2 + log_weight 2 (ln M_y^ - ln M_y) / (F K M_y^)] / M_y^
+ *   p[j] = sum_f w[j - f h] sum_k g[f,k] (Re X^[f,k] cos(2 pi k n / N) - Im X^[f,k] sin(2 pi k n / N)), n = j - f h in [0, N)
+ *   dwav[t] = p[t + N/2] + p at the padded positions that reflect onto t (j < N/2 reads sample N/2 - j; j >= T + N/2 reads
+ *   2 (T - 1) - (j - N/2)), summed over the resolutions in index order.
+ * Four launches with dwav, two without, whatever B and R are; no atomics, every order fixed: two runs give the same bits and a row's
+ * bits depend neither on B nor on its place in the batch; nothing is allocated, cleared or waited for.
+ * unetrir_spectral_loss_supported: 1 for n_fft even, 16 <= n_fft <= 1024, 2 <= win_length <= n_fft, 1 <= hop_length,
+ * n_fft / 2 + 1 <= T <= 16384, else 0.  ws: unetrir_spectral_loss_ws_bytes(B, T, R, res) bytes, 8-byte aligned (0: B <= 0, R outside
+ * 1...8, a null res, an unsupported resolution, or more than 2^31 - 1 workgroups in a launch).
+ * UNETRIR_EINVAL before the device is touched: a null wav_pred / wav_true / spectral_out / ws / res, B <= 0, R outside 1...8, an
+ * unsupported resolution, floor_db not finite or outside (0, 200], a negative or non-finite sc_weight / log_weight / weight, a
+ * non-positive or non-finite inv_global_batch, accumulate without dwav, ws too small or misaligned. */
+int unetrir_spectral_loss_supported(int T, int n_fft, int win_length, int hop_length);
+size_t unetrir_spectral_loss_ws_bytes(int B, int T, int R, const int* res);
+int unetrir_spectral_loss_f32(const float* wav_pred, const float* wav_true, int B, int T, int R, const int* res, double floor_db,
+                              double sc_weight, double log_weight, double weight, double inv_global_batch, int accumulate, float* dwav,
+                              double* spectral_out, float* loss_out, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+
 /* ---- auralization: dry audio rendered through impulse responses, y_b = h_b * x_b (auralize.hip; the formulation is in its header).
  *
  * unetrir_auralize_f32: rir fp32 [B][K] (h); dry fp32 [N] with dry_stride = 0 (one dry signal for all rows) or [B][dry_stride], dry_stride

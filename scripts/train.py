@@ -9,8 +9,9 @@ The defaults are main_training.py's (:27-47): target size (144, 160, 2), LargeMe
 alpha 0.9, no sigmoid / diff loss, 500 epochs, lr 5e-7 with the exponential decay from epoch 80, batch 16, Adam.  A run continues
 from the latest checkpoint in --out when there is one (checkpoints are written every second epoch, :363-364).  The features of
 the whole data set live on the device (unet_rir_amd.Dataset); a batch is one kernel launch.  --wave-loss WEIGHT adds the loss on the
-reconstructed waveform (unet_rir_amd.WaveLoss) and --decay-loss WEIGHT the loss on its energy decay curve (unet_rir_amd.DecayLoss): the
-data set then keeps the waveforms and the generators hand them out.
+reconstructed waveform (unet_rir_amd.WaveLoss), --decay-loss WEIGHT the loss on its energy decay curve (unet_rir_amd.DecayLoss) and
+--spectral-loss WEIGHT its multi-resolution STFT loss (unet_rir_amd.SpectralLoss): the data set then keeps the waveforms and the
+generators hand them out.
 """
 import argparse
 import json
@@ -78,6 +79,13 @@ def main():
                     help="add WEIGHT / batch * sum_b Q_b, the mean squared dB error of the energy decay curve of the reconstructed waveform, "
                          "to the loss (needs --dataset; not for vae / vqvae / diffvae)")
     ap.add_argument("--decay-floor-db", type=float, default=60.0, metavar="DB", help="the decay curves are floored DB below the target's energy")
+    ap.add_argument("--spectral-loss", type=float, default=None, metavar="WEIGHT",
+                    help="add WEIGHT / batch * sum_b Q_b, the multi-resolution STFT loss (squared spectral convergence + squared log-magnitude "
+                         "distance) of the reconstructed waveform, to the loss (needs --dataset; not for vae / vqvae / diffvae)")
+    ap.add_argument("--spectral-resolutions", default="128:64:32,512:256:128,1024:512:256", metavar="N:WIN:HOP,...",
+                    help="the loss's transforms: n_fft:win_length:hop_length, comma-separated (1 to 8)")
+    ap.add_argument("--spectral-floor-db", type=float, default=60.0, metavar="DB",
+                    help="the magnitudes are smoothed DB below the power a bin carries with the target's energy spread evenly")
     ap.add_argument("--epochs", type=int, default=500)
     ap.add_argument("--lr", type=float, default=5e-7)
     ap.add_argument("--no-lr-decay", action="store_true")
@@ -100,7 +108,16 @@ def main():
         raise SystemExit("--decay-loss needs the target waveforms: give --dataset DIR NAME")
     wave = None if a.wave_loss is None else U.WaveLoss(weight=a.wave_loss, norm=a.wave_loss_norm)
     decay = None if a.decay_loss is None else U.DecayLoss(weight=a.decay_loss, floor_db=a.decay_floor_db)
-    wavs = wave is not None or decay is not None
+    if a.spectral_loss is not None and not a.dataset:
+        raise SystemExit("--spectral-loss needs the target waveforms: give --dataset DIR NAME")
+    spectral = None
+    if a.spectral_loss is not None:
+        try:
+            res = tuple(tuple(int(v) for v in r.split(":")) for r in a.spectral_resolutions.split(","))
+            spectral = U.SpectralLoss(weight=a.spectral_loss, resolutions=res, floor_db=a.spectral_floor_db)
+        except ValueError as e:
+            raise SystemExit(f"--spectral-resolutions: {e}")
+    wavs = wave is not None or decay is not None or spectral is not None
     if a.synthetic:
         batches = list(U.synthetic_batches(a.synthetic, a.batch, a.height, a.width, dev))
         model = build_model(a, dev)
@@ -127,7 +144,7 @@ def main():
 
     model = build_model(a, dev)
     trainer = U.Trainer(model, lr=a.lr, alpha=a.alpha, sigmoid_loss=a.sigmoid_loss, diff_loss=a.diff_loss, beta=a.beta,
-                        optimizer=a.optimizer, wave_loss=wave, decay_loss=decay)
+                        optimizer=a.optimizer, wave_loss=wave, decay_loss=decay, spectral_loss=spectral)
     manager = U.CheckpointManager(trainer, a.out, max_to_keep=2)
     start = 0
     if manager.latest_checkpoint is not None:

@@ -197,6 +197,12 @@ _SIGS = {
     "unetrir_decay_loss_supported": (C.c_int, [C.c_int]),
     "unetrir_decay_loss_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, c_f32p, C.c_void_p,
                                          c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    # the multi-resolution STFT loss on the waveform (spectralloss.hip); res is a host array of 3 R ints
+    "unetrir_spectral_loss_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "unetrir_spectral_loss_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "unetrir_spectral_loss_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double,
+                                            C.c_double, C.c_double, C.c_double, C.c_int, c_f32p, C.c_void_p, c_f32p, C.c_void_p,
+                                            C.c_size_t, c_stream]),
     # y = h * x on the fp32 matrix cores (auralize.hip)
     "unetrir_auralize_supported": (C.c_int, [C.c_int]),
     "unetrir_auralize_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, c_stream]),

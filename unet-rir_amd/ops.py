@@ -728,6 +728,58 @@ def decay_loss(wav_pred, wav_true, decay_out, ws: Workspace, floor_db=60.0, weig
                                             _p(decay_out), _p(loss_out), ws.ptr, ws.nbytes, _stream()), "decay_loss")
 
 
+def _res_array(resolutions):
+    """R triples (n_fft, win_length, hop_length) -> (a host int array of 3 R entries, R)"""
+    res = [tuple(int(v) for v in r) for r in resolutions]
+    if not 1 <= len(res) <= 8 or any(len(r) != 3 for r in res):
+        raise ValueError("resolutions: 1 to 8 triples (n_fft, win_length, hop_length)")
+    return (C.c_int * (3 * len(res)))(*[v for r in res for v in r]), len(res)
+
+
+def spectral_loss_supported(T, n_fft, win_length, hop_length):
+    """Whether `spectral_loss` takes waveforms of T samples at this resolution (n_fft even in 16 ... 1024, 2 <= win_length <= n_fft,
+    hop_length >= 1, n_fft / 2 + 1 <= T <= 16384)."""
+    return bool(_lib.lib().unetrir_spectral_loss_supported(int(T), int(n_fft), int(win_length), int(hop_length)))
+
+
+def spectral_loss_ws_bytes(B, T, resolutions):
+    """Bytes `spectral_loss` keeps in its workspace (0: a shape the kernels do not take)."""
+    arr, R = _res_array(resolutions)
+    return int(_lib.lib().unetrir_spectral_loss_ws_bytes(int(B), int(T), R, arr))
+
+
+def spectral_loss(wav_pred, wav_true, spectral_out, ws: Workspace, resolutions, floor_db=60.0, sc_weight=1.0, log_weight=1.0, weight=1.0,
+                  global_batch=None, dwav=None, accumulate=False, loss_out=None):
+    """The multi-resolution STFT loss (squared spectral convergence + squared log-magnitude distance, magnitudes smoothed at -floor_db
+    relative to the target's mean bin power) of wav_pred against wav_true, fp32 [B, T], and (with dwav, fp32 like them) its gradient
+    on wav_pred, written or with accumulate added: spectral_out fp64 [3] = (sum_b mean_r SC, sum_b mean_r LM, rows counted);
+    loss_out[0] += weight / global_batch * (sc_weight spectral_out[0] + log_weight spectral_out[1]).  Four launches with dwav, two
+    without (include/unetrir.h)."""
+    if not isinstance(wav_pred, torch.Tensor) or not wav_pred.is_cuda or wav_pred.dim() != 2:
+        raise ValueError("spectral_loss: wav_pred must be a CUDA tensor [B, T]")
+    B, T = wav_pred.shape
+    _f32c(wav_pred, (B, T), "wav_pred", wav_pred)
+    _f32c(wav_true, (B, T), "wav_true", wav_pred)
+    if dwav is not None:
+        _f32c(dwav, (B, T), "dwav", wav_pred)
+    elif accumulate:
+        raise ValueError("spectral_loss: accumulate adds to a dwav the caller gives")
+    if (spectral_out.dtype != torch.float64 or not spectral_out.is_contiguous() or tuple(spectral_out.shape) != (3,) or
+            spectral_out.device != wav_pred.device):
+        raise ValueError(f"spectral_loss: spectral_out must be a contiguous float64 [3] tensor on {wav_pred.device}")
+    if loss_out is not None and (loss_out.dtype != torch.float32 or loss_out.dim() != 1 or loss_out.numel() < 1 or
+                                 not loss_out.is_contiguous() or loss_out.device != wav_pred.device):
+        raise ValueError(f"spectral_loss: loss_out must be a contiguous float32 vector on {wav_pred.device}")
+    arr, R = _res_array(resolutions)
+    gb = B if global_batch is None else global_batch
+    need = int(_lib.lib().unetrir_spectral_loss_ws_bytes(B, T, R, arr))
+    if need:
+        ws.reserve(need)
+    check(_lib.lib().unetrir_spectral_loss_f32(_p(wav_pred), _p(wav_true), B, T, R, arr, float(floor_db), float(sc_weight),
+                                               float(log_weight), float(weight), 1.0 / gb, int(bool(accumulate)), _p(dwav),
+                                               _p(spectral_out), _p(loss_out), ws.ptr, ws.nbytes, _stream()), "spectral_loss")
+
+
 def auralize_supported(K):
     """Whether `auralize_f32` takes impulse responses of K taps (1 <= K <= 16384)."""
     return bool(_lib.lib().unetrir_auralize_supported(int(K)))

@@ -133,7 +133,8 @@ class Trainer:
     """
 
     def __init__(self, model, lr=None, alpha=0.9, world_size=1, group=None, bucket_bytes=32 << 20, dropout=True, force_dp=False,
-                 sigmoid_loss=False, diff_loss=False, beta=0.5, graph=False, dropout_seed=None, optimizer="adam", wave_loss=None, decay_loss=None):
+                 sigmoid_loss=False, diff_loss=False, beta=0.5, graph=False, dropout_seed=None, optimizer="adam", wave_loss=None, decay_loss=None,
+                 spectral_loss=None):
         """force_dp: run the bucketed all-reduce path even at world_size 1 (needs an initialised process group; rehearsal).
         sigmoid_loss / diff_loss / beta: the switches of compute_loss (main_training.py:38-40, :214-222; both False in the
         reference's live configuration): column weights sigmoid(beta, ...) of preprocess.py:116-121 on the phase term, and the
@@ -154,7 +155,11 @@ class Trainer:
         curve of that waveform (csrc/decayloss.hip): behind the wave-loss call, which also hands over the waveform, the term's
         dL/dpred is added to that call's dpred (csrc/istft_bwd.hip) and loss_out[0] grows by the term.  Without a `wave_loss` the
         trainer keeps one of weight 0 - an exact zero whose launch yields the waveform and the spectrogram loss's dL/dpred.  The same
-        engines are refused."""
+        engines are refused.
+        spectral_loss: a `unet_rir_amd.SpectralLoss` - every step then also minimises weight / global batch * sum_b Q_b, the
+        multi-resolution STFT loss of that waveform (csrc/spectralloss.hip), in the same place and under the same rules as the
+        decay_loss.  With both, the decay term writes its cotangent on the waveform, the spectral term adds to it, and ONE
+        vector-Jacobian product carries the sum onto dpred."""
         self.module = None
         engine = model
         if not hasattr(model, "specs") and hasattr(model, "engine"):
@@ -171,21 +176,25 @@ class Trainer:
                                  "drives the spectrogram models only")
         self.wave_loss = wave_loss
         self.decay_loss = decay_loss
-        self._wave = wave_loss              # the WaveLoss the step calls: the user's, or with a decay_loss alone one of weight 0
-        if decay_loss is not None:
+        self.spectral_loss = spectral_loss
+        self._wave = wave_loss              # the WaveLoss the step calls: the user's, or for a decay_loss / spectral_loss without one, one of weight 0
+        for name, term, what in (("decay_loss", decay_loss, "decay"), ("spectral_loss", spectral_loss, "spectral")):
+            if term is None:
+                continue
             own = [n for n in ("kl_out", "vq_out", "acc_out") if hasattr(engine, n)]
             if own:
-                raise ValueError(f"decay_loss: {type(engine).__name__} has a loss term or target of its own ({own[0]}); the decay loss "
+                raise ValueError(f"{name}: {type(engine).__name__} has a loss term or target of its own ({own[0]}); the {what} loss "
                                  "drives the spectrogram models only")
             geo = lambda o: (o.des_shape, o.n_fft, o.win_length, o.hop_length)
-            if wave_loss is None:
+            if self._wave is None:
                 from .waveloss import WaveLoss
-                self._wave = WaveLoss(weight=0.0, des_shape=decay_loss.des_shape, n_fft=decay_loss.n_fft, win_length=decay_loss.win_length,
-                                      hop_length=decay_loss.hop_length)
+                self._wave = WaveLoss(weight=0.0, des_shape=term.des_shape, n_fft=term.n_fft, win_length=term.win_length,
+                                      hop_length=term.hop_length)
                 self._wave.prepare(engine.device, engine.B)
-            elif geo(wave_loss) != geo(decay_loss):
-                raise ValueError(f"decay_loss: its geometry {geo(decay_loss)} differs from the wave_loss's {geo(wave_loss)}")
-            decay_loss.prepare(engine.device, engine.B)
+            elif geo(self._wave) != geo(term):
+                raise ValueError(f"{name}: its geometry {geo(term)} differs from the "
+                                 f"{'wave_loss' if wave_loss is not None else 'decay_loss'}'s {geo(self._wave)}")
+            term.prepare(engine.device, engine.B)
         if lr is None:
             lr = optimizer.learning_rate if isinstance(optimizer, LAMB) else 5e-7
         self.lr, self.alpha = lr, alpha
@@ -304,11 +313,19 @@ class Trainer:
             phase_ref = spec_in if eng.loss_diff else None
             dpred = self._wave(eng.pred, wav_true, phase_ref=phase_ref, spec_target=spec_out, alpha=self.alpha,
                                inv_norm=1.0 / (2.0 * eng.H * eng.W * gb), phase_weight=eng.loss_phase_weight, global_batch=gb,
-                               loss_out=eng.loss_out, want_wav=self.decay_loss is not None)
-            if self.decay_loss is not None:
+                               loss_out=eng.loss_out, want_wav=self.decay_loss is not None or self.spectral_loss is not None)
+            if self.decay_loss is not None and self.spectral_loss is None:
                 # the call above also handed over the waveform; the decay term's dL/dpred goes on top of its dpred
                 self.decay_loss(self._wave.wav_pred, wav_true, pred=eng.pred, phase_ref=phase_ref, dpred=dpred, accumulate=True,
                                 global_batch=gb, loss_out=eng.loss_out)
+            elif self.spectral_loss is not None:
+                # with a decay term as well: that one writes its cotangent on the waveform, the spectral term adds to it, and one
+                # vector-Jacobian product carries the sum onto dpred
+                dwav = None
+                if self.decay_loss is not None:
+                    dwav = self.decay_loss(self._wave.wav_pred, wav_true, global_batch=gb, loss_out=eng.loss_out)
+                self.spectral_loss(self._wave.wav_pred, wav_true, pred=eng.pred, phase_ref=phase_ref, dpred=dpred, accumulate=True,
+                                   dwav=dwav, global_batch=gb, loss_out=eng.loss_out)
         self._backward_and_reduce(dpred)
         self.apply_gradients()
 
@@ -320,6 +337,8 @@ class Trainer:
             raise ValueError("this trainer has a wave_loss: step(..., wav_true=) needs the target waveforms")
         if self.decay_loss is not None and wav_true is None:
             raise ValueError("this trainer has a decay_loss: step(..., wav_true=) needs the target waveforms")
+        if self.spectral_loss is not None and wav_true is None:
+            raise ValueError("this trainer has a spectral_loss: step(..., wav_true=) needs the target waveforms")
         if self._wave is None:
             wav_true = None
         eng.training = True
@@ -533,11 +552,15 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
     `train_loss` / `val_loss` carry the term.
 
     With `trainer.decay_loss` the batches are those four-tuples too, and the record gains `train_decay` / `val_decay`: the mean of Q_b
-    (dB^2) over the counted samples, steps and replicas, accumulated and read back the same way (the validation pass: the loss alone)."""
+    (dB^2) over the counted samples, steps and replicas, accumulated and read back the same way (the validation pass: the loss alone).
+
+    With `trainer.spectral_loss` likewise `train_sc` / `val_sc` and `train_logmag` / `val_logmag`: the means of mean_r SC and mean_r LM
+    over the counted samples, steps and replicas."""
     eng = trainer.engine
     wl = trainer.wave_loss
     dl = trainer.decay_loss
-    wave = trainer._wave                       # the WaveLoss the steps call (an internal one of weight 0 with a decay_loss alone)
+    sl = trainer.spectral_loss
+    wave = trainer._wave                       # the WaveLoss the steps call (an internal one of weight 0 when the user gave none)
 
     def unpack(batch):
         """(spec_in, emb, spec_out, wav_true or None)"""
@@ -545,8 +568,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
             spec_in, emb, spec_out = batch
             return spec_in, emb, spec_out, None
         if len(batch) != 4:
-            raise ValueError(f"a trainer with a {'wave_loss' if wl is not None else 'decay_loss'} takes batches (spec_in, emb, spec_out, "
-                             "wav_true) or (..., (room, wav_true))")
+            which = "wave_loss" if wl is not None else ("decay_loss" if dl is not None else "spectral_loss")
+            raise ValueError(f"a trainer with a {which} takes batches (spec_in, emb, spec_out, wav_true) or (..., (room, wav_true))")
         spec_in, emb, spec_out, extra = batch
         return spec_in, emb, spec_out, extra[1] if isinstance(extra, (tuple, list)) else extra
     lr0 = trainer.lr if lr0 is None else lr0
@@ -570,6 +593,7 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         atot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_acc else None       # correct rows: training, validation
         wtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if wl is not None else None      # sum_b E_b / D_b: training, validation
         dtot = torch.zeros(4, dtype=torch.float64, device=eng.device) if dl is not None else None      # (sum_b Q_b, samples counted): training, validation
+        stot = torch.zeros(6, dtype=torch.float64, device=eng.device) if sl is not None else None      # (sum SC, sum LM, samples counted): training, validation
         eng.reg_loss()
         reg0 = eng.reg_out[0].double()           # l2 terms on the weights the first step of the epoch sees
         for batch in train_batches(epoch):
@@ -579,6 +603,8 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 wtot[0] += wl.wave_out[0]
             if dl is not None:
                 dtot[0:2] += dl.decay_out
+            if sl is not None:
+                stot[0:3] += sl.spectral_out
             tot[:3] += eng.loss_out[:3].double()     # total data loss, amplitude term, phase term of this step (raw sums ~1e5: fp64)
             if has_kl:
                 ktot[0] += eng.kl_out[1].double()
@@ -606,6 +632,9 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         if dl is not None and val_batches is None:
             dv = reduce_(dtot.clone())
             rec["train_decay"] = float(dv[0]) / max(float(dv[1]), 1.0)
+        if sl is not None and val_batches is None:
+            sv = reduce_(stot.clone())
+            rec["train_sc"], rec["train_logmag"] = float(sv[0]) / max(float(sv[2]), 1.0), float(sv[1]) / max(float(sv[2]), 1.0)
         if has_acc and val_batches is None:        # with a validation pass: both counts in one read-back behind it
             rec["train_acc"] = float(reduce_(atot.clone())[0]) / (n * eng.B * trainer.world_size)
         if val_batches is not None:
@@ -620,12 +649,15 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 eng.forward(spec_in, emb, dropout_mask=mask, target=spec_out, global_batch=eng.B * trainer.world_size, alpha=trainer.alpha)
                 if wave is not None:
                     wave(eng.pred, wav_true, phase_ref=spec_in if eng.loss_diff else None, global_batch=eng.B * trainer.world_size,
-                         loss_out=eng.loss_out, backward=False, want_wav=dl is not None)
+                         loss_out=eng.loss_out, backward=False, want_wav=dl is not None or sl is not None)
                 if wl is not None:
                     wtot[1] += wl.wave_out[0]
                 if dl is not None:
                     dl(wave.wav_pred, wav_true, global_batch=eng.B * trainer.world_size, loss_out=eng.loss_out, backward=False)
                     dtot[2:4] += dl.decay_out
+                if sl is not None:
+                    sl(wave.wav_pred, wav_true, global_batch=eng.B * trainer.world_size, loss_out=eng.loss_out, backward=False)
+                    stot[3:6] += sl.spectral_out
                 vt += eng.loss_out[:3].double()
                 if has_kl:
                     ktot[1] += eng.kl_out[1].double()
@@ -652,6 +684,10 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 dv = reduce_(dtot.clone())
                 rec["train_decay"] = float(dv[0]) / max(float(dv[1]), 1.0)
                 rec["val_decay"] = float(dv[2]) / max(float(dv[3]), 1.0)
+            if sl is not None:
+                sv = reduce_(stot.clone())
+                rec["train_sc"], rec["train_logmag"] = float(sv[0]) / max(float(sv[2]), 1.0), float(sv[1]) / max(float(sv[2]), 1.0)
+                rec["val_sc"], rec["val_logmag"] = float(sv[3]) / max(float(sv[5]), 1.0), float(sv[4]) / max(float(sv[5]), 1.0)
             if has_acc:
                 acc = reduce_(atot.clone())
                 rec["train_acc"] = float(acc[0]) / (n * eng.B * trainer.world_size)
