@@ -745,6 +745,37 @@ int unetrir_auralize_supported(int K);
 int unetrir_auralize_f32(const float* rir, const float* dry, float* out, int B, int K, int N, long long dry_stride, int L,
                          unetrir_stream_t stream);
 
+/* ---- the FFT form of auralization: the same y_b = h_b * x_b by uniform partitioned overlap-save, every transform in LDS
+ *      (auralize_fft.hip, fft_lds.h; formulation and the derivation of the bound are in the former's header).
+ *
+ * unetrir_auralize_fft_f32: arguments and their rules as unetrir_auralize_f32, plus a workspace.  With the block P =
+ * unetrir_auralize_fft_block(K) (2048 for every supported K, 0 otherwise), real transforms of 2P samples, Q = ceil(K / P) partitions
+ * of h and J = ceil(L / P) output blocks anchored at n = 0:
+ *   H_q = rfft(h_b[qP ... (q+1)P) | P zeros),   X_i = rfft(x_b[(i-1)P ... (i+1)P)) with zeros outside 0 <= m < N,
+ *   Y_j = sum_{q <= min(j, Q-1)} H_q X_{j-q}, summed in ascending q in fp32 complex starting from +0,
+ *   out[b][jP ... (j+1)P) = the last P samples of irfft(Y_j).
+ * Two launches whatever B, N, L (the spectra of h and x; products, inverse and store), no atomics, no host synchronisation,
+ * capturable; every element of out written exactly once and nothing beyond it.  With dry_stride = 0 the spectra of x are computed
+ * once for all rows.  Twiddles are a table of fp32 values correctly rounded from an fp64 evaluation.
+ * The bits of an element depend on (h_b, x_b, n) and the fixed block grid alone: not on the run, B, the row's place in the batch,
+ * shared or per-row x, L (a truncated call returns the head of the full result, bit for bit) or N beyond the samples themselves
+ * (x followed by explicit zeros gives the same bits).  They are NOT the direct form's, and the result is NOT exact on integer data.
+ * A non-finite input sample spoils every output block its 2P-window or its partition feeds, not K outputs.
+ * Error, per element n of block j, u = 2^-24, Q_j = min(j, Q-1) + 1:
+ *   |out[b][n] - y_b[n]| <= u (19 log2(2P) + 8 + Q_j) sum_{q < Q_j} |h_b[qP ... (q+1)P)|_1 |x_b[(j-q-1)P ... (j-q+1)P)|_2
+ * to first order in u (19 = 4.83 + 2 x 6.66 per radix-2 level rounded up: the componentwise error of H^ and the L2 errors of X^ and of
+ * the inverse; 8: the rounding of the product, the split passes and the second-order terms); loose by orders of magnitude on random data.
+ * unetrir_auralize_fft_supported(K): 1 for 1 <= K <= 16384, as the direct form.  ws: unetrir_auralize_fft_ws_bytes(B, K, N, dry_stride,
+ * L) bytes = 16384 (B Q + (dry_stride ? B : 1) J), 16-byte aligned; 0 for arguments the call refuses.
+ * UNETRIR_EINVAL before the device is touched: a null pointer (ws included), B, K or N < 1, K unsupported, L outside 1 ... N + K - 1, a
+ * dry_stride other than 0 or >= N, ws too small or misaligned, more workgroups than a launch takes (B Q + (dry_stride ? B : 1) J or
+ * B J above 2^31 - 8). */
+int unetrir_auralize_fft_supported(int K);
+int unetrir_auralize_fft_block(int K);
+size_t unetrir_auralize_fft_ws_bytes(int B, int K, int N, long long dry_stride, int L);
+int unetrir_auralize_fft_f32(const float* rir, const float* dry, float* out, int B, int K, int N, long long dry_stride, int L, void* ws,
+                             size_t ws_bytes, unetrir_stream_t stream);
+
 /* ---- scoring of generated impulse responses: the loss block of the evaluation loop (rir_generation.py:185-225) and its per-room
  *      bookkeeping (:227-290, :311-357), on the device and without a read-back.
  *

@@ -12,6 +12,8 @@
                (--diff-gen: the predicted phase is a difference to the input's)
 --dry          the dry recording: a .wav file at --sr, read whole by the same rules (channels averaged, mean removed)
 --length       full (default: N + K - 1 samples), same (N) or a number of samples
+--method       direct (default: one fma per tap on the matrix cores, exact on integer data) or fft (partitioned overlap-save: the fast
+               one for long recordings, within a rounding bound instead of exact)
 --out          OUT_DIR/NAME.wav per position, 32-bit float at --sr: NAME is the response's file name, or b{batch}_{row} for generated ones
 --peak         scale every output file so that the loudest sample of the whole set is this (default: values as computed)
 """
@@ -99,6 +101,7 @@ def main():
     ap.add_argument("--sr", type=int, default=48000)
     ap.add_argument("--duration", type=float, default=0.2, help="seconds of every --rirs file that are used")
     ap.add_argument("--length", default="full")
+    ap.add_argument("--method", choices=("direct", "fft"), default="direct")
     ap.add_argument("--peak", type=float, default=None)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
@@ -116,7 +119,7 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     rendered = []
     for names, wav in (rir_batches(a, dev) if a.rirs else model_batches(a, dev)):
-        wet = U.auralize(wav, dry, length=length).cpu().numpy()
+        wet = U.auralize(wav, dry, length=length, method=a.method).cpu().numpy()
         rendered += list(zip(names, wet))
     gain = 1.0
     if a.peak is not None:

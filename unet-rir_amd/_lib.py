@@ -206,6 +206,12 @@ _SIGS = {
     # y = h * x on the fp32 matrix cores (auralize.hip)
     "unetrir_auralize_supported": (C.c_int, [C.c_int]),
     "unetrir_auralize_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, c_stream]),
+    # the same by partitioned overlap-save, FFTs in LDS (auralize_fft.hip)
+    "unetrir_auralize_fft_supported": (C.c_int, [C.c_int]),
+    "unetrir_auralize_fft_block": (C.c_int, [C.c_int]),
+    "unetrir_auralize_fft_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
+    "unetrir_auralize_fft_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
+                                           C.c_size_t, c_stream]),
     "unetrir_eval_metrics_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int,
                                            C.c_void_p, c_stream]),
     "unetrir_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),

@@ -9,6 +9,14 @@ at once.  `auralize` is that last link behind `PostProcess` / `GriffinLim`:
     y_b[n] = sum_k h_b[k] x_b[n - k]       direct form on the fp32 matrix cores, one launch, fp32 fma chain in ascending k:
                                            exact on integer data, the same bits on every run (include/unetrir.h)
 
+    wet = auralize(wav, dry, method="fft")                               # the same, by partitioned overlap-save (csrc/auralize_fft.hip):
+                                           block 2048, FFTs in LDS, two launches and a workspace; within a derived rounding bound
+                                           (include/unetrir.h) instead of exact, its own reproducible bits
+
+Which one (profiles/auralize_fft.json, B = 32, x shared): at K = 9600 "fft" is 15 x faster for 2 s of audio and 27 x for 10 s (0.048 and
+0.103 ms against 0.715 and 2.77), and 2.7 - 4 x faster than torch.fft.rfft . irfft; "direct" wins below K of a hundred or two (K = 32:
+0.031 against 0.037 ms; K = 256: 0.048 against 0.036) and wherever the result must be exact or must not change with the method.
+
 `write_wav` is the counterpart of `PostProcess.save_wav` (postprocess.py:135-149) for the rendered signals.
 """
 import struct
@@ -19,12 +27,17 @@ import torch
 from . import ops
 
 
-def auralize(rir, dry, length="full", out=None):
+def auralize(rir, dry, length="full", out=None, method="direct"):
     """rir fp32 [B, K] or [K], dry fp32 [N] (one source heard through every response: the microphone-array case) or [B, N] (one source
     per row) -> fp32 [B, L]: the first L samples of the convolution.  length: "full" (N + K - 1), "same" (N) or an int in 1 ... N + K - 1;
     a shorter L returns the head of the full result, bit for bit.  out: a contiguous fp32 [B, L] tensor to write instead of a new one.
-    CUDA tensors, contiguous fp32, on one device (checked before the launch: ValueError); the launch goes to the current stream and
+    method: "direct" (the default: exact on integer data, one rounding per tap) or "fft" (partitioned overlap-save, block 2048, two
+    launches and a workspace of 16 KB per spectrum that lives for the call: within the bound of include/unetrir.h, not exact, other
+    bits than "direct" but as reproducible).
+    CUDA tensors, contiguous fp32, on one device (checked before the launch: ValueError); the launches go to the current stream and
     nothing synchronises with the host."""
+    if method not in ("direct", "fft"):
+        raise ValueError(f'auralize: method must be "direct" or "fft", not {method!r}')
     if not isinstance(rir, torch.Tensor) or not isinstance(dry, torch.Tensor):
         raise ValueError("auralize: rir and dry must be tensors")
     if rir.dim() == 1:
@@ -49,7 +62,10 @@ def auralize(rir, dry, length="full", out=None):
         out = torch.empty((B, L), dtype=torch.float32, device=rir.device)
     elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, L):
         raise ValueError(f"auralize: out must be a tensor of shape {(B, L)}")
-    ops.auralize_f32(rir, dry, out)
+    if method == "fft":
+        ops.auralize_fft_f32(rir, dry, out)
+    else:
+        ops.auralize_f32(rir, dry, out)
     return out
 
 

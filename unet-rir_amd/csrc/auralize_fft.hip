@@ -1,0 +1,257 @@
+// auralize_fft.hip - the FFT form of auralize: y_b = h_b * x_b by uniform partitioned overlap-save, transforms in LDS (fft_lds.h), gfx950.
+//
+//     y_b[n] = sum_{k=0}^{K-1} h_b[k] x_b[n - k]          0 <= n < L <= N + K - 1,   x_b[m] = 0 outside 0 <= m < N
+//
+// Formulation.  Block P = 2048 for every K, real transforms of 2P = 4096 samples (a 2048-point complex FFT + split: 16 KB of LDS).
+// Q = ceil(K / P) partitions of h, J = ceil(L / P) output blocks anchored at n = 0:
+//     H_q = rfft(h[qP ... (q+1)P) | 0_P)                              q in [0, Q)      (zeros beyond K)
+//     X_i = rfft(x[(i-1)P ... (i+1)P))                                i in [0, J)      (zeros outside 0 <= m < N)
+//     Y_j = sum_{q = 0}^{min(j, Q-1)} H_q X_{j-q}                     ascending q, fp32 complex, the first product added to +0
+//     out[jP ... (j+1)P) = the LAST P samples of irfft(Y_j)           (the first P are the circular wrap-around)
+// A spectrum is packed as fft_lds.h packs it: 2048 float2, bin 0 and bin 2048 (both real) in slot 0, multiplied separately.
+//
+// Launches: two.  (1) one workgroup per spectrum, B Q of h then J (x shared, dry_stride = 0: computed once for all rows) or B J of x,
+// into the workspace [H: B][Q][2048] [X: 1 or B][J][2048] float2;  (2) one workgroup per row and pair of output blocks (2g, 2g + 1): the
+// products of both accumulate in registers (8 bins per thread and block, spectra read 16 bytes per lane; a step q reads H_q and one new
+// X, which serves block 2g now and block 2g + 1 at step q + 1: 2Q + 1 spectra for two blocks instead of 4Q), then per block inverse
+// split, inverse FFT and one store per output sample, scaled by the exact 2^-12.  The pairing decides what is read when, not what is
+// computed: each Y_j is the same sequence of operations whatever its place in a pair, and the complex products and the sums around them
+// are written as explicit fused multiply-adds / unfused sums (contraction off), so the bits do not depend on how the loop was compiled.
+// No atomics, no host synchronisation, nothing cleared; every element of out written once and nothing beyond it.
+//
+// Bits.  The block grid is anchored at n = 0 and P is a constant, so the bits of out[b][n] depend on (h_b, x_b, n) alone: not on B,
+// the row's place, L (J only decides which blocks exist), shared or per-row x, or N beyond the samples themselves (an x window past N
+// is the same zeros as explicit zeros, and every q <= min(j, Q-1) is summed whether or not its window is empty).
+//
+// Error.  Per element n of block j, with u = 2^-24, Q_j = min(j, Q-1) + 1 and s_j = sum_{q < Q_j} |h_q|_1 |x[(j-q-1)P ... (j-q+1)P)|_2:
+//     |out[n] - y[n]| <= u (19 log2(2P) + 8 + Q_j) s_j                                                     (first order in u)
+// derived (not fitted) as follows.  A transform of 2P real points is log2(P) radix-2 levels (a radix-8 pass is three of them: at most
+// one complex product by a correctly rounded twiddle, |w^ - w| <= u, and one sum per element and level) plus the split, one more such
+// level with a second sum: log2(2P) levels.  (a) Componentwise, every input reaches every output along one path, per level a factor
+// (1 + u)(1 + sqrt(2) 2u)(1 + u) (twiddle, product [Higham, Accuracy and Stability, (3.13)], sum): |H^_q[k] - H_q[k]| <= 4.83 u
+// log2(2P) |h_q|_1, hence |(H^_q - H_q) X|_2 <= 4.83 u log2(2P) |h_q|_1 |X|_2.  (b) In L2 a level costs eta = u + 4 sqrt(2) u = 6.66 u
+// [Higham, Theorem 24.2]: |X^ - X|_2 <= 6.66 u log2(2P) |X|_2 and |H_q (X^ - X)|_2 <= |h_q|_1 6.66 u log2(2P) |X|_2, as |H_q[k]| <=
+// |h_q|_1.  (c) The product rounds by sqrt(2) 2u = 2.83 u and the ascending sum of Q_j terms by (Q_j - 1) u of sum_q |H_q X_{j-q}|_2.
+// (d) The inverse adds 6.66 u log2(2P) of |Y_j|_2 <= sum_q |h_q|_1 |X_{j-q}|_2 and carries the errors before it over unchanged
+// (Parseval: |X|_2 = sqrt(2P) |x|_2 cancels the 1 / sqrt(2P) of the inverse); the scaling by 2^-12 is exact.  Sum: (4.83 + 2 x 6.66)
+// log2(2P) + 2.83 + Q_j - 1 = 18.15 log2(2P) + 1.83 + Q_j, and the error of an element is at most the L2 norm of its block's: rounded
+// up to c1 = 19, c2 = 8 (the slack covers the split's second sum in each of the three transforms and the second-order terms).  The
+// bound is loose by two to five orders of magnitude on random data (errors add like a random walk, not in phase): the tests also hold
+// integer data to round(out) == y.
+//
+// Not exact on integer data (the direct form is); a non-finite sample spoils the whole blocks its window feeds, not K outputs.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kernels.h"
+#include "fft_lds.h"
+
+namespace {
+
+using namespace fftlds;
+
+constexpr int AF_P = 2048;                              // block; the real transform has 2 AF_P points
+constexpr int AF_M = AF_P;                              // complex points of that transform
+constexpr int AF_THREADS = AF_M / 8;
+constexpr int AF_MAXK = 16384;
+constexpr size_t AF_SPEC = AF_M * sizeof(cf);           // bytes of a packed spectrum
+constexpr int AF_G = 2;                                 // consecutive output blocks per workgroup of the second launch
+
+// The image of the real window a[m] = src[lo + m], m in [0, 2P), as z[i] = a[2i] + i a[2i+1]; zero for m >= mlim and outside [0, n)
+FL_HD void af_load(cf* buf, const float* __restrict__ src, long long lo, long long n, int mlim, int t) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int i = t + AF_THREADS * e, m = 2 * i;
+        const long long s = lo + m;
+        cf z;
+        z.x = (m < mlim && s >= 0 && s < n) ? src[s] : 0.f;
+        z.y = (m + 1 < mlim && s + 1 >= 0 && s + 1 < n) ? src[s + 1] : 0.f;
+        buf[fl_swz(i)] = z;
+    }
+}
+
+// bins 2 i and 2 i + 1 of the image, i = t + 256 e: 16 bytes per lane
+FL_HD void af_store_spec(float4* __restrict__ spec, const cf* buf, int t) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int i = t + AF_THREADS * e;
+        const cf a = buf[fl_swz(2 * i)], b = buf[fl_swz(2 * i + 1)];
+        spec[i] = make_float4(a.x, a.y, b.x, b.y);
+    }
+}
+
+// a thread's 8 bins of one spectrum: bins 2 i and 2 i + 1, i = t + 256 e, 16 bytes per lane and load
+struct AfBins {
+    float4 v[4];
+};
+FL_HD void af_read(AfBins& d, const float4* __restrict__ S, int t) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d.v[e] = S[t + AF_THREADS * e];
+}
+
+// acc += h x on the thread's 8 bins; slot 0 holds the two real bins 0 and P
+FL_HD void af_mac(cf (&acc)[8], const AfBins& h, const AfBins& x, int t) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        cf p0 = fl_mul(cf{h.v[e].x, h.v[e].y}, cf{x.v[e].x, x.v[e].y});
+        const cf p1 = fl_mul(cf{h.v[e].z, h.v[e].w}, cf{x.v[e].z, x.v[e].w});
+        if (e == 0 && t == 0) p0 = {h.v[0].x * x.v[0].x, h.v[0].y * x.v[0].y};
+        acc[2 * e] = {acc[2 * e].x + p0.x, acc[2 * e].y + p0.y};
+        acc[2 * e + 1] = {acc[2 * e + 1].x + p1.x, acc[2 * e + 1].y + p1.y};
+    }
+}
+
+// Y_{j0 + g} = sum_q H_q X_{j0 + g - q} for g = 0 ... gmax (< G) at once, each in ascending q from +0: step q reads H_q and ONE new
+// spectrum of x, X_{j0 - q}; the other G - 1 it needs are still in registers from the steps before (X_i sits in slot (i - j0) mod G, so
+// the q loop is unrolled by G to keep the slots static).  H (this row's spectra) and X are indexed by spectrum, AF_M / 2 float4 each.
+template <int G>
+FL_HD void af_accumulate(cf (&acc)[G][8], const float4* __restrict__ H, const float4* __restrict__ X, int j0, int gmax, int Q, int t) {
+    AfBins x[G], h;
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[g][e] = {0.f, 0.f};
+#pragma unroll
+    for (int g = 1; g < G; ++g)
+        if (g <= gmax) af_read(x[g], X + (size_t)(j0 + g) * (AF_M / 2), t);
+    const int qn = (j0 + gmax < Q - 1 ? j0 + gmax : Q - 1) + 1;
+    for (int qq = 0; qq < qn; qq += G) {
+#pragma unroll
+        for (int s = 0; s < G; ++s) {
+            const int q = qq + s;
+            if (q < qn) {
+                af_read(h, H + (size_t)q * (AF_M / 2), t);
+                if (q <= j0) af_read(x[(G - s) % G], X + (size_t)(j0 - q) * (AF_M / 2), t);
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    if (g <= gmax && q <= j0 + g) af_mac(acc[g], h, x[(g - s + G) % G], t);
+            }
+        }
+    }
+}
+
+FL_HD void af_store_acc(cf* buf, const cf (&acc)[8], int t) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int i = t + AF_THREADS * e;
+        buf[fl_swz(2 * i)] = acc[2 * e];
+        buf[fl_swz(2 * i + 1)] = acc[2 * e + 1];
+    }
+}
+
+// The last P samples of the inverse: z[P/2 + i] holds samples P + 2 i and P + 2 i + 1 of the block that starts at n0, times 2 M
+FL_HD void af_store_out(float* __restrict__ y, const cf* buf, long long n0, long long L, int t) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int i = t + AF_THREADS * e;
+        const cf z = buf[fl_swz(AF_M / 2 + i)];
+        const long long n = n0 + 2 * i;
+        const float a = z.x * (1.f / (2 * AF_M)), b = z.y * (1.f / (2 * AF_M));
+        if (n + 1 < L && ((uintptr_t)(y + n) & 7) == 0) {
+            *reinterpret_cast<float2*>(y + n) = make_float2(a, b);
+        } else {
+            if (n < L) y[n] = a;
+            if (n + 1 < L) y[n + 1] = b;
+        }
+    }
+}
+
+// The logical block of this workgroup among n, in a grid padded to a multiple of 8 (a value >= n: nothing to do).  Workgroups are dealt
+// round-robin over the 8 XCDs (observed, not promised, and only speed rests on it), so XCD x works the contiguous run of blocks
+// [x ceil(n / 8), (x + 1) ceil(n / 8)): consecutive blocks of one row, which read the same spectra, meet in one L2.
+__device__ __forceinline__ int af_block(int n) {
+    return (int)(blockIdx.x & 7) * ((n + 7) >> 3) + (int)(blockIdx.x >> 3);
+}
+__host__ unsigned af_grid(long long n) { return (unsigned)((n + 7) / 8 * 8); }
+
+__global__ __launch_bounds__(AF_THREADS) void auralize_fft_spectra_kernel(const float* __restrict__ rir, const float* __restrict__ dry,
+                                                                          float4* __restrict__ spec, int K, int N, long long dry_stride,
+                                                                          int Q, int J, int nH, int nX) {
+    __shared__ cf buf[AF_M];
+    const int t = threadIdx.x;
+    const int blk = af_block(nH + nX);
+    if (blk >= nH + nX) return;
+    int id = blk;
+    if (id < nH) {
+        const int b = id / Q, q = id - b * Q;
+        af_load(buf, rir + (size_t)b * K, (long long)q * AF_P, K, AF_P, t);
+    } else {
+        id -= nH;
+        const int r = id / J, i = id - r * J;
+        af_load(buf, dry + (long long)r * dry_stride, (long long)(i - 1) * AF_P, N, 2 * AF_P, t);
+    }
+    __syncthreads();
+    fl_fft<AF_M, -1>(buf, t);
+    fl_split_fwd<AF_M>(buf, t, AF_THREADS);
+    __syncthreads();
+    af_store_spec(spec + (size_t)blk * (AF_M / 2), buf, t);
+}
+
+template <int G>
+__global__ __launch_bounds__(AF_THREADS) void auralize_fft_render_kernel(const float4* __restrict__ spec, float* __restrict__ out, int Q,
+                                                                         int J, int JG, int L, int nH, int xrows, int B) {
+    __shared__ cf buf[AF_M];
+    const int t = threadIdx.x;
+    const int blk = af_block(B * JG);
+    if (blk >= B * JG) return;
+    const int b = blk / JG, j0 = (blk - b * JG) * G;
+    const int gmax = J - 1 - j0 < G - 1 ? J - 1 - j0 : G - 1;
+    const float4* __restrict__ H = spec + (size_t)b * Q * (AF_M / 2);
+    const float4* __restrict__ X = spec + ((size_t)nH + (xrows > 1 ? (size_t)b * J : 0)) * (AF_M / 2);
+    cf acc[G][8];
+    af_accumulate<G>(acc, H, X, j0, gmax, Q, t);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (g > gmax) break;
+        if (g) __syncthreads();                         // the stores of block g - 1 have read the image
+        af_store_acc(buf, acc[g], t);
+        __syncthreads();
+        fl_split_inv<AF_M>(buf, t, AF_THREADS);
+        __syncthreads();
+        fl_fft<AF_M, 1>(buf, t);
+        af_store_out(out + (size_t)b * L, buf, (long long)(j0 + g) * AF_P, L, t);
+    }
+}
+
+// Q, J, the spectra of h and of x; false for arguments the kernels do not take
+bool af_plan(int B, int K, int N, long long dry_stride, int L, long long& Q, long long& J, long long& nH, long long& nX) {
+    if (B < 1 || K < 1 || K > AF_MAXK || N < 1) return false;
+    if (L < 1 || (long long)L > (long long)N + K - 1) return false;
+    if (dry_stride != 0 && dry_stride < N) return false;
+    Q = (K + AF_P - 1) / AF_P;
+    J = ((long long)L + AF_P - 1) / AF_P;
+    nH = (long long)B * Q;
+    nX = (dry_stride == 0 ? 1 : (long long)B) * J;
+    return nH + nX <= 0x7ffffff8LL && (long long)B * J <= 0x7ffffff8LL;          // grids are padded to a multiple of 8
+}
+
+}  // namespace
+
+extern "C" {
+
+int unetrir_auralize_fft_supported(int K) { return K >= 1 && K <= AF_MAXK ? 1 : 0; }
+
+int unetrir_auralize_fft_block(int K) { return unetrir_auralize_fft_supported(K) ? AF_P : 0; }
+
+size_t unetrir_auralize_fft_ws_bytes(int B, int K, int N, long long dry_stride, int L) {
+    long long Q, J, nH, nX;
+    return af_plan(B, K, N, dry_stride, L, Q, J, nH, nX) ? (size_t)(nH + nX) * AF_SPEC : 0;
+}
+
+int unetrir_auralize_fft_f32(const float* rir, const float* dry, float* out, int B, int K, int N, long long dry_stride, int L, void* ws,
+                             size_t ws_bytes, unetrir_stream_t stream) {
+    long long Q, J, nH, nX;
+    if (!rir || !dry || !out || !ws || !af_plan(B, K, N, dry_stride, L, Q, J, nH, nX)) return UNETRIR_EINVAL;
+    if (ws_bytes < (size_t)(nH + nX) * AF_SPEC || ((uintptr_t)ws & 15)) return UNETRIR_EINVAL;
+    float4* spec = static_cast<float4*>(ws);
+    hipLaunchKernelGGL(auralize_fft_spectra_kernel, dim3(af_grid(nH + nX)), dim3(AF_THREADS), 0, (hipStream_t)stream, rir, dry, spec, K,
+                       N, dry_stride, (int)Q, (int)J, (int)nH, (int)nX);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const long long JG = (J + AF_G - 1) / AF_G;
+    hipLaunchKernelGGL(auralize_fft_render_kernel<AF_G>, dim3(af_grid((long long)B * JG)), dim3(AF_THREADS), 0, (hipStream_t)stream,
+                       (const float4*)spec, out, (int)Q, (int)J, (int)JG, L, (int)nH, dry_stride == 0 ? 1 : B, B);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -785,10 +785,8 @@ def auralize_supported(K):
     return bool(_lib.lib().unetrir_auralize_supported(int(K)))
 
 
-def auralize_f32(rir, dry, out):
-    """out fp32 [B, L] = the first L samples of rir fp32 [B, K] convolved with dry fp32 [N] (one dry signal heard through every row) or
-    [B, N] (one per row), 1 <= L <= N + K - 1: direct form on the fp32 matrix cores in one launch on the current stream, every element
-    an fp32 fma chain in ascending tap order (include/unetrir.h)."""
+def _auralize_args(rir, dry, out):
+    """The tensor checks of both forms of auralize -> (B, K, N, L)"""
     named = ((rir, "rir"), (dry, "dry"), (out, "out"))
     if not all(isinstance(t, torch.Tensor) for t, _ in named):
         raise ValueError("auralize: rir, dry and out must be tensors")
@@ -808,9 +806,51 @@ def auralize_f32(rir, dry, out):
     for t, what in named:
         if not t.is_cuda or t.device != rir.device:
             raise ValueError(f"auralize: {what} must be a CUDA tensor on the device of rir (there is no CPU path)")
+    return B, K, N, L
+
+
+def auralize_f32(rir, dry, out):
+    """out fp32 [B, L] = the first L samples of rir fp32 [B, K] convolved with dry fp32 [N] (one dry signal heard through every row) or
+    [B, N] (one per row), 1 <= L <= N + K - 1: direct form on the fp32 matrix cores in one launch on the current stream, every element
+    an fp32 fma chain in ascending tap order (include/unetrir.h)."""
+    B, K, N, L = _auralize_args(rir, dry, out)
     if not auralize_supported(K):
         raise ValueError(f"auralize: impulse responses of {K} taps are not supported (1 ... 16384)")
     check(_lib.lib().unetrir_auralize_f32(_p(rir), _p(dry), _p(out), B, K, N, 0 if dry.dim() == 1 else N, L, _stream()), "auralize")
+
+
+def auralize_fft_supported(K):
+    """Whether `auralize_fft_f32` takes impulse responses of K taps (1 <= K <= 16384)."""
+    return bool(_lib.lib().unetrir_auralize_fft_supported(int(K)))
+
+
+def auralize_fft_block(K):
+    """The block P of the overlap-save form for K taps (2048; 0: K is not supported)."""
+    return int(_lib.lib().unetrir_auralize_fft_block(int(K)))
+
+
+def auralize_fft_ws_bytes(B, K, N, dry_stride, L):
+    """Bytes `auralize_fft_f32` keeps in its workspace: the spectra of h and x (0: arguments the call refuses)."""
+    return int(_lib.lib().unetrir_auralize_fft_ws_bytes(int(B), int(K), int(N), int(dry_stride), int(L)))
+
+
+def auralize_fft_f32(rir, dry, out, ws: Workspace = None):
+    """`auralize_f32` by partitioned overlap-save with FFTs in LDS: two launches on the current stream, within the bound of
+    include/unetrir.h of the convolution, not the direct form's bits.  ws: a Workspace that is grown to what the call needs (a
+    temporary one when None)."""
+    B, K, N, L = _auralize_args(rir, dry, out)
+    if not auralize_fft_supported(K):
+        raise ValueError(f"auralize: impulse responses of {K} taps are not supported (1 ... 16384)")
+    stride = 0 if dry.dim() == 1 else N
+    need = auralize_fft_ws_bytes(B, K, N, stride, L)
+    if ws is None:
+        ws = Workspace(rir.device, need)
+    elif not isinstance(ws, Workspace) or ws.buf.device != rir.device:
+        raise ValueError(f"auralize: ws must be a Workspace on {rir.device}")
+    else:
+        ws.reserve(need)
+    check(_lib.lib().unetrir_auralize_fft_f32(_p(rir), _p(dry), _p(out), B, K, N, stride, L, ws.ptr, ws.nbytes, _stream()),
+          "auralize_fft")
 
 
 def griffinlim_ws_bytes(B, n_bins, n_frames, n_fft):
