@@ -727,6 +727,35 @@ int unetrir_spectral_loss_f32(const float* wav_pred, const float* wav_true, int 
                               double sc_weight, double log_weight, double weight, double inv_global_batch, int accumulate, float* dwav,
                               double* spectral_out, float* loss_out, void* ws, size_t ws_bytes, unetrir_stream_t stream);
 
+/* ---- the FFT form of the multi-resolution STFT loss: the same definition with fp32 transforms in LDS (spectralloss_fft.hip, fft_lds.h).
+ *
+ * unetrir_spectral_loss_fft_f32: arguments and their rules as unetrir_spectral_loss_f32; the same E0, P0, delta, M_x, SC, LM, Q_b, L,
+ * gradient, frames, fold of the reflected edges and order of the resolutions.  Only the arithmetic differs: window taps, spectra and
+ * every per-bin quantity are fp32 (a real transform of N points as a complex FFT of N / 2 points, radix-8 Stockham, twiddles correctly
+ * rounded from fp64); every reduction (E0, sum w^2, the three sums of a (row, resolution), the sums over r and b, the overlap-add and
+ * fold of a sample) is accumulated in fp64 from fp32 terms in a fixed order; every element of dwav is rounded once (or, with
+ * accumulate, dwav[i] = (float)((double)dwav[i] + g)).  The adjoint recomputes the spectra of its frames: the workspace holds the
+ * partial sums and the windowed fp32 frames only (4 bytes per frame and window tap; no spectra).
+ * Four launches with dwav, two without, whatever B and R are; no atomics, every order fixed: two runs give the same bits and a row's
+ * bits depend neither on B nor on its place in the batch; nothing is allocated, cleared or waited for.  A row with a silent target
+ * counts nothing and gets zeros.  The bits are NOT those of unetrir_spectral_loss_f32.
+ * Error.  No derived per-element bound: the result is that of an fp32 STFT and its adjoint.  With e(v) = max_t |v - dwav64| /
+ * max_t |dwav64| per row against the fp64 definition, the tests hold e(kernel) <= 4 e(complex64 torch.stft under autograd) + 2^-22
+ * on independent y^ and y (the complex64 form itself: about 1e-4 of the peak at the default resolutions), and spectral_out[0:2] and the
+ * increment of loss_out to a relative 64 log2(N_max) 2^-24 (6.66 u per radix-2 level in L2 [Higham, Theorem 24.2], twice for M_y^ - M_y,
+ * twice for the square, a factor |M| / |M_y^ - M_y| <= 2 on independent data, rounded up); spectral_out[2] is exact.  e grows as
+ * y^ -> y, where M_y^ - M_y cancels: unetrir_spectral_loss_f32 is the form for a gradient that must be held to a
+ * bound.  Inputs are taken to be finite and delta P0 to be a normal fp32 number.
+ * unetrir_spectral_loss_fft_supported: 1 for n_fft in {128, 256, 512, 1024}, 2 <= win_length <= n_fft, 1 <= hop_length,
+ * n_fft / 2 + 1 <= T <= 16384, else 0.  ws: unetrir_spectral_loss_fft_ws_bytes(B, T, R, res) bytes, 8-byte aligned (0: B <= 0, R
+ * outside 1...8, a null res, an unsupported resolution, or more than 2^31 - 1 workgroups in a launch).
+ * UNETRIR_EINVAL before the device is touched: in the cases of unetrir_spectral_loss_f32, with this predicate and this size. */
+int unetrir_spectral_loss_fft_supported(int T, int n_fft, int win_length, int hop_length);
+size_t unetrir_spectral_loss_fft_ws_bytes(int B, int T, int R, const int* res);
+int unetrir_spectral_loss_fft_f32(const float* wav_pred, const float* wav_true, int B, int T, int R, const int* res, double floor_db,
+                                  double sc_weight, double log_weight, double weight, double inv_global_batch, int accumulate, float* dwav,
+                                  double* spectral_out, float* loss_out, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+
 /* ---- auralization: dry audio rendered through impulse responses, y_b = h_b * x_b (auralize.hip; the formulation is in its header).
  *
  * unetrir_auralize_f32: rir fp32 [B][K] (h); dry fp32 [N] with dry_stride = 0 (one dry signal for all rows) or [B][dry_stride], dry_stride

@@ -86,6 +86,9 @@ def main():
                     help="the loss's transforms: n_fft:win_length:hop_length, comma-separated (1 to 8)")
     ap.add_argument("--spectral-floor-db", type=float, default=60.0, metavar="DB",
                     help="the magnitudes are smoothed DB below the power a bin carries with the target's energy spread evenly")
+    ap.add_argument("--spectral-method", choices=("dft", "fft"), default="dft",
+                    help="the loss's transforms: fp64 DFTs on the matrix cores, held to a derived bound (dft), or fp32 FFTs in LDS (fft: "
+                         "n_fft 128, 256, 512 or 1024)")
     ap.add_argument("--epochs", type=int, default=500)
     ap.add_argument("--lr", type=float, default=5e-7)
     ap.add_argument("--no-lr-decay", action="store_true")
@@ -114,7 +117,7 @@ def main():
     if a.spectral_loss is not None:
         try:
             res = tuple(tuple(int(v) for v in r.split(":")) for r in a.spectral_resolutions.split(","))
-            spectral = U.SpectralLoss(weight=a.spectral_loss, resolutions=res, floor_db=a.spectral_floor_db)
+            spectral = U.SpectralLoss(weight=a.spectral_loss, resolutions=res, floor_db=a.spectral_floor_db, method=a.spectral_method)
         except ValueError as e:
             raise SystemExit(f"--spectral-resolutions: {e}")
     wavs = wave is not None or decay is not None or spectral is not None

@@ -203,6 +203,12 @@ _SIGS = {
     "unetrir_spectral_loss_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double,
                                             C.c_double, C.c_double, C.c_double, C.c_int, c_f32p, C.c_void_p, c_f32p, C.c_void_p,
                                             C.c_size_t, c_stream]),
+    # the same loss with fp32 FFTs in LDS (spectralloss_fft.hip)
+    "unetrir_spectral_loss_fft_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "unetrir_spectral_loss_fft_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "unetrir_spectral_loss_fft_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double,
+                                                C.c_double, C.c_double, C.c_double, C.c_int, c_f32p, C.c_void_p, c_f32p, C.c_void_p,
+                                                C.c_size_t, c_stream]),
     # y = h * x on the fp32 matrix cores (auralize.hip)
     "unetrir_auralize_supported": (C.c_int, [C.c_int]),
     "unetrir_auralize_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, c_stream]),

@@ -1,7 +1,8 @@
 // fft_lds.h - a complex fp32 FFT of M = 64 ... 2048 points (a power of two) held in LDS and worked by ONE workgroup of M / 8 threads, and
 // the packing that turns it into a real transform of 2 M points.  Self-contained; every function is __host__ __device__ so that the
 // same arithmetic can be walked thread by thread on the host (done for every M against a naive fp64 DFT: relative L2 error 0.9e-7
-// at M = 64 to 1.3e-7 at 2048, both directions and the real transform; on the device only M = 2048 is instantiated so far).
+// at M = 64 to 1.3e-7 at 2048, both directions and the real transform; on the device M = 2048 is instantiated by auralize_fft.hip and
+// M = 64, 128, 256, 512 by spectralloss_fft.hip, several images side by side in one workgroup: see there).
 //
 // Scheme.  Stockham autosort, decimation in time, radix 8 while 8 divides what is left and one last pass of radix 4 or 2 (M = 2048:
 // 8 x 8 x 8 x 4, four passes).  A pass of radix R over sub-transforms of NS points (NS = the product of the radices before it):

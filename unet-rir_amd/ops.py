@@ -755,6 +755,33 @@ def spectral_loss(wav_pred, wav_true, spectral_out, ws: Workspace, resolutions, 
     on wav_pred, written or with accumulate added: spectral_out fp64 [3] = (sum_b mean_r SC, sum_b mean_r LM, rows counted);
     loss_out[0] += weight / global_batch * (sc_weight spectral_out[0] + log_weight spectral_out[1]).  Four launches with dwav, two
     without (include/unetrir.h)."""
+    _spectral_loss_call("unetrir_spectral_loss", "spectral_loss", wav_pred, wav_true, spectral_out, ws, resolutions, floor_db, sc_weight,
+                        log_weight, weight, global_batch, dwav, accumulate, loss_out)
+
+
+def spectral_loss_fft_supported(T, n_fft, win_length, hop_length):
+    """Whether `spectral_loss_fft` takes waveforms of T samples at this resolution (n_fft 128, 256, 512 or 1024, 2 <= win_length <=
+    n_fft, hop_length >= 1, n_fft / 2 + 1 <= T <= 16384)."""
+    return bool(_lib.lib().unetrir_spectral_loss_fft_supported(int(T), int(n_fft), int(win_length), int(hop_length)))
+
+
+def spectral_loss_fft_ws_bytes(B, T, resolutions):
+    """Bytes `spectral_loss_fft` keeps in its workspace (0: a shape the kernels do not take)."""
+    arr, R = _res_array(resolutions)
+    return int(_lib.lib().unetrir_spectral_loss_fft_ws_bytes(int(B), int(T), R, arr))
+
+
+def spectral_loss_fft(wav_pred, wav_true, spectral_out, ws: Workspace, resolutions, floor_db=60.0, sc_weight=1.0, log_weight=1.0, weight=1.0,
+                      global_batch=None, dwav=None, accumulate=False, loss_out=None):
+    """`spectral_loss` with fp32 FFTs in LDS in place of the fp64 DFTs: the same arguments, outputs and launch counts, reductions in
+    fp64 from fp32 terms, every element of dwav rounded once; an fp32 transform's error, not the DFT form's bound (include/unetrir.h)."""
+    _spectral_loss_call("unetrir_spectral_loss_fft", "spectral_loss_fft", wav_pred, wav_true, spectral_out, ws, resolutions, floor_db,
+                        sc_weight, log_weight, weight, global_batch, dwav, accumulate, loss_out)
+
+
+def _spectral_loss_call(symbol, name, wav_pred, wav_true, spectral_out, ws, resolutions, floor_db, sc_weight, log_weight, weight,
+                        global_batch, dwav, accumulate, loss_out):
+    """The checks and the call of both forms of the spectral loss.  The messages carry the name `spectral_loss` for either."""
     if not isinstance(wav_pred, torch.Tensor) or not wav_pred.is_cuda or wav_pred.dim() != 2:
         raise ValueError("spectral_loss: wav_pred must be a CUDA tensor [B, T]")
     B, T = wav_pred.shape
@@ -772,12 +799,12 @@ def spectral_loss(wav_pred, wav_true, spectral_out, ws: Workspace, resolutions, 
         raise ValueError(f"spectral_loss: loss_out must be a contiguous float32 vector on {wav_pred.device}")
     arr, R = _res_array(resolutions)
     gb = B if global_batch is None else global_batch
-    need = int(_lib.lib().unetrir_spectral_loss_ws_bytes(B, T, R, arr))
+    ws_bytes, entry = getattr(_lib.lib(), symbol + "_ws_bytes"), getattr(_lib.lib(), symbol + "_f32")
+    need = int(ws_bytes(B, T, R, arr))
     if need:
         ws.reserve(need)
-    check(_lib.lib().unetrir_spectral_loss_f32(_p(wav_pred), _p(wav_true), B, T, R, arr, float(floor_db), float(sc_weight),
-                                               float(log_weight), float(weight), 1.0 / gb, int(bool(accumulate)), _p(dwav),
-                                               _p(spectral_out), _p(loss_out), ws.ptr, ws.nbytes, _stream()), "spectral_loss")
+    check(entry(_p(wav_pred), _p(wav_true), B, T, R, arr, float(floor_db), float(sc_weight), float(log_weight), float(weight), 1.0 / gb,
+                int(bool(accumulate)), _p(dwav), _p(spectral_out), _p(loss_out), ws.ptr, ws.nbytes, _stream()), name)
 
 
 def auralize_supported(K):
