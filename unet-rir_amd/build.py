@@ -67,8 +67,32 @@ def build_ablations(verbose=False):
     return build(force=False, verbose=verbose, extra_flags=["-DUNETRIR_ABLATIONS"], lib=ABL_LIB, obj_dir=os.path.join(HERE, "build_abl"))
 
 
+PROBE_DIR = os.path.join(os.path.dirname(HERE), "tests", "probe")
+PROBE_SRC = os.path.join(PROBE_DIR, "fft_probe.hip")
+PROBE_LIB = os.path.join(HERE, "libunetrir_probe.so")
+
+
+def probe_needs_build():
+    return _stale(PROBE_LIB, [PROBE_SRC, os.path.join(PROBE_DIR, "fft_walk.h"), os.path.join(CSRC, "fft_lds.h")])
+
+
+def build_probe(force=False, verbose=False):
+    """The tests' probe of csrc/fft_lds.h (tests/probe/fft_probe.hip: the header walked on the host and run on the device with no
+    consumer around it; loaded by tests/fft_probe.py).  A library of its own: nothing of it is in libunetrir.so or include/unetrir.h."""
+    if not force and not probe_needs_build():
+        return PROBE_LIB
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc] + FLAGS + ["-shared", "-I", CSRC, PROBE_SRC, "-o", PROBE_LIB]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    return PROBE_LIB
+
+
 if __name__ == "__main__":
-    if "--ablations" in sys.argv:
+    if "--probe" in sys.argv:
+        print(build_probe(force="--force" in sys.argv, verbose=True))
+    elif "--ablations" in sys.argv:
         print(build_ablations(verbose=True))
     else:
         print(build(force="--force" in sys.argv, verbose=True))

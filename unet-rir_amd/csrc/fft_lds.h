@@ -1,8 +1,13 @@
 // fft_lds.h - a complex fp32 FFT of M = 64 ... 2048 points (a power of two) held in LDS and worked by ONE workgroup of M / 8 threads, and
 // the packing that turns it into a real transform of 2 M points.  Self-contained; every function is __host__ __device__ so that the
-// same arithmetic can be walked thread by thread on the host (done for every M against a naive fp64 DFT: relative L2 error 0.9e-7
-// at M = 64 to 1.3e-7 at 2048, both directions and the real transform; on the device M = 2048 is instantiated by auralize_fft.hip and
-// M = 64, 128, 256, 512 by spectralloss_fft.hip, several images side by side in one workgroup: see there).
+// same arithmetic can be walked thread by thread on the host.  tests/probe/fft_walk.h is that walk and tests/test_fft_lds.py holds it,
+// for M = 64 ... 2048, both directions and the real transform, to an fp64 DFT: relative L2 error per image of uniform data 0.7e-7
+// (M = 64) to 1.2e-7 (2048) complex and 0.7e-7 to 1.2e-7 real - the figure depends on the data by +-20 % at M = 64 - which is 0.99 to
+// 1.25 times that of pocketfft in complex64 on the same image; an impulse's response is within 5.3 u (complex, real forward) or 9.8 u
+// (real inverse) of the closed form at every element, u = 2^-24; and the table below is the correctly rounded fp32 of cos / -sin at
+// all 4096 components.  tests/test_fft_lds_gpu.py holds the device to the bits of that walk.  On the device M = 2048 is instantiated
+// by auralize_fft.hip and M = 64, 128, 256, 512 by spectralloss_fft.hip, several images side by side in one workgroup: see there;
+// M = 1024 by the tests' probe (tests/probe/fft_probe.hip) alone.
 //
 // Scheme.  Stockham autosort, decimation in time, radix 8 while 8 divides what is left and one last pass of radix 4 or 2 (M = 2048:
 // 8 x 8 x 8 x 4, four passes).  A pass of radix R over sub-transforms of NS points (NS = the product of the radices before it):
