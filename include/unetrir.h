@@ -1012,6 +1012,36 @@ int unetrir_griffinlim_f32(const float* feat, int B, int H, int W, int n_bins, i
                            unetrir_stream_t stream);
 int unetrir_uniform_f32(float* out, long long n, unsigned long long seed, unsigned long long step, unetrir_stream_t stream);
 
+/* ---- the FFT form of the Griffin-Lim reconstruction (griffinlim_fft.hip): the definition above unchanged - the same S, angles0, loop,
+ *      window pair, envelope rule, trimming, pad modes, reading of momentum, init_phase / (seed, draw) - with fp32 state and fp32 FFTs
+ *      held in LDS (csrc/fft_lds.h) in place of fp64 state and fp64 DFTs.  That is the precision librosa itself keeps its angles in.
+ *      The iteration amplifies rounding (fastest with momentum), so there is NO bound per element: measured, the waveform stays within
+ *      1e-7 ... 1e-4 of the peak of the fp64 form's and reconstructs the magnitude equally well.  unetrir_griffinlim_f32 is
+ *      the form to hold a result to a bound; this one is for evaluation runs, which pay the loop on every batch.
+ *      State in ws, all fp32, [b][f][k]: S (the fp64 value of the DFT form rounded once) and three complex planes that take turns as
+ *      rebuilt, tprev and the plane being written; angles0 = the fp32 rounding of (cospi(2u), sinpi(2u)) taken in fp64.  S angles is not
+ *      stored: every synthesis forms it in its loader as S n(rebuilt - alpha tprev), n(a) = a / (hypotf(a) + 1e-16f), alpha = the fp32
+ *      rounding of momentum / (1 + momentum) (launch 0: S angles0; launch 1: tprev = 0).
+ *      n_iter + 2 launches on `stream` whatever B is: init, one launch per iteration (a workgroup inverse-transforms the frames that
+ *      reach its own frames' windows, overlap-adds them into a run of the waveform in LDS - ascending frame order per sample, fp32 - and
+ *      transforms its own frames forward: the intermediate waveform and the windowed frames never reach memory), and a last synthesis
+ *      that stores wav.  No allocation, no memset, no host synchronisation (capturable in a HIP graph); fixed summation orders and no
+ *      atomics: two runs are bit-identical, and a row's bits depend neither on B nor on its place in the batch.
+ *      unetrir_griffinlim_fft_supported: n_fft in {128, 256, 512, 1024}; n_bins = n_fft / 2 + 1; n_frames >= 2; 2 <= win_length <=
+ *      n_fft (any value); hop_length >= 1 and 4 hop_length >= win_length (at most four frames reach a sample); hop_length (n_frames -
+ *      1) > n_fft / 2 (one reflection reaches into the waveform; asked of both pad modes); hop_length n_frames + n_fft <= 2^31 - 1.
+ *      unetrir_griffinlim_fft_ws_bytes = 28 B n_frames n_bins rounded up to a multiple of 8 (7 fp32 planes), 0 for anything
+ *      unsupported or B outside 1 ... 65535.
+ *      UNETRIR_EINVAL before the device is touched: an unsupported geometry, B outside 1 ... 65535, n_bins > H, n_frames > W,
+ *      n_iter < 0, a negative or non-finite momentum, pad_mode outside {0, 1}, a null feat / wav / ws, ws not 8-byte aligned,
+ *      ws_bytes < unetrir_griffinlim_fft_ws_bytes. */
+int unetrir_griffinlim_fft_supported(int n_bins, int n_frames, int n_fft, int win_length, int hop_length);
+size_t unetrir_griffinlim_fft_ws_bytes(int B, int n_bins, int n_frames, int n_fft, int win_length, int hop_length);
+int unetrir_griffinlim_fft_f32(const float* feat, int B, int H, int W, int n_bins, int n_frames, int n_fft, int win_length,
+                               int hop_length, int pad_mode, int denormalize, int n_iter, float momentum, const float* init_phase,
+                               unsigned long long seed, unsigned long long draw, float* wav, void* ws, size_t ws_bytes,
+                               unetrir_stream_t stream);
+
 /* ---- output head behind UpSampling2D((2, 2)) (dl_models/u_net.py:247-248, resize_factor_0 = [2, 2]) without the up-sampled tensor
  *      (head_up2.hip): nearest-neighbour x2 followed by Conv2D(2, (6,6), 'same') is a 4x4 'same' convolution (pad 1 before, 2 after)
  *      with 8 output channels (o, a, b) on the coarse grid [B][h][w][C] followed by depth-to-space:

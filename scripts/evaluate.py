@@ -16,7 +16,7 @@
                with characteristics=True, shuffle=False, as rir_generation.py:67-70 (--rooms / --arrays filter it, default all)
 --synthetic N  N batches of `synthetic_batches`, which yields no waveforms: wav_true is the reconstruction of spec_out
 --algorithm    ph (default): reconstruct from the predicted phase; gl: Griffin-Lim from the predicted magnitude
-               (rir_generation.py:62, :137; --gl-iters, --gl-momentum, --gl-seed)
+               (rir_generation.py:62, :137; --gl-iters, --gl-momentum, --gl-seed; --gl-method fft: the fp32 FFT form of the loop)
 --acoustics    also score the room-acoustic figures (arrival of the direct sound, direct-to-reverberant ratio, C50, centre time,
                early decay time) of predicted against true waveform and write a fourth file, NAME_acoustics.csv
 """
@@ -126,6 +126,8 @@ def main():
     ap.add_argument("--gl-iters", type=int, default=32)
     ap.add_argument("--gl-momentum", type=float, default=0.99)
     ap.add_argument("--gl-seed", type=int, default=0)
+    ap.add_argument("--gl-method", choices=("dft", "fft"), default="dft",
+                    help="dft: fp64, held to a bound per element; fft: fp32 FFTs in LDS, librosa's own precision, faster")
     ap.add_argument("--acoustics", action="store_true")
     ap.add_argument("--out", required=True)
     ap.add_argument("--name", default="unet")
@@ -137,7 +139,7 @@ def main():
     dev = torch.device("cuda:0")
     model = build_model(a, dev)
     ev = U.Evaluator(model, diff_gen=a.diff_gen, algorithm=a.algorithm, gl_iters=a.gl_iters, gl_momentum=a.gl_momentum,
-                     gl_seed=a.gl_seed, acoustics=a.acoustics)
+                     gl_seed=a.gl_seed, gl_method=a.gl_method, acoustics=a.acoustics)
     for batch in (file_batches(a.data, dev) if a.data else dataset_batches(a, dev) if a.dataset else synthetic(a, dev)):
         ev.update(*batch)
     res = ev.result()

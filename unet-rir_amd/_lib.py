@@ -306,6 +306,11 @@ _SIGS = {
                                          C.c_int, C.c_int, C.c_float, c_f32p, C.c_ulonglong, C.c_ulonglong, c_f32p, C.c_void_p,
                                          C.c_size_t, c_stream]),
     "unetrir_uniform_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_ulonglong, c_stream]),
+    "unetrir_griffinlim_fft_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "unetrir_griffinlim_fft_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "unetrir_griffinlim_fft_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.c_float, c_f32p, C.c_ulonglong, C.c_ulonglong, c_f32p, C.c_void_p,
+                                             C.c_size_t, c_stream]),
     # tfa.optimizers.LAMB (lamb.hip)
     "unetrir_lamb_chunk_elems": (C.c_int, []),
     "unetrir_lamb_table_init": (C.c_longlong, [C.POINTER(LambSeg), C.c_int, C.c_void_p, C.c_longlong]),

@@ -33,38 +33,22 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "kernels.h"
+#include "griffinlim_common.h"
 
 namespace {
 
 constexpr int GL_MAX_NFFT = 1024;
-constexpr double GL_MD = 100.0;               // Normalizer.md (preprocess.py:23)
-constexpr double GL_EP = 1e-5;                // 10^(-md/20)    (preprocess.py:24)
-constexpr double GL_REF = 128.0;              // amp / 128      (preprocess.py:27)
-constexpr double GL_TINY32 = 1.1754943508222875e-38;   // numpy.finfo(float32).tiny: librosa's envelope threshold
 constexpr int GL_TM = 16;                     // frames per workgroup = rows of one MFMA tile
 constexpr int GL_KC = 128;                    // K elements staged in LDS at a time
 constexpr int GL_LD = GL_KC + 4;              // LDS row stride in doubles: 16 rows land 8 banks apart (2-way, the b64 minimum)
 constexpr int GL_T = 256;                     // 4 waves, one 16-column tile each
 
-#define GL_GOLD64 0x9E3779B97F4A7C15ULL
-// "UNIFRM64": separates the phase key from the keys dropout_mask_kernel and normal_kernel derive from the same (seed, step)
-#define GL_UNIFORM_TAG 0x554E4946524D3634ULL
-
 typedef double gl_d4 __attribute__((ext_vector_type(4)));
 
-// Element i of draw (seed, step) - the recipe of include/unetrir.h (unetrir_uniform_f32)
-__device__ __forceinline__ unsigned long long uniform_key(unsigned long long seed, unsigned long long step) {
-    return mix64(mix64(seed * GL_GOLD64 + step) ^ GL_UNIFORM_TAG);
-}
-__device__ __forceinline__ float uniform_at(unsigned long long key, long long i) {
-    const unsigned long long r = mix64(key + GL_GOLD64 * (unsigned long long)(i + 1));
-    return (float)(unsigned)(r >> 40) * (1.0f / 16777216.0f);          // top 24 bits -> [0, 1)
-}
-
 __global__ void uniform_kernel(float* __restrict__ out, long long n, unsigned long long seed, unsigned long long step) {
-    const unsigned long long key = uniform_key(seed, step);
+    const unsigned long long key = gl_uniform_key(seed, step);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        out[i] = uniform_at(key, i);
+        out[i] = gl_uniform_at(key, i);
 }
 
 // periodic Hann of win samples centred in n_fft zeros, tap n (features.hip)
@@ -84,7 +68,7 @@ __global__ __launch_bounds__(256) void gl_init_kernel(const float* __restrict__ 
                                                       const float* __restrict__ init_phase, unsigned long long seed,
                                                       unsigned long long draw, double* __restrict__ S, double* __restrict__ spec_re,
                                                       double* __restrict__ spec_im) {
-    const unsigned long long key = uniform_key(seed, draw);
+    const unsigned long long key = gl_uniform_key(seed, draw);
     const long long n = (long long)g.B * g.n_frames * g.n_bins;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         const int k = (int)(e % g.n_bins);
@@ -93,7 +77,7 @@ __global__ __launch_bounds__(256) void gl_init_kernel(const float* __restrict__ 
         double amp = (double)feat[(((size_t)b * 2) * g.H + k) * g.W + f];
         if (denormalize) amp = (pow(10.0, (amp * GL_MD - GL_MD) / 20.0) - GL_EP) * GL_REF;
         const long long i = ((long long)b * g.n_bins + k) * g.n_frames + f;
-        const float u = init_phase ? init_phase[i] : uniform_at(key, i);
+        const float u = init_phase ? init_phase[i] : gl_uniform_at(key, i);
         double sn, cs;
         sincospi(2.0 * (double)u, &sn, &cs);
         S[e] = amp;
@@ -269,19 +253,6 @@ bool gl_geometry_ok(int B, int n_bins, int n_frames, int n_fft) {
 // workspace in doubles: S, spec (2 planes), rebuilt x 2 (2 planes each) over B n_frames n_bins, then the windowed frames
 // B n_frames n_fft (win_length <= n_fft taps are used)
 size_t gl_plane(int B, int n_bins, int n_frames) { return (size_t)B * n_frames * n_bins; }
-
-// The ABI carries momentum as a float, but librosa's is a double and 32 iterations carry the 2.4e-9 between 0.99f and 0.99 into
-// the waveform at 1e-8...3e-7 of its peak.  The argument is therefore read as the shortest decimal that rounds to the float given
-// (0.99f -> 0.99, as numpy prints a float32): the number the caller wrote.
-double gl_decimal(float v) {
-    char buf[40];
-    for (int p = 1; p <= 9; ++p) {
-        snprintf(buf, sizeof buf, "%.*e", p - 1, (double)v);
-        const double d = strtod(buf, nullptr);
-        if ((float)d == v) return d;
-    }
-    return (double)v;
-}
 
 unsigned gl_grid(long long n) {
     long long b = (n + 255) / 256;

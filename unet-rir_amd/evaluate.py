@@ -114,8 +114,9 @@ class Evaluator:
     `Autoencoder` of this package).  `diff_gen` (:173-176, :190-193): the phase that is scored and reconstructed is
     `pred[..., 1] + spec_in[..., 1]` while `mse_spec` keeps the raw prediction.  `room` of a batch is a sequence of names out
     of `rooms` or an integer tensor of indices into it, on the device; anything else counts in the global figures only.
-    `algorithm` 'gl' (:176-178 with algorithm='gl'): the waveform comes from `GriffinLim(gl_iters, gl_momentum, seed=gl_seed)` on
-    the predicted magnitude; the phase plane - and `diff_gen`'s sum - still feed the phase figure but not the waveform.
+    `algorithm` 'gl' (:176-178 with algorithm='gl'): the waveform comes from `GriffinLim(gl_iters, gl_momentum, seed=gl_seed,
+    method=gl_method)` on the predicted magnitude ("fft": the fp32 form, the one meant for evaluation runs); the phase plane - and
+    `diff_gen`'s sum - still feed the phase figure but not the waveform.
     `acoustics=True` adds the room-acoustic errors of `ACOUSTIC_ERRORS` (windows `n_pre`, `n_dir`, `n_early` in samples at `fs`, see
     `acoustics`) of every batch that comes with its waveform pair: two more launches behind the accumulation, inside the scoring
     stage's time, and their running sums share the one read-back.
@@ -125,17 +126,20 @@ class Evaluator:
     times come from HIP events recorded on the stream and are read in `result()`."""
 
     def __init__(self, model, diff_gen=False, rooms=ROOMS, n50=2400, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH,
-                 hop_length=HOP_LENGTH, algorithm="ph", gl_iters=32, gl_momentum=0.99, gl_seed=0, acoustics=False, n_pre=120, n_dir=120,
-                 n_early=2400, fs=48000):
+                 hop_length=HOP_LENGTH, algorithm="ph", gl_iters=32, gl_momentum=0.99, gl_seed=0, gl_method="dft", acoustics=False,
+                 n_pre=120, n_dir=120, n_early=2400, fs=48000):
         self.model, self.diff_gen, self.rooms, self.n50 = model, bool(diff_gen), tuple(rooms), int(n50)
         if not self.rooms:
             raise ValueError("at least one room")
         if algorithm not in ("ph", "gl"):
             raise ValueError("algorithm must be 'ph' or 'gl'")
+        if gl_method not in ("dft", "fft"):
+            raise ValueError(f'gl_method must be "dft" or "fft", not {gl_method!r}')
         self.algorithm = algorithm
         self.des_shape, self.n_fft, self.win_length, self.hop_length = tuple(des_shape), n_fft, win_length, hop_length
         self._index = {r: i for i, r in enumerate(self.rooms)}
-        self._post = PostProcess(algorithm="ph") if algorithm == "ph" else GriffinLim(gl_iters, gl_momentum, seed=gl_seed)
+        self._post = (PostProcess(algorithm="ph") if algorithm == "ph" else
+                      GriffinLim(gl_iters, gl_momentum, seed=gl_seed, method=gl_method))
         self.acoustics, self.n_pre, self.n_dir, self.n_early, self.fs = bool(acoustics), int(n_pre), int(n_dir), int(n_early), float(fs)
         if min(self.n_pre, self.n_dir, self.n_early) < 0 or not self.fs > 0:
             raise ValueError("n_pre, n_dir and n_early are sample counts >= 0 and fs is positive")

@@ -188,13 +188,21 @@ class GriffinLim:
     The random initial phases are draw number `draws` of stream `seed` (ops.uniform); the counter advances by one per call, so
     successive calls get fresh phases and a rebuilt object with the same seed repeats them.  `init_phase` (fp32
     [B, n_bins, n_frames] or [n_bins, n_frames], turns in [0, 1)) replaces the draw and leaves the counter alone.  The fp64
-    workspace is kept while the shape holds."""
+    workspace is kept while the shape holds.
 
-    def __init__(self, n_iter=32, momentum=0.99, pad_mode="reflect", seed=0):
+    `method` "dft" (the default) is that fp64 form, the one to hold a result to a bound; "fft" runs the same loop with fp32 state and
+    fp32 FFTs in LDS (csrc/griffinlim_fft.hip): librosa's own complex64 precision, n_iter + 2 launches instead of 2 n_iter + 3 - the
+    form for evaluation runs.  It takes n_fft 128 ... 1024 with hop_length >= win_length / 4 (ops.griffinlim_fft_supported); any other
+    geometry raises in post_process.  The draws, `init_phase`, the layouts, `out=` and the kept workspace are the same for both."""
+
+    def __init__(self, n_iter=32, momentum=0.99, pad_mode="reflect", seed=0, method="dft"):
         if n_iter < 0 or momentum < 0:
             raise ValueError("n_iter and momentum must not be negative")
         if pad_mode not in ops.PAD_MODES:
             raise ValueError(f"pad_mode must be one of {sorted(ops.PAD_MODES)}")
+        if method not in ("dft", "fft"):
+            raise ValueError(f'method must be "dft" or "fft", not {method!r}')
+        self.method = method
         self.n_iter, self.momentum, self.pad_mode, self.seed = int(n_iter), float(momentum), pad_mode, int(seed)
         self.algorithm = "gl"
         self.waveform = None
@@ -204,6 +212,10 @@ class GriffinLim:
     def post_process(self, feature, vector=None, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH, hop_length=HOP_LENGTH,
                      sr=SAMPLE_RATE, nhwc=None, out=None, init_phase=None):
         f, single = _feature_nchw(feature, nhwc)
+        if self.method == "fft" and not ops.griffinlim_fft_supported(des_shape[0], des_shape[1], n_fft, win_length, hop_length):
+            raise ValueError(f'GriffinLim(method="fft") does not take des_shape {tuple(des_shape)}, n_fft {n_fft}, win_length '
+                             f'{win_length}, hop_length {hop_length} (n_fft 128 ... 1024, n_bins = n_fft / 2 + 1, hop_length >= '
+                             f'win_length / 4, hop_length (n_frames - 1) > n_fft / 2); use method="dft"')
         wav = out if out is not None else torch.empty((f.shape[0], hop_length * (des_shape[1] - 1)), dtype=torch.float32,
                                                       device=f.device)
         if init_phase is not None:
@@ -212,9 +224,9 @@ class GriffinLim:
             init_phase = (init_phase.unsqueeze(0) if init_phase.dim() == 2 else init_phase).contiguous().float()
         if self._ws is None or self._ws.device != f.device:
             self._ws = ops.Workspace(f.device)
-        ops.griffinlim(f, wav, des_shape[0], des_shape[1], n_fft, win_length, hop_length, self._ws, pad_mode=self.pad_mode,
-                       denormalize=True, n_iter=self.n_iter, momentum=self.momentum, init_phase=init_phase, seed=self.seed,
-                       draw=self.draws)
+        op = ops.griffinlim_fft if self.method == "fft" else ops.griffinlim
+        op(f, wav, des_shape[0], des_shape[1], n_fft, win_length, hop_length, self._ws, pad_mode=self.pad_mode, denormalize=True,
+           n_iter=self.n_iter, momentum=self.momentum, init_phase=init_phase, seed=self.seed, draw=self.draws)
         if init_phase is None:
             self.draws += 1
         self.waveform = wav[0] if single else wav

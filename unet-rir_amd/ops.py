@@ -890,6 +890,17 @@ def griffinlim(feat, wav, n_bins, n_frames, n_fft, win_length, hop_length, ws: W
     """feat fp32 [B, 2, H, W] (plane 0, the magnitude, alone is read) -> wav fp32 [B, hop (n_frames - 1)]: un_pad +
     Normalizer.denormalize + librosa.griffinlim (postprocess.py:47-50, :69-71, :130-131) for the whole batch, fp64 inside.
     init_phase fp32 [B, n_bins, n_frames] in turns, or None: draw (seed, draw) of `uniform` over that shape."""
+    B, H, W = _griffinlim_gate(feat, wav, n_bins, n_frames, hop_length, pad_mode, init_phase)
+    need = griffinlim_ws_bytes(B, n_bins, n_frames, n_fft)
+    if need:
+        ws.reserve(need)
+    check(_lib.lib().unetrir_griffinlim_f32(_p(feat), B, H, W, n_bins, n_frames, n_fft, win_length, hop_length, PAD_MODES[pad_mode],
+                                            int(denormalize), int(n_iter), float(momentum), _p(init_phase), int(seed), int(draw),
+                                            _p(wav), ws.ptr, ws.nbytes, _stream()), "griffinlim")
+
+
+def _griffinlim_gate(feat, wav, n_bins, n_frames, hop_length, pad_mode, init_phase):
+    """The tensor checks of both forms of griffinlim -> (B, H, W)"""
     if feat.dtype != torch.float32 or wav.dtype != torch.float32 or not feat.is_contiguous() or not wav.is_contiguous():
         raise ValueError("griffinlim takes contiguous fp32 tensors")
     if feat.dim() != 4 or feat.shape[1] != 2 or wav.dim() != 2 or wav.shape[0] != feat.shape[0] or \
@@ -900,12 +911,32 @@ def griffinlim(feat, wav, n_bins, n_frames, n_fft, win_length, hop_length, ws: W
     B, _, H, W = feat.shape
     if init_phase is not None:
         _f32c(init_phase, (B, n_bins, n_frames), "init_phase", feat)
-    need = griffinlim_ws_bytes(B, n_bins, n_frames, n_fft)
+    return B, H, W
+
+
+def griffinlim_fft_supported(n_bins, n_frames, n_fft, win_length, hop_length):
+    """Whether `griffinlim_fft` takes this geometry: n_fft 128, 256, 512 or 1024, n_bins = n_fft / 2 + 1, n_frames >= 2, 2 <= win_length
+    <= n_fft, hop_length >= win_length / 4, hop_length (n_frames - 1) > n_fft / 2 (include/unetrir.h)."""
+    return bool(_lib.lib().unetrir_griffinlim_fft_supported(int(n_bins), int(n_frames), int(n_fft), int(win_length), int(hop_length)))
+
+
+def griffinlim_fft_ws_bytes(B, n_bins, n_frames, n_fft, win_length, hop_length):
+    """Bytes of fp32 state `griffinlim_fft` keeps in its workspace (0: a geometry the kernels do not take)."""
+    return int(_lib.lib().unetrir_griffinlim_fft_ws_bytes(int(B), int(n_bins), int(n_frames), int(n_fft), int(win_length),
+                                                          int(hop_length)))
+
+
+def griffinlim_fft(feat, wav, n_bins, n_frames, n_fft, win_length, hop_length, ws: Workspace, pad_mode="reflect", denormalize=True,
+                   n_iter=32, momentum=0.99, init_phase=None, seed=0, draw=0):
+    """`griffinlim` with fp32 state and fp32 FFTs in LDS in place of fp64 state and fp64 DFTs: the same arguments and output, n_iter + 2
+    launches; librosa's own complex64 precision, not a bound per element (include/unetrir.h)."""
+    B, H, W = _griffinlim_gate(feat, wav, n_bins, n_frames, hop_length, pad_mode, init_phase)
+    need = griffinlim_fft_ws_bytes(B, n_bins, n_frames, n_fft, win_length, hop_length)
     if need:
         ws.reserve(need)
-    check(_lib.lib().unetrir_griffinlim_f32(_p(feat), B, H, W, n_bins, n_frames, n_fft, win_length, hop_length, PAD_MODES[pad_mode],
-                                            int(denormalize), int(n_iter), float(momentum), _p(init_phase), int(seed), int(draw),
-                                            _p(wav), ws.ptr, ws.nbytes, _stream()), "griffinlim")
+    check(_lib.lib().unetrir_griffinlim_fft_f32(_p(feat), B, H, W, n_bins, n_frames, n_fft, win_length, hop_length, PAD_MODES[pad_mode],
+                                                int(denormalize), int(n_iter), float(momentum), _p(init_phase), int(seed), int(draw),
+                                                _p(wav), ws.ptr, ws.nbytes, _stream()), "griffinlim_fft")
 
 
 def uniform(out, seed, step):
