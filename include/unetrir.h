@@ -492,6 +492,19 @@ int unetrir_head6x6_fwd_bf16(const unetrir_bf16* x, int ldx, int B, int H, int W
                              const float* bias, float* y, int ldy, unetrir_stream_t stream);
 int unetrir_head6x6_wgrad_bf16(const unetrir_bf16* x, int ldx, int B, int H, int W, int C, const unetrir_bf16* dy,
                                int lddy, float* dw, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+/* ---- the stem's gradients through the next layer (bf16 storage).  Conv2D(64, 3x3) on the 2-channel input is followed by
+ *      Conv2D(64 -> 64, 3x3) with nothing in between (dl_models/u_net.py:269-276, :366), so the stem's kernel and bias
+ *      gradients follow from g = dL/d(output of the second convolution) [B][H][W][ldg] (64 channels), the network input x
+ *      [B][H][W][ldx] (channels 0, 1 read) and the second kernel's transposed bf16 work copy w1t [64][9][64] - a 5 x 5
+ *      correlation of x with g, border terms for the zero padding of the tensor between the two layers, and a contraction with
+ *      w1t - without the 64-channel data gradient between them.  dw0 [64][3][3][ldw] = gradient + reg_coef * w0 (channels >= 2:
+ *      reg_coef * w0), db0 [64].  Fixed summation order: bit-reproducible.  Supported for 64 -> 64 channels, W <= 4096, ldg a
+ *      multiple of 8, ldx even; ws >= unetrir_stem_composite_ws_bytes(B), 8-byte aligned. */
+int unetrir_stem_composite_supported(int B, int H, int W, int C0, int C1);
+size_t unetrir_stem_composite_ws_bytes(int B);
+int unetrir_stem_composite_bf16(const unetrir_bf16* g, int ldg, const unetrir_bf16* x, int ldx, int B, int H, int W,
+                                const unetrir_bf16* w1t, float reg_coef, const float* w0, float* dw0, int ldw, float* db0,
+                                void* ws, size_t ws_bytes, unetrir_stream_t stream);
 /* ---- fused column statistics (bf16).  The 3x3 stride-1 kernels that serve most layers can emit, per 16 x 32 pixel tile,
  *      the per-channel (sum, sum of squares) of the bf16 output they store: colstat is [rows][N][2] floats with N the
  *      convolution's output channels (forward: Cout, data gradient: Cin).  BatchNormalization statistics (dl_models/

@@ -32,6 +32,7 @@ def rel(a, b):
 
 spec_in, emb, spec_out = bench.synthetic_batch(B, H, H, dev, 1234)
 e32, e16 = build("f32"), build("bf16")
+e16.stem_composite = False          # the trace compares every intermediate gradient, d enc1.down included: the path that forms it
 e16.load_keras_params(e32.export_keras_params())
 res = {"forward": [], "backward": [], "vec": {}}
 for flag in (False,):

@@ -933,6 +933,21 @@ int unetrir_conv2d_transpose_wgrad_bf16(const unetrir_conv_geom* g, const unetri
     return run_wgrad<BF16>(g, true, x, ldx, dy, lddy, dw, reg_coef, w, ws, ws_bytes, nullptr, (hipStream_t)stream);
 }
 
+/* The stem's weight and bias gradients through the next 3x3 layer, without the data gradient between them (stem_composite.hip). */
+int unetrir_stem_composite_supported(int B, int H, int W, int C0, int C1) { return stem_composite_applies(B, H, W, C0, C1) ? 1 : 0; }
+
+size_t unetrir_stem_composite_ws_bytes(int B) { return B > 0 ? stem_composite_ws_bytes(B) : 0; }
+
+int unetrir_stem_composite_bf16(const unetrir_bf16* g, int ldg, const unetrir_bf16* x, int ldx, int B, int H, int W,
+                                const unetrir_bf16* w1t, float reg_coef, const float* w0, float* dw0, int ldw, float* db0, void* ws,
+                                size_t ws_bytes, unetrir_stream_t stream) {
+    if (!g || !x || !w1t || !dw0 || !db0 || !ws || !stem_composite_applies(B, H, W, 64, 64) || ldg < 64 || (ldg & 7) || ldx < 2 ||
+        (ldx & 1) || ldw < 2 || ((uintptr_t)g & 15) || ((uintptr_t)x & 3) || ((uintptr_t)ws & 7) || (reg_coef != 0.f && !w0) ||
+        ws_bytes < stem_composite_ws_bytes(B))
+        return UNETRIR_EINVAL;
+    return launch_stem_composite(g, ldg, x, ldx, B, H, W, w1t, reg_coef, w0, dw0, ldw, db0, ws, (hipStream_t)stream);
+}
+
 /* fp32 master weights [N][T][C] -> bf16 work copies: same orientation with the channel dimension padded to Cp, and
  * transposed [C][T][Np] with the row dimension padded to Np (pad entries are written as zero by the first; the second
  * leaves columns >= N untouched: pre-zero the buffer once). */

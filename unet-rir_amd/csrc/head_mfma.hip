@@ -153,6 +153,11 @@ int launch_head_fwd_mfma(const void* x, int ldx, int B, int H, int W, int C, con
 // 160-byte pixel stride so ds_read_b64_tr_b16 is conflict-free) meets the six dy rows y = iy - kh + 2, kept as shifted
 // copies D' in a 6-slot LDS ring (528-byte (n,kw) stride: conflict-free ds_read_b64).  K order inside a 32-pixel step:
 // k = 8*lq + j  <->  pixel 4*lq + j (j < 4) or 16 + 4*lq + j - 4, the same on both operands.
+// The same kernel serves the stem's composite gradient (stem_composite.hip): there x is the 64-channel gradient G, dy the
+// 2-channel network input, and the window is 5 rows high - NKH = 5 drops the sixth vertical tap and the input row it needs.
+// ONES makes the unused (n,kw) row 12 a row of ones: at the vertical tap that pairs an x row with the dy row of the same
+// index (kh = 2) it yields the plain pixel sum of x per channel, each image row once, written behind the 72 gradient rows
+// (x is zero-filled outside the image, so the ones need no mask).  pstride = floats of one workgroup's partials.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_h;
 
@@ -160,9 +165,10 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_h;
 #define HW_DL 264             // D' (n,kw) stride, elements (528 B)
 #define HW_ROWS 16            // dy rows per workgroup step: 2 workgroups per CU x 256 CUs = 512 blocks for 32 x 256 rows
 
+template <int NKH, bool ONES>
 __global__ __launch_bounds__(256, 2) void head_wgrad_mfma_kernel(const __bf16* __restrict__ x, int ldx, int B, int H, int W, int C,
                                                                  const __bf16* __restrict__ dy, int lddy,
-                                                                 float* __restrict__ part) {
+                                                                 float* __restrict__ part, size_t pstride) {
     // 78.2 KB of LDS: two workgroups per CU hide each other's row loads (one x row buffer; (n,kw) rows 12..15 are zero
     // fragments made in registers)
     __shared__ __attribute__((aligned(16))) __bf16 Xs[256 * HW_XL];         // 40960 B
@@ -176,9 +182,9 @@ __global__ __launch_bounds__(256, 2) void head_wgrad_mfma_kernel(const __bf16* _
     for (int i = tid; i < 6 * 12 * HW_DL; i += 256) (&Dp[0][0])[i] = (__bf16)0.f;   // the pads stay zero
     for (int i = tid; i < 2 * 272; i += 256) (&dyrow[0][0])[i] = (__bf16)0.f;
 
-    f32x4 acc[6];
+    f32x4 acc[NKH];
 #pragma unroll
-    for (int kh = 0; kh < 6; ++kh) acc[kh] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kh = 0; kh < NKH; ++kh) acc[kh] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int g8 = tid & 7, qsub = tid >> 3;          // x staging: 16-byte granule g8 of pixel qsub + 32*j
     uint4 rx[8];
@@ -217,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void head_wgrad_mfma_kernel(const __bf16* _
         };
         load_x(y0 - 2);
         bf16x2 dnext = load_dy(0), dhalo = load_dy_halo(0);
-        const int nsteps = nrows + 5;
+        const int nsteps = nrows + NKH - 1;
         for (int i = 0; i < nsteps; ++i) {
             const int iy = y0 - 2 + i;
             __syncthreads();                          // the previous step's MFMAs are done with the x row and with the ring
@@ -241,9 +247,9 @@ __global__ __launch_bounds__(256, 2) void head_wgrad_mfma_kernel(const __bf16* _
             __syncthreads();
             if ((unsigned)iy < (unsigned)H) {
                 // ring slot of each vertical tap's dy row (wave-uniform), -1 where that row is outside the block
-                int doff[6];
+                int doff[NKH];
 #pragma unroll
-                for (int kh = 0; kh < 6; ++kh) {
+                for (int kh = 0; kh < NKH; ++kh) {
                     const int orow = i - kh;
                     doff[kh] = (orow < 0 || orow >= nrows) ? -1 : ((y0 + orow) % 6) * (12 * HW_DL);
                 }
@@ -258,14 +264,15 @@ __global__ __launch_bounds__(256, 2) void head_wgrad_mfma_kernel(const __bf16* _
                     const bf16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_h*)(xr + 16 * HW_XL));
                     const bf16x8 fb = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
-                    for (int kh = 0; kh < 6; ++kh) {
+                    for (int kh = 0; kh < NKH; ++kh) {
                         if (doff[kh] < 0) continue;
                         const __bf16* dr = dr0 + doff[kh] + ks * 32;
                         bf16x4 alo = *reinterpret_cast<const bf16x4*>(dr);
                         bf16x4 ahi = *reinterpret_cast<const bf16x4*>(dr + 16);
-                        if (l15 >= 12) {                  // (n,kw) rows 12..15 do not exist: zero fragments
+                        if (l15 >= 12) {                  // (n,kw) rows 12..15 do not exist: zero fragments (ONES: row 12 is all ones)
+                            const __bf16 fill = (__bf16)((ONES && l15 == 12) ? 1.f : 0.f);
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) { alo[e] = (__bf16)0.f; ahi[e] = (__bf16)0.f; }
+                            for (int e = 0; e < 4; ++e) { alo[e] = fill; ahi[e] = fill; }
                         }
                         const bf16x8 fa = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7);
                         acc[kh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc[kh], 0, 0, 0);
@@ -276,10 +283,10 @@ __global__ __launch_bounds__(256, 2) void head_wgrad_mfma_kernel(const __bf16* _
         __syncthreads();
     }
     // acc[kh][j] = dW[(n,kw) = 4*lq + j][kh][channel c0 + wave*16 + l15]
-    float* out = part + (size_t)blockIdx.x * 2 * 36 * C;
+    float* out = part + (size_t)blockIdx.x * pstride;
     const int c = c0 + wave * 16 + l15;
 #pragma unroll
-    for (int kh = 0; kh < 6; ++kh)
+    for (int kh = 0; kh < NKH; ++kh)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int idx = 4 * lq + j;
@@ -288,6 +295,7 @@ __global__ __launch_bounds__(256, 2) void head_wgrad_mfma_kernel(const __bf16* _
                 out[(size_t)(n * 36 + kh * 6 + kw) * C + c] = acc[kh][j];
             }
         }
+    if (ONES && lq == 3 && c < C) out[(size_t)72 * C + c] = acc[2][0];      // row 12 = 4 * 3 + 0: the pixel sum of x
 }
 
 int launch_head_wgrad_mfma(const void* x, int ldx, int B, int H, int W, int C, const void* dy, int lddy, float* part, int max_blocks,
@@ -295,8 +303,20 @@ int launch_head_wgrad_mfma(const void* x, int ldx, int B, int H, int W, int C, c
     int nblk = B * ((H + HW_ROWS - 1) / HW_ROWS) * ((W + 255) / 256);
     if (nblk > max_blocks) nblk = max_blocks;
     *nblk_out = nblk;
-    hipLaunchKernelGGL(head_wgrad_mfma_kernel, dim3(nblk, (C + 63) / 64), dim3(256), 0, s, (const __bf16*)x, ldx, B, H, W, C,
-                       (const __bf16*)dy, lddy, part);
+    hipLaunchKernelGGL((head_wgrad_mfma_kernel<6, false>), dim3(nblk, (C + 63) / 64), dim3(256), 0, s, (const __bf16*)x, ldx, B, H, W, C,
+                       (const __bf16*)dy, lddy, part, (size_t)2 * 36 * C);
+    return (int)hipGetLastError();
+}
+
+// The 5 x 5 correlation of the stem's composite gradient: part[blk][73][64] = rows (n, kh, kw) of the 6 x 6 table (kh < 5 written;
+// kw = 5 written and unused) and the pixel sums of x in row 72.  C = 64.
+int launch_stem_corr_mfma(const void* x, int ldx, int B, int H, int W, const void* dy, int lddy, float* part, int max_blocks,
+                          int* nblk_out, hipStream_t s) {
+    int nblk = B * ((H + HW_ROWS - 1) / HW_ROWS) * ((W + 255) / 256);
+    if (nblk > max_blocks) nblk = max_blocks;
+    *nblk_out = nblk;
+    hipLaunchKernelGGL((head_wgrad_mfma_kernel<5, true>), dim3(nblk, 1), dim3(256), 0, s, (const __bf16*)x, ldx, B, H, W, 64,
+                       (const __bf16*)dy, lddy, part, (size_t)73 * 64);
     return (int)hipGetLastError();
 }
 

@@ -160,6 +160,13 @@ bool head_mfma_applies(int W, int C);
 int launch_head_fwd_mfma(const void* x, int ldx, int B, int H, int W, int C, const float* w, const float* bias, float* y, int ldy, hipStream_t s);
 int launch_head_wgrad_mfma(const void* x, int ldx, int B, int H, int W, int C, const void* dy, int lddy, float* part, int max_blocks,
                            int* nblk_out, hipStream_t s);
+// the stem's gradients through the next 3x3 layer (stem_composite.hip); its 5 x 5 correlation is head_wgrad_mfma_kernel<5, true>
+int launch_stem_corr_mfma(const void* x, int ldx, int B, int H, int W, const void* dy, int lddy, float* part, int max_blocks,
+                          int* nblk_out, hipStream_t s);
+bool stem_composite_applies(int B, int H, int W, int C0, int C1);
+size_t stem_composite_ws_bytes(int B);
+int launch_stem_composite(const void* g, int ldg, const void* x, int ldx, int B, int H, int W, const void* w1t, float reg, const float* w0,
+                          float* dw0, int ldw, float* db0, void* ws, hipStream_t s);
 bool head_dgrad_mfma_applies(int W, int C);
 int launch_head_dgrad_mfma(const void* dy, int lddy, int B, int H, int W, const float* w, int C, void* dx, int lddx, hipStream_t s);
 bool upconv3x3g_applies(const Conv3Args& a);

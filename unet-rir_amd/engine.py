@@ -110,6 +110,13 @@ class UNetEngine(EngineBase):
         if share is not None and (share.H, share.W, share.F0, share.k, share.depth, share.batchnorm, share.dtype, share.inf_vector_shape,
                                   share.s0) != (H, W, F0, k, depth, batchnorm, dtype, self.inf_vector_shape, s0):
             raise ValueError("share= needs an engine of the same configuration (only the batch size may differ)")
+        # stem_composite: the stem's kernel and bias gradients come from g_y[1], the input and the enc1.cb1 kernel in one op
+        # (csrc/stem_composite.hip) instead of the full-resolution enc1.cb1 data gradient (155 GFLOP, 268 MB written at configs[1])
+        # and a weight gradient that reads it back; g_down[1] is then never allocated.  bf16 storage, s0 = 1, 3x3 stem of 64 filters,
+        # on a HIP device (the op has no other form); otherwise, or with the attribute set to False, the two-kernel path runs.
+        self.stem_composite_supported = bool(dtype == "bf16" and s0 == 1 and k == 3 and self.device.type == "cuda" and
+                                             ops.stem_composite_supported(B, H, W, self.ch[0], self.ch[0]))
+        self.stem_composite = self.stem_composite_supported
         self._build_params(share)
         self._alloc()
         self.ws = ops.Workspace(self.device)
@@ -123,8 +130,10 @@ class UNetEngine(EngineBase):
         # and run together (ops.ReduceBatch); the 37.7 MB slab sets of configs[1] reduce at once, while they are still in the
         # Infinity Cache (parking them measured 0.06-0.09 ms per step slower)
         self._init_side_stream(share, overlap_wgrad, 96 << 20, park_max_bytes=16 << 20)
+        if self.stem_composite_supported:
+            self.ws.reserve(ops.stem_composite_ws_bytes(self.B))
         self.head_direct = ops.head6x6_supported(self.ch[0])
-        if s0 == 2:      # the folded head: its own kernels in both storage types, reading the folded work copy of head.kernel
+        if s0 == 2:     # the folded head: its own kernels in both storage types, reading the folded work copy of head.kernel
             if ops.head_up2_supported(self.ch[0], self.dtype) != (ops.UP2_FWD | ops.UP2_DGRAD | ops.UP2_WGRAD):
                 raise ValueError("the head behind resize_factor_0=[2,2] needs number_filters_0 % 8 == 0")
             self._fold_copy("head.kernel", self.ch[0], share)
@@ -215,7 +224,8 @@ class UNetEngine(EngineBase):
             h, w = hw[l - 1]
             c = ch[l - 1]
             self.down[l], self.y[l] = A(h, w, c), A(h, w, c)
-            self.g_down[l], self.g_y[l] = A(h, w, c), A(h, w, c)
+            # g_down[1] has no reader under stem_composite: allocated on first use (_g_down1)
+            self.g_down[l], self.g_y[l] = (None if l == 1 and self.stem_composite else A(h, w, c)), A(h, w, c)
             if l <= D:
                 self.cat[l], self.g_cat[l] = A(h, w, 2 * c), A(h, w, 2 * c)
                 self.a[l] = self.cat[l].slice(0, c)
@@ -350,6 +360,12 @@ class UNetEngine(EngineBase):
         ops.conv2d_dgrad_colstat(self.geo[name], dy, self.wb(name + ".kernel"), dx, buf)
         ops.colsum_colstat(buf, rows, dx.C, c0, c_n, bias_grad)
         return True
+
+    def _g_down1(self):
+        """dL/d(enc1.down output), for the path without stem_composite (an engine built with it on holds none until then)."""
+        if self.g_down[1] is None:
+            self.g_down[1] = ops.new_act(self.B, *self.hw[0], self.ch[0], self.device, dtype=self.adt)
+        return self.g_down[1]
 
     def _bn_relu_bwd(self, name, da: Act, y: Act, dy: Act):
         if self.batchnorm:
@@ -537,18 +553,30 @@ class UNetEngine(EngineBase):
             if not self.batchnorm:
                 with self._wg() as ws_:
                     ops.colsum(self.g_y[l], g[f"enc{l}.cb1.bias"], ws_)
-            down_bias_done = self._dgrad_colsum(f"enc{l}.cb1", self.g_y[l], self.g_down[l], g[f"enc{l}.down.bias"], 0, self.g_down[l].C)
+            if l == 1 and self.stem_composite:
+                # enc1.down and enc1.cb1 are linear with nothing between them and the stem has no data gradient: both stem
+                # gradients straight from g_y[1], the input and the bf16 enc1.cb1 kernel the data gradient would have read
+                if not self.stem_composite_supported:
+                    raise RuntimeError("stem_composite is not available for this engine configuration")
+                # on the MAIN stream, which has nothing else left, beside the enc1.cb1 weight gradient on the side stream (behind it on
+                # the side stream: 0.07 ms per step slower, scripts/ab_switch.py); the hand-over below waits for both streams
+                ops.stem_composite(self.g_y[1], self.x4, self.wb("enc1.cb1.kernel"), g["enc1.down.kernel"], g["enc1.down.bias"],
+                                   self.ws, reg=reg, w0=p["enc1.down.kernel"])
+                ready("enc1.down.bias")
+                break
+            g_dn = self.g_down[l] if l > 1 else self._g_down1()
+            down_bias_done = self._dgrad_colsum(f"enc{l}.cb1", self.g_y[l], g_dn, g[f"enc{l}.down.bias"], 0, g_dn.C)
             x_in = self.a[l - 1] if l > 1 else self.x4
             with self._wg() as ws_:
-                ops.conv2d_wgrad(self.geo[f"enc{l}.down"], x_in, self.g_down[l], g[f"enc{l}.down.kernel"], ws_, reg=reg,
+                ops.conv2d_wgrad(self.geo[f"enc{l}.down"], x_in, g_dn, g[f"enc{l}.down.kernel"], ws_, reg=reg,
                                  w=p[f"enc{l}.down.kernel"], defer=self._rb if self.park_reduces else None)
             if not down_bias_done:
                 with self._wg() as ws_:
-                    ops.colsum(self.g_down[l], g[f"enc{l}.down.bias"], ws_)
+                    ops.colsum(g_dn, g[f"enc{l}.down.bias"], ws_)
             ready(f"enc{l}.down.bias")
             if l > 1:
                 skip = self.g_cat[l - 1].slice(0, self.ch[l - 2])
-                ops.conv2d_dgrad(self.geo[f"enc{l}.down"], self.g_down[l], self.wb(f"enc{l}.down.kernel"), skip, addend=skip)
+                ops.conv2d_dgrad(self.geo[f"enc{l}.down"], g_dn, self.wb(f"enc{l}.down.kernel"), skip, addend=skip)
                 g_a = skip
         self._end_backward()
 

@@ -511,6 +511,24 @@ def head6x6_wgrad(x: Act, dy: Act, dw, ws: Workspace):
                                                _stream()), "head6x6_wgrad")
 
 
+def stem_composite_supported(B, H, W, C0, C1):
+    """Whether stem_composite serves a stem of C0 filters in front of a 3x3 layer of C1 filters at this size (bf16 storage)."""
+    return bool(_lib.lib().unetrir_stem_composite_supported(int(B), int(H), int(W), int(C0), int(C1)))
+
+
+def stem_composite_ws_bytes(B):
+    return int(_lib.lib().unetrir_stem_composite_ws_bytes(int(B)))
+
+
+def stem_composite(g: Act, x: Act, w1t, dw0, db0, ws: Workspace, reg=0.0, w0=None):
+    """Kernel and bias gradients of the stem Conv2D(64, 3x3) from g = dL/d(output of the 3x3 layer behind it), the network input x
+    and that layer's transposed bf16 kernel copy w1t - the data gradient between the two layers is never formed.  dw0 is the
+    stem's [64][3][3][pad] gradient tensor (+ reg * w0), db0 its [64] bias gradient."""
+    ws.reserve(stem_composite_ws_bytes(g.B))
+    check(_lib.lib().unetrir_stem_composite_bf16(_p(g), g.ld, _p(x), x.ld, g.B, g.H, g.W, _p(w1t), reg, _p(w0) if reg else None, _p(dw0),
+                                                 int(dw0.shape[-1]), _p(db0), ws.ptr, ws.nbytes, _stream()), "stem_composite")
+
+
 H1_FWD, H1_BWD = 1, 2       # passes in the mask head1x1_supported returns
 
 
