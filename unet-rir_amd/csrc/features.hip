@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "kernels.h"
+#include "stft_common.h"
 
 namespace {
 
@@ -26,13 +27,6 @@ constexpr double FEAT_EP = 1e-5;                // 10^(-md/20)    (preprocess.py
 constexpr double FEAT_REF = 128.0;              // amp / 128      (preprocess.py:27)
 constexpr double FEAT_PI = 3.14159265358979323846;
 constexpr double FEAT_TINY32 = 1.1754943508222875e-38;   // numpy.finfo(float32).tiny: librosa's envelope threshold
-
-// periodic Hann of win samples centred in n_fft zeros, tap n
-__device__ __forceinline__ double hann_tap(int n, int n_fft, int win) {
-    const int m = n - (n_fft - win) / 2;
-    if (m < 0 || m >= win) return 0.0;
-    return 0.5 - 0.5 * cospi(2.0 * (double)m / (double)win);
-}
 
 __global__ __launch_bounds__(256) void stft_feature_kernel(const float* __restrict__ wav, int T, int n_fft, int win, int hop,
                                                            int pad_mode, int remove_mean, int normalize, int n_frames,
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(256) void stft_feature_kernel(const float* __restri
         if (i < 0) v = pad_mode == 0 ? (double)x[-i] - mean : 0.0;                  // numpy 'reflect' (edge not repeated)
         else if (i >= T) v = pad_mode == 0 ? (double)x[2 * (T - 1) - i] - mean : 0.0;
         else v = (double)x[i] - mean;
-        xw[n] = v * hann_tap(n, n_fft, win);
+        xw[n] = v * stft_hann<double>(n, n_fft, win);
     }
     __syncthreads();
     const int nb = n_fft / 2 + 1, n_lo = (n_fft - win) / 2, n_hi = n_lo + win, mask = n_fft - 1;
@@ -106,11 +100,7 @@ __global__ __launch_bounds__(256) void istft_feature_kernel(const float* __restr
     const float* __restrict__ f_amp = feat + ((size_t)b * 2 + 0) * H * W;
     const float* __restrict__ f_ph = feat + ((size_t)b * 2 + 1) * H * W;
     const int nb = n_fft / 2 + 1, n_lo = (n_fft - win) / 2, n_hi = n_lo + win, mask = n_fft - 1;
-    for (int n = tid; n < n_fft; n += 256) {
-        double sn, cs;
-        sincospi(2.0 * (double)n / (double)n_fft, &sn, &cs);
-        tw_c[n] = cs; tw_s[n] = sn;
-    }
+    stft_tables(tw_c, tw_s, nullptr, n_fft, win, 256);
     // frames whose non-zero window taps reach [p0, p0 + ISEG) in padded coordinates: n = p - hop f in [n_lo, n_hi)
     const int p0 = t0 + n_fft / 2, p = p0 + s;
     int f_lo = (p0 - n_hi + 1 + hop - 1) / hop;          // ceil; the numerator may be negative only when f_lo clamps to 0 anyway
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(256) void istft_feature_kernel(const float* __restr
         const int n = p - hop * f;
         if (n < n_lo || n >= n_hi) continue;             // zero window tap (the barriers above are reached by every thread
                                                          // before this point in each iteration)
-        const double w = hann_tap(n, n_fft, win);
+        const double w = stft_hann<double>(n, n_fft, win);
         // irfft sample n: (1/N) [X0 + (-1)^n X_{N/2} + 2 sum_{0<k<N/2} (Re X_k cos(2 pi k n / N) - Im X_k sin(2 pi k n / N))];
         // the imaginary parts of bins 0 and N/2 are ignored, as numpy.fft.irfft does
         double part = 0.0;

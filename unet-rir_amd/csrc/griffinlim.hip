@@ -34,6 +34,7 @@
 #include <stdlib.h>
 #include "kernels.h"
 #include "griffinlim_common.h"
+#include "stft_common.h"
 
 namespace {
 
@@ -49,13 +50,6 @@ __global__ void uniform_kernel(float* __restrict__ out, long long n, unsigned lo
     const unsigned long long key = gl_uniform_key(seed, step);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         out[i] = gl_uniform_at(key, i);
-}
-
-// periodic Hann of win samples centred in n_fft zeros, tap n (features.hip)
-__device__ __forceinline__ double gl_hann_tap(int n, int n_fft, int win) {
-    const int m = n - (n_fft - win) / 2;
-    if (m < 0 || m >= win) return 0.0;
-    return 0.5 - 0.5 * cospi(2.0 * (double)m / (double)win);
 }
 
 struct GlGeom {
@@ -86,16 +80,6 @@ __global__ __launch_bounds__(256) void gl_init_kernel(const float* __restrict__ 
     }
 }
 
-// twiddles of one turn and the padded window, shared by the transforms
-__device__ __forceinline__ void gl_tables(double* tw_c, double* tw_s, double* wtab, int n_fft, int win) {
-    for (int n = threadIdx.x; n < n_fft; n += blockDim.x) {
-        double sn, cs;
-        sincospi(2.0 * (double)n / (double)n_fft, &sn, &cs);
-        tw_c[n] = cs; tw_s[n] = sn;
-        if (wtab) wtab[n] = gl_hann_tap(n, n_fft, win);
-    }
-}
-
 // Synthesis: frames[b][f][n - n_lo] = w[n] / N * sum_k c_k (Re X[f][k] cos(2 pi k n / N) - Im X[f][k] sin(2 pi k n / N)) for the
 // non-zero window taps n in [n_lo, n_lo + win); c_k = 1 for k = 0 and N/2, else 2 - numpy.fft.irfft, which ignores the imaginary
 // parts of those two bins (their sines are exact zeros in the table).  A = X (16 frames x K bins, re and im), B = the twiddles.
@@ -108,7 +92,7 @@ __global__ __launch_bounds__(GL_T) void gl_synth_kernel(const double* __restrict
     const int b = blockIdx.y, f0 = blockIdx.x * GL_TM;
     const int n_lo = (g.n_fft - g.win) / 2, n_hi = n_lo + g.win, mask = g.n_fft - 1;
     const int n = n_lo + (blockIdx.z * 4 + wave) * 16 + row;          // this lane's column: a window tap (may be >= n_hi: not stored)
-    gl_tables(tw_c, tw_s, nullptr, g.n_fft, g.win);
+    stft_tables(tw_c, tw_s, nullptr, g.n_fft, g.win, blockDim.x);
     gl_d4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int kc = 0; kc < g.n_bins; kc += GL_KC) {
         __syncthreads();                                             // the previous chunk is no longer read (first pass: tables)
@@ -134,7 +118,7 @@ __global__ __launch_bounds__(GL_T) void gl_synth_kernel(const double* __restrict
         }
     }
     if (n < n_hi) {
-        const double w = gl_hann_tap(n, g.n_fft, g.win) / (double)g.n_fft;
+        const double w = stft_hann<double>(n, g.n_fft, g.win) / (double)g.n_fft;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                                // f64 C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
             const int f = f0 + kq + 4 * r;
@@ -145,12 +129,10 @@ __global__ __launch_bounds__(GL_T) void gl_synth_kernel(const double* __restrict
 
 // librosa.istft's sample at padded coordinate q (= output index + n_fft/2) from the windowed frames: sum over the frames whose
 // non-zero taps reach q, in frame order, divided by the squared-window envelope where that exceeds tiny32.
-__device__ __forceinline__ double gl_ola_sample(const double* __restrict__ fr_b, const double* wtab, int q, int n_lo, int n_hi, int win,
-                                                int hop, int n_frames) {
-    const int num = q - n_hi + 1;
-    const int g_lo = num <= 0 ? 0 : (num + hop - 1) / hop;
-    int g_hi = (q - n_lo) / hop;
-    if (g_hi > n_frames - 1) g_hi = n_frames - 1;
+__device__ __forceinline__ double gl_ola_sample(const double* __restrict__ fr_b, const double* wtab, int q, int n_lo, int win, int hop,
+                                                int n_frames) {
+    int g_lo, g_hi;
+    stft_frame_range<false>(q, n_lo, win, hop, n_frames, g_lo, g_hi);
     double acc = 0.0, wss = 0.0;
     for (int gi = g_lo; gi <= g_hi; ++gi) {
         const int m = q - hop * gi;                                  // tap of frame gi, in [n_lo, n_hi)
@@ -178,7 +160,7 @@ __global__ __launch_bounds__(GL_T) void gl_analysis_kernel(const double* __restr
     const int k = (blockIdx.z * 4 + wave) * 16 + row;                // this lane's column: a bin (may be >= n_bins: not stored)
     const double* __restrict__ fr_b = frames + (size_t)b * g.n_frames * g.win;
     const long long period = 2LL * (g.T_out - 1);
-    gl_tables(tw_c, tw_s, wtab, g.n_fft, g.win);
+    stft_tables(tw_c, tw_s, wtab, g.n_fft, g.win, blockDim.x);
     gl_d4 acc_re = {0.0, 0.0, 0.0, 0.0}, acc_im = {0.0, 0.0, 0.0, 0.0};
     for (int tc = 0; tc < g.win; tc += GL_KC) {
         __syncthreads();                                             // the previous chunk is no longer read (first pass: tables)
@@ -197,7 +179,7 @@ __global__ __launch_bounds__(GL_T) void gl_analysis_kernel(const double* __restr
                     }
                     inside = true;
                 }
-                if (inside) v = wtab[n] * gl_ola_sample(fr_b, wtab, (int)i + half, n_lo, n_hi, g.win, g.hop, g.n_frames);
+                if (inside) v = wtab[n] * gl_ola_sample(fr_b, wtab, (int)i + half, n_lo, g.win, g.hop, g.n_frames);
             }
             xw[r * GL_LD + j] = v;
         }
@@ -234,13 +216,12 @@ __global__ __launch_bounds__(GL_T) void gl_analysis_kernel(const double* __restr
 // the last overlap-add: wav[b][t] = (float) istft sample t
 __global__ __launch_bounds__(256) void gl_ola_kernel(const double* __restrict__ frames, GlGeom g, float* __restrict__ wav) {
     __shared__ double wtab[GL_MAX_NFFT];
-    for (int n = threadIdx.x; n < g.n_fft; n += blockDim.x) wtab[n] = gl_hann_tap(n, g.n_fft, g.win);
+    for (int n = threadIdx.x; n < g.n_fft; n += blockDim.x) wtab[n] = stft_hann<double>(n, g.n_fft, g.win);
     __syncthreads();
     const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= g.T_out) return;
     const int n_lo = (g.n_fft - g.win) / 2;
-    const double y = gl_ola_sample(frames + (size_t)b * g.n_frames * g.win, wtab, t + g.n_fft / 2, n_lo, n_lo + g.win, g.win, g.hop,
-                                   g.n_frames);
+    const double y = gl_ola_sample(frames + (size_t)b * g.n_frames * g.win, wtab, t + g.n_fft / 2, n_lo, g.win, g.hop, g.n_frames);
     wav[(size_t)b * g.T_out + t] = (float)y;
 }
 

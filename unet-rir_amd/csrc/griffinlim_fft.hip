@@ -38,6 +38,7 @@
 #include <math.h>
 #include "kernels.h"
 #include "griffinlim_common.h"
+#include "stft_common.h"
 #include "fft_lds.h"
 
 namespace {
@@ -64,12 +65,6 @@ struct GfWs {
     cf* plane[3];
     float* S;
 };
-
-__device__ __forceinline__ float gf_hann_tap(int n, int n_fft, int win) {
-    const int m = n - (n_fft - win) / 2;
-    if (m < 0 || m >= win) return 0.f;
-    return (float)(0.5 - 0.5 * cospi(2.0 * (double)m / (double)win));
-}
 
 __global__ __launch_bounds__(256) void gf_init_kernel(const float* __restrict__ feat, GfGeom g, int denormalize,
                                                       const float* __restrict__ init_phase, unsigned long long seed, unsigned long long draw,
@@ -119,12 +114,11 @@ __device__ __forceinline__ void gf_segment(cf* img, float* seg, const float* wta
 #pragma clang fp contract(off)
     constexpr int TG = M / 8, IMG = GF_IMG / M;
     const int tid = threadIdx.x, grp = tid / TG, t = tid % TG;
-    const int n_hi = g.n_lo + g.win, hop = g.hop;
-    // the frames whose non-zero taps reach the padded positions [s_lo + M, s_hi + M)
-    const int num = s_lo + M - n_hi + 1;
-    const int g_lo = num <= 0 ? 0 : (num + hop - 1) / hop;
-    int g_hi = (s_hi - 1 + M - g.n_lo) / hop;
-    if (g_hi > g.n_frames - 1) g_hi = g.n_frames - 1;
+    const int hop = g.hop;
+    // the frames whose non-zero taps reach the padded positions [s_lo + M, s_hi + M): from the first of its first to the last of its last
+    int g_lo, g_hi, other;
+    stft_frame_range<false>(s_lo + M, g.n_lo, g.win, hop, g.n_frames, g_lo, other);
+    stft_frame_range<false>(s_hi - 1 + M, g.n_lo, g.win, hop, g.n_frames, other, g_hi);
     for (int s = s_lo + tid; s < s_hi; s += GF_T) seg[s - s_lo] = 0.f;
     cf* buf = img + grp * M;
     for (int p0 = g_lo; p0 <= g_hi; p0 += IMG) {
@@ -147,9 +141,9 @@ __device__ __forceinline__ void gf_segment(cf* img, float* seg, const float* wta
         fl_fft<M, 1>(buf, t);
         const int p1 = p0 + IMG - 1 < g_hi ? p0 + IMG - 1 : g_hi;
         for (int s = s_lo + tid; s < s_hi; s += GF_T) {
-            const int q = s + M, nm = q - n_hi + 1;
-            int a = nm <= 0 ? 0 : (nm + hop - 1) / hop;
-            int z = (q - g.n_lo) / hop;
+            const int q = s + M;
+            int a, z;
+            stft_frame_range<false>(q, g.n_lo, g.win, hop, g.n_frames, a, z);
             if (a < p0) a = p0;
             if (z > p1) z = p1;
             float acc = seg[s - s_lo];
@@ -164,10 +158,9 @@ __device__ __forceinline__ void gf_segment(cf* img, float* seg, const float* wta
     // a thread finishes the samples it has summed itself
     const float inv_n = 1.f / (float)(2 * M);
     for (int s = s_lo + tid; s < s_hi; s += GF_T) {
-        const int q = s + M, nm = q - n_hi + 1;
-        const int a = nm <= 0 ? 0 : (nm + hop - 1) / hop;
-        int z = (q - g.n_lo) / hop;
-        if (z > g.n_frames - 1) z = g.n_frames - 1;
+        const int q = s + M;
+        int a, z;
+        stft_frame_range<false>(q, g.n_lo, g.win, hop, g.n_frames, a, z);
         float wss = 0.f;
         for (int gi = a; gi <= z; ++gi) {
             const float w = wtab[q - hop * gi];
@@ -189,7 +182,7 @@ __device__ __forceinline__ void gf_iterate(cf* img, float* seg, float* wtab, con
     const int n_hi = g.n_lo + g.win, T = g.T_out;
     const int f0 = tile * g.own;
     const int nown = g.n_frames - f0 < g.own ? g.n_frames - f0 : g.own;
-    for (int n = tid; n < 2 * M; n += GF_T) wtab[n] = gf_hann_tap(n, 2 * M, g.win);
+    for (int n = tid; n < 2 * M; n += GF_T) wtab[n] = stft_hann<float>(n, 2 * M, g.win);
     // the samples the taps of frames f0 ... f0 + nown - 1 reach: lo <= s < hi before the padding, then what the reflection maps to
     const int lo = g.hop * f0 + g.n_lo - M, hi = g.hop * (f0 + nown - 1) + n_hi - M;
     int s_lo = lo < 0 ? 0 : lo, s_hi = hi > T ? T : hi;
@@ -259,7 +252,7 @@ __device__ __forceinline__ void gf_final(cf* img, float* seg, float* wtab, const
                                          const cf* __restrict__ cur, const cf* __restrict__ prev, int mode, float alpha,
                                          float* __restrict__ wav) {
     const int tid = threadIdx.x;
-    for (int n = tid; n < 2 * M; n += GF_T) wtab[n] = gf_hann_tap(n, 2 * M, g.win);
+    for (int n = tid; n < 2 * M; n += GF_T) wtab[n] = stft_hann<float>(n, 2 * M, g.win);
     const long long lo = (long long)tile * g.chunk;
     const int s_lo = (int)lo, s_hi = lo + g.chunk > g.T_out ? g.T_out : s_lo + g.chunk;
     if (s_hi - s_lo > GF_SEG || s_hi <= s_lo) return;                // not reached

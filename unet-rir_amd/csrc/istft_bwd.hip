@@ -11,11 +11,12 @@
 // One launch, one workgroup per (column, sample), no workspace and no atomics: the loader recomputes env[t] for each of its samples
 // from the at most win / hop + 1 frames that reach it, in ascending frame order (the order of istft_feature_kernel's own envelope);
 // fp64 inside, one rounding per output, every sum in a fixed order - two runs give the same bits and a sample's bits depend neither
-// on B nor on its place in the batch.  The device functions are restated here rather than shared: waveloss.hip keeps its bits.
+// on B nor on its place in the batch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 #include "kernels.h"
+#include "stft_common.h"
 
 namespace {
 
@@ -27,12 +28,6 @@ constexpr double IB_REF = 128.0;
 constexpr double IB_PI = 3.14159265358979323846;
 constexpr double IB_TINY32 = 1.1754943508222875e-38;
 constexpr double IB_LN10 = 2.30258509299404568402;
-
-__device__ __forceinline__ double ib_hann(int n, int n_fft, int win) {
-    const int m = n - (n_fft - win) / 2;
-    if (m < 0 || m >= win) return 0.0;
-    return 0.5 - 0.5 * cospi(2.0 * (double)m / (double)win);
-}
 
 template <bool ACC>
 __global__ __launch_bounds__(256) void istft_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ phase_ref,
@@ -60,10 +55,10 @@ __global__ __launch_bounds__(256) void istft_bwd_kernel(const float* __restrict_
                 if (g_hi > n_frames - 1) g_hi = n_frames - 1;
                 double wss = 0.0;
                 for (int g = g_lo; g <= g_hi; ++g) {
-                    const double w = ib_hann(p - hop * g, n_fft, win);
+                    const double w = stft_hann<double>(p - hop * g, n_fft, win);
                     wss += w * w;
                 }
-                if (wss > IB_TINY32) v = ib_hann(n, n_fft, win) * ((double)db[i] / wss);
+                if (wss > IB_TINY32) v = stft_hann<double>(n, n_fft, win) * ((double)db[i] / wss);
             }
             sg[n] = v;
         }

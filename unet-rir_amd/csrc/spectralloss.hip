@@ -33,93 +33,51 @@
 //                         fixed order (every workgroup of a row forms the same bits).  The epilogue forms M_y^, M_y, the three partial
 //                         sums of the workgroup (a slab in the workspace) and, per bin, Re X^, Im X^ and the two factors of g that do
 //                         not need the row-wide sum:  a = 2 (M_y^ - M_y) / M_y^,  q = 2 (ln M_y^ - ln M_y) / (F K M_y^^2).
-//   2 sl_finalize_kernel  one workgroup: the slabs of each (b, r) in index order -> SC, LM and the two scalars that scale the gradient
-//                         (c sc_weight / sum M_y^2, c log_weight; zeros for a row that is not counted); Q_b over r in index order;
-//                         spectral_out = (sum_b mean_r SC, sum_b mean_r LM, rows counted); loss_out[0] += (float) L.
+//   2 sl_finalize_kernel  (spectralloss_common.h: the FFT form's too) one workgroup: the slabs of each (b, r) in index order -> SC, LM
+//                         and the two scalars that scale the gradient; Q_b over r in index order; spectral_out; loss_out[0] += (float) L.
 //   3 sl_synth_kernel     16 frames x 64 window taps per workgroup: the loader forms dRe, dIm from the four planes and the two scalars,
 //                         the GEMM against the same table gives frames[f][n] = w[n] sum_k (dRe cos - dIm sin) over the non-zero taps.
-//   4 sl_fold_kernel      gather: one thread owns one output sample; per resolution in index order the frames that reach t + N/2 and
-//                         the reflected positions, each in ascending frame order; one rounding to fp32 (or (float)((double) dwav + g)).
+//   4 sl_fold_kernel      (spectralloss_common.h: the FFT form's too) gather: one thread owns one output sample; per resolution in
+//                         index order the frames that reach t + N/2 and the reflected positions, each in ascending frame order; one
+//                         rounding to fp32 (or (float)((double) dwav + g)).
 // No atomics, every summation order fixed: two runs give the same bits, and a row's bits depend neither on B nor on its place in the
 // batch.  Nothing is allocated, cleared or waited for, so the call can be captured in a HIP graph.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 #include "kernels.h"
+#include "spectralloss_common.h"
 
 namespace {
 
-constexpr int SL_MAX_NFFT = 1024;
 constexpr int SL_MIN_NFFT = 16;
-constexpr int SL_MAX_T = 16384;
-constexpr int SL_MAX_R = 8;
 constexpr int SL_TM = 16;                     // frames per workgroup = rows of one MFMA tile
 constexpr int SL_TN = 64;                     // columns per workgroup: one 16-column tile per wave
 constexpr int SL_KC = 128;                    // reduction elements staged in LDS at a time
 constexpr int SL_LD = SL_KC + 4;              // LDS row stride in doubles (griffinlim.hip: 16 rows land 8 banks apart)
-constexpr int SL_T = 256;                     // 4 waves
 
 typedef double sl_d4 __attribute__((ext_vector_type(4)));
 
 struct SlRes {
     int N, win, hop, F, K, n_lo;
     int ftiles, ktiles, ttiles;               // frame tiles; groups of 64 of the N/2 bin columns; groups of 64 window taps
-    int atile0, stile0;                       // this resolution's first tile in the analysis / synthesis grid of a row
+    int tile0, stile0;                        // this resolution's first tile in the analysis / synthesis grid of a row
+    int ntiles;                               // its tiles in the analysis grid, ftiles ktiles: one slab each
     long long plane0, frame0;                 // offsets (doubles) of its four planes / its frames inside a row's share
 };
 
 struct SlPlan {
     int R, B, T;
-    int atiles, stiles;                       // tiles of one row: analysis, synthesis
+    int tiles, stiles;                        // tiles of one row: analysis, synthesis
     long long planes_row, frames_row;         // doubles per row
     SlRes res[SL_MAX_R];
 };
 
-// workspace, in doubles:  slabs [B][atiles][3] | terms [B][R][2] (SC, LM) | coef [B][R][2] | rows [B][3] | planes [B][planes_row] |
+// workspace, in doubles:  slabs [B][tiles][3] | terms [B][R][2] (SC, LM) | coef [B][R][2] | rows [B][3] | planes [B][planes_row] |
 //                         frames [B][frames_row]
 struct SlWs {
     double *slabs, *terms, *coef, *rows, *planes, *frames;
 };
-
-__device__ __forceinline__ double sl_hann_tap(int n, int n_fft, int win) {
-    const int m = n - (n_fft - win) / 2;
-    if (m < 0 || m >= win) return 0.0;
-    return 0.5 - 0.5 * cospi(2.0 * (double)m / (double)win);
-}
-
-__device__ __forceinline__ void sl_tables(double* tw_c, double* tw_s, double* wtab, int n_fft, int win) {
-    for (int n = threadIdx.x; n < n_fft; n += SL_T) {
-        double sn, cs;
-        sincospi(2.0 * (double)n / (double)n_fft, &sn, &cs);
-        tw_c[n] = cs; tw_s[n] = sn;
-        if (wtab) wtab[n] = sl_hann_tap(n, n_fft, win);
-    }
-}
-
-// three sums over the workgroup at once, every thread gets them: the lanes of a wave by a shuffle tree (a fixed pairing), the four
-// waves in index order
-__device__ __forceinline__ void sl_block_sum3(double (*red)[SL_T / 64], double& a, double& b, double& c) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); c += __shfl_down(c, off, 64);
-    }
-    __syncthreads();                                                 // red is no longer read
-    if (lane == 0) { red[0][wave] = a; red[1][wave] = b; red[2][wave] = c; }
-    __syncthreads();
-    a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-    b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    c = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
-}
-
-// the resolution a tile of a row's grid belongs to, and the tile's index inside it
-__device__ __forceinline__ int sl_find(const SlPlan& p, int tile, bool synth, int& local) {
-    int r = 0;
-    for (int i = 1; i < p.R; ++i)
-        if (tile >= (synth ? p.res[i].stile0 : p.res[i].atile0)) r = i;
-    local = tile - (synth ? p.res[r].stile0 : p.res[r].atile0);
-    return r;
-}
 
 __global__ __launch_bounds__(SL_T) void sl_analysis_kernel(const float* __restrict__ wav_pred, const float* __restrict__ wav_true, SlPlan p,
                                                            double delta, int backward, SlWs ws) {
@@ -127,17 +85,17 @@ __global__ __launch_bounds__(SL_T) void sl_analysis_kernel(const float* __restri
     __shared__ double red[3][SL_T / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row = lane & 15, kq = lane >> 4;
-    const int b = blockIdx.x / p.atiles, tile = blockIdx.x % p.atiles;
+    const int b = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
     int local;
-    const SlRes g = p.res[sl_find(p, tile, false, local)];
+    const SlRes g = p.res[sl_find(p, &SlRes::tile0, tile, local)];
     const int f0 = (local / g.ktiles) * SL_TM, k0 = (local % g.ktiles) * SL_TN + wave * 16;
     const int k = k0 + row;                                          // this lane's column: a bin below N/2 (may be past them: not counted)
     const int T = p.T, N = g.N, half = N / 2, n_hi = g.n_lo + g.win;
     const float* __restrict__ yp = wav_pred + (size_t)b * T;
     const float* __restrict__ yt = wav_true + (size_t)b * T;
-    double* __restrict__ slab = ws.slabs + ((size_t)b * p.atiles + tile) * 3;
+    double* __restrict__ slab = ws.slabs + ((size_t)b * p.tiles + tile) * 3;
 
-    sl_tables(tw_c, tw_s, wtab, N, g.win);
+    stft_tables(tw_c, tw_s, wtab, N, g.win, SL_T);
     // E0 and sum w^2: a thread's groups of four samples (taps: the ones it has just written) in index order, then the fixed pairing -
     // the same bits in every workgroup of the row, whatever the row's alignment (zeros past its end add exact zeros)
     double e0 = 0.0, w2 = 0.0, none = 0.0;
@@ -226,40 +184,6 @@ __global__ __launch_bounds__(SL_T) void sl_analysis_kernel(const float* __restri
     if (tid == 0) { slab[0] = s_d; slab[1] = s_y; slab[2] = s_l; }
 }
 
-__global__ __launch_bounds__(SL_T) void sl_finalize_kernel(SlPlan p, double sc_weight, double log_weight, double scale, SlWs ws,
-                                                           double* __restrict__ spectral_out, float* __restrict__ loss_out) {
-    __shared__ double red[3][SL_T / 64];
-    const int tid = threadIdx.x;
-    const double c = scale / (double)p.R;
-    for (long long pair = tid; pair < (long long)p.B * p.R; pair += SL_T) {
-        const int b = (int)(pair / p.R), r = (int)(pair % p.R);
-        const SlRes& g = p.res[r];
-        const double* s = ws.slabs + ((size_t)b * p.atiles + g.atile0) * 3;
-        double d = 0.0, y = 0.0, l = 0.0;
-        for (int i = 0; i < g.ftiles * g.ktiles; ++i) { d += s[3 * i]; y += s[3 * i + 1]; l += s[3 * i + 2]; }
-        const bool counted = y > 0.0;                                // M_y >= sqrt(delta P0) > 0 in a counted row
-        ws.terms[2 * pair] = counted ? d / y : 0.0;
-        ws.terms[2 * pair + 1] = counted ? l / ((double)g.F * (double)g.K) : 0.0;
-        ws.coef[2 * pair] = counted ? c * sc_weight / y : 0.0;
-        ws.coef[2 * pair + 1] = counted ? c * log_weight : 0.0;
-        if (r == 0) ws.rows[3 * (size_t)b + 2] = counted ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    double q_sc = 0.0, q_lm = 0.0, q_n = 0.0;
-    for (int b = tid; b < p.B; b += SL_T) {
-        double sc = 0.0, lm = 0.0;
-        for (int r = 0; r < p.R; ++r) { sc += ws.terms[2 * ((size_t)b * p.R + r)]; lm += ws.terms[2 * ((size_t)b * p.R + r) + 1]; }
-        sc /= (double)p.R; lm /= (double)p.R;
-        ws.rows[3 * (size_t)b] = sc; ws.rows[3 * (size_t)b + 1] = lm;
-        q_sc += sc; q_lm += lm; q_n += ws.rows[3 * (size_t)b + 2];
-    }
-    sl_block_sum3(red, q_sc, q_lm, q_n);
-    if (tid == 0) {
-        spectral_out[0] = q_sc; spectral_out[1] = q_lm; spectral_out[2] = q_n;
-        if (loss_out) loss_out[0] += (float)(scale * (sc_weight * q_sc + log_weight * q_lm));
-    }
-}
-
 // frames[b][f][n - n_lo] = w[n] sum_k (dRe[f,k] cos(2 pi k n / N) - dIm[f,k] sin(2 pi k n / N)) for the non-zero taps.  A = dRe, dIm
 // (16 frames x a chunk of bins), B = the twiddles; wave w owns taps n_lo + 16 (4 tap group + w) ... + 15.
 __global__ __launch_bounds__(SL_T) void sl_synth_kernel(SlPlan p, SlWs ws) {
@@ -269,7 +193,7 @@ __global__ __launch_bounds__(SL_T) void sl_synth_kernel(SlPlan p, SlWs ws) {
     const int b = blockIdx.x / p.stiles, tile = blockIdx.x % p.stiles;
     if (ws.rows[3 * (size_t)b + 2] == 0.0) return;                   // a row that is not counted: the fold writes its zeros
     int local;
-    const int r_of = sl_find(p, tile, true, local);
+    const int r_of = sl_find(p, &SlRes::stile0, tile, local);
     const SlRes g = p.res[r_of];
     const int f0 = (local / g.ttiles) * SL_TM, m0 = (local % g.ttiles) * SL_TN + wave * 16;
     const int N = g.N, n_hi = g.n_lo + g.win;
@@ -277,7 +201,7 @@ __global__ __launch_bounds__(SL_T) void sl_synth_kernel(SlPlan p, SlWs ws) {
     const double ca = ws.coef[2 * ((size_t)b * p.R + r_of)], cb = ws.coef[2 * ((size_t)b * p.R + r_of) + 1];
     const double* __restrict__ pl = ws.planes + (size_t)b * p.planes_row + g.plane0;
     const size_t P = (size_t)g.F * g.K;
-    sl_tables(tw_c, tw_s, nullptr, N, g.win);
+    stft_tables(tw_c, tw_s, nullptr, N, g.win, SL_T);
     const bool live = g.n_lo + m0 < n_hi;
     sl_d4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int kc = 0; kc < g.K; kc += SL_KC) {
@@ -309,7 +233,7 @@ __global__ __launch_bounds__(SL_T) void sl_synth_kernel(SlPlan p, SlWs ws) {
         }
     }
     if (n < n_hi) {
-        const double w = sl_hann_tap(n, N, g.win);
+        const double w = stft_hann<double>(n, N, g.win);
         double* __restrict__ fr = ws.frames + (size_t)b * p.frames_row + g.frame0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                                // f64 C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
@@ -317,37 +241,6 @@ __global__ __launch_bounds__(SL_T) void sl_synth_kernel(SlPlan p, SlWs ws) {
             if (f < g.F) fr[(size_t)f * g.win + (n - g.n_lo)] = w * acc[r];
         }
     }
-}
-
-// p[j]: the frames whose non-zero taps reach the padded position j, in ascending frame order
-__device__ __forceinline__ double sl_ola(const double* __restrict__ fr, const SlRes& g, int j) {
-    const int num = j - (g.n_lo + g.win) + 1;
-    const int f_lo = num <= 0 ? 0 : (num + g.hop - 1) / g.hop;
-    int f_hi = j < g.n_lo ? -1 : (j - g.n_lo) / g.hop;
-    if (f_hi > g.F - 1) f_hi = g.F - 1;
-    double acc = 0.0;
-    for (int f = f_lo; f <= f_hi; ++f) acc += fr[(size_t)f * g.win + (j - g.hop * f - g.n_lo)];
-    return acc;
-}
-
-__global__ __launch_bounds__(256) void sl_fold_kernel(SlPlan p, SlWs ws, int accumulate, float* __restrict__ dwav) {
-    const int chunks = (p.T + 255) / 256;
-    const int b = blockIdx.x / chunks, t = (blockIdx.x % chunks) * 256 + threadIdx.x;
-    if (t >= p.T) return;
-    const size_t o = (size_t)b * p.T + t;
-    double total = 0.0;
-    if (ws.rows[3 * (size_t)b + 2] != 0.0) {
-        for (int r = 0; r < p.R; ++r) {
-            const SlRes& g = p.res[r];
-            const double* __restrict__ fr = ws.frames + (size_t)b * p.frames_row + g.frame0;
-            const int half = g.N / 2;
-            double acc = sl_ola(fr, g, t + half);
-            if (t >= 1 && t <= half) acc += sl_ola(fr, g, half - t);
-            if (t <= p.T - 2 && t >= p.T - 1 - half) acc += sl_ola(fr, g, 2 * (p.T - 1) - t + half);
-            total += acc;
-        }
-    }
-    dwav[o] = accumulate ? (float)((double)dwav[o] + total) : (float)total;
 }
 
 bool sl_supported(int T, int N, int win, int hop) {
@@ -364,17 +257,16 @@ size_t sl_plan(int B, int T, int R, const int* res, SlPlan* out) {
         const int N = res[3 * r], win = res[3 * r + 1], hop = res[3 * r + 2];
         if (!sl_supported(T, N, win, hop)) return 0;
         SlRes& g = p.res[r];
-        g.N = N; g.win = win; g.hop = hop; g.F = 1 + T / hop; g.K = N / 2 + 1; g.n_lo = (N - win) / 2;
+        sl_res_fill(g, T, N, win, hop, frames);
         g.ftiles = (g.F + SL_TM - 1) / SL_TM; g.ktiles = (N / 2 + SL_TN - 1) / SL_TN; g.ttiles = (win + SL_TN - 1) / SL_TN;
-        g.atile0 = (int)at; g.stile0 = (int)st; g.plane0 = planes; g.frame0 = frames;
+        g.tile0 = (int)at; g.stile0 = (int)st; g.ntiles = g.ftiles * g.ktiles; g.plane0 = planes;
         at += (long long)g.ftiles * g.ktiles; st += (long long)g.ftiles * g.ttiles;
-        planes += 4LL * g.F * g.K; frames += (long long)g.F * win;
+        planes += 4LL * g.F * g.K;
     }
-    const long long chunks = (T + 255) / 256;
-    if (at * B > 0x7fffffffLL || st * B > 0x7fffffffLL || chunks * B > 0x7fffffffLL) return 0;      // the grids are one-dimensional
-    p.atiles = (int)at; p.stiles = (int)st; p.planes_row = planes; p.frames_row = frames;
+    if (at * B > 0x7fffffffLL || st * B > 0x7fffffffLL || sl_fold_blocks(B, T) > 0x7fffffffLL) return 0;      // the grids are one-dimensional
+    p.tiles = (int)at; p.stiles = (int)st; p.planes_row = planes; p.frames_row = frames;
     if (out) *out = p;
-    return (size_t)B * ((size_t)at * 3 + (size_t)R * 4 + 3 + (size_t)planes + (size_t)frames);
+    return sl_head_doubles(B, at, R) + (size_t)B * ((size_t)planes + (size_t)frames);
 }
 
 }  // namespace
@@ -390,29 +282,23 @@ size_t unetrir_spectral_loss_ws_bytes(int B, int T, int R, const int* res) { ret
 int unetrir_spectral_loss_f32(const float* wav_pred, const float* wav_true, int B, int T, int R, const int* res, double floor_db,
                               double sc_weight, double log_weight, double weight, double inv_global_batch, int accumulate, float* dwav,
                               double* spectral_out, float* loss_out, void* ws, size_t ws_bytes, unetrir_stream_t stream) {
-    if (!wav_pred || !wav_true || !spectral_out || !ws || !res || B <= 0 || R < 1 || R > SL_MAX_R) return UNETRIR_EINVAL;
-    if (!isfinite(floor_db) || !(floor_db > 0.0) || floor_db > 200.0 || !(sc_weight >= 0.0) || !isfinite(sc_weight) ||
-        !(log_weight >= 0.0) || !isfinite(log_weight) || !(weight >= 0.0) || !isfinite(weight) || !(inv_global_batch > 0.0) ||
-        !isfinite(inv_global_batch) || (accumulate && !dwav))
+    if (!sl_args_ok(wav_pred, wav_true, B, R, res, floor_db, sc_weight, log_weight, weight, inv_global_batch, accumulate, dwav,
+                    spectral_out, ws))
         return UNETRIR_EINVAL;
     SlPlan p;
     const size_t need = sl_plan(B, T, R, res, &p) * sizeof(double);
-    if (need == 0 || ws_bytes < need || ((uintptr_t)ws & 7)) return UNETRIR_EINVAL;
+    if (need == 0 || ws_bytes < need) return UNETRIR_EINVAL;
     SlWs w;
-    w.slabs = (double*)ws;
-    w.terms = w.slabs + (size_t)B * p.atiles * 3;
-    w.coef = w.terms + (size_t)B * R * 2;
-    w.rows = w.coef + (size_t)B * R * 2;
-    w.planes = w.rows + (size_t)B * 3;
+    w.planes = sl_head_carve(w, ws, B, p.tiles, R);
     w.frames = w.planes + (size_t)B * p.planes_row;
     const double delta = pow(10.0, -floor_db / 10.0), scale = weight * inv_global_batch;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sl_analysis_kernel, dim3((unsigned)(B * p.atiles)), dim3(SL_T), 0, s, wav_pred, wav_true, p, delta, (int)(dwav != nullptr),
+    hipLaunchKernelGGL(sl_analysis_kernel, dim3((unsigned)(B * p.tiles)), dim3(SL_T), 0, s, wav_pred, wav_true, p, delta, (int)(dwav != nullptr),
                        w);
     hipLaunchKernelGGL(sl_finalize_kernel, dim3(1), dim3(SL_T), 0, s, p, sc_weight, log_weight, scale, w, spectral_out, loss_out);
     if (dwav) {
         hipLaunchKernelGGL(sl_synth_kernel, dim3((unsigned)(B * p.stiles)), dim3(SL_T), 0, s, p, w);
-        hipLaunchKernelGGL(sl_fold_kernel, dim3((unsigned)(B * ((T + 255) / 256))), dim3(256), 0, s, p, w, accumulate, dwav);
+        hipLaunchKernelGGL(sl_fold_kernel, dim3((unsigned)sl_fold_blocks(B, T)), dim3(SL_T), 0, s, p, w, accumulate, dwav);
     }
     return (int)hipGetLastError();
 }

@@ -18,15 +18,13 @@
 //                          swizzled address; fl_fft<M, -1>, fl_split_fwd<M> (slot 0 holds bins 0 and N / 2, both real); the epilogue forms
 //                          M_y^, M_y and the three partial sums of the workgroup: one slab.  No spectrum is written to memory.  E0_b and
 //                          sum w^2 are recomputed per workgroup in a fixed order (every workgroup of a row forms the same bits).
-//   2 slf_finalize_kernel  one workgroup: the slabs of each (b, r) in index order -> SC, LM and the two scalars that scale the gradient;
-//                          Q_b over r in index order; spectral_out; loss_out[0] += (float) L.
+//   2 sl_finalize_kernel   the DFT form's (spectralloss_common.h), over these slabs.
 //   3 slf_adjoint_kernel   recomputes the analysis of its frames (cheaper than four planes of spectra in memory), forms G = g X^ with
 //                          the row scalars, halves the interior bins 0 < k < N / 2 (exact) - sum_{k=0}^{N/2} (dRe cos - dIm sin) is N
 //                          irfft of that, and the header's inverse returns the signal times 2 M = N, so nothing else scales - runs
 //                          fl_split_inv and fl_fft<M, +1> in the same image, multiplies by the window and writes the win non-zero taps
 //                          of each frame as fp32.
-//   4 slf_fold_kernel      gather: one thread owns one output sample; per resolution in index order the frames that reach t + N/2 and
-//                          the reflected positions, each in ascending frame order; one rounding to fp32 (or (float)((double) dwav + g)).
+//   4 sl_fold_kernel       the DFT form's gather (spectralloss_common.h) on fp32 frames, accumulated in fp64.
 // No atomics, every summation order fixed, complex products through fl_mul (contraction off): two runs give the same bits, and a row's
 // bits depend neither on B nor on its place in the batch.  Nothing is allocated, cleared or waited for, so the call can be captured
 // in a HIP graph.  A row with a silent target counts nothing and gets zeros.
@@ -34,22 +32,18 @@
 #include <stdint.h>
 #include <math.h>
 #include "kernels.h"
+#include "spectralloss_common.h"
 #include "fft_lds.h"
 
 namespace {
 
 using namespace fftlds;
 
-constexpr int SF_MAX_NFFT = 1024;
-constexpr int SF_MIN_NFFT = 128;
-constexpr int SF_MAX_T = 16384;
-constexpr int SF_MAX_R = 8;
-constexpr int SF_T = 256;                     // 4 waves
 constexpr int SF_IMG = 2048;                  // complex points of the workgroup's image: 16 KB
 
 struct SfRes {
     int N, win, hop, F, K, n_lo;
-    int ftiles;                               // workgroups of 2048 / N frames
+    int ntiles;                               // workgroups of 2048 / N frames
     int tile0;                                // this resolution's first workgroup in the grid of a row
     long long frame0;                         // offset (floats) of its frames inside a row's share
 };
@@ -58,7 +52,7 @@ struct SfPlan {
     int R, B, T;
     int tiles;                                // workgroups of one row
     long long frames_row;                     // floats per row
-    SfRes res[SF_MAX_R];
+    SfRes res[SL_MAX_R];
 };
 
 // workspace:  doubles  slabs [B][tiles][3] | terms [B][R][2] (SC, LM) | coef [B][R][2] | rows [B][3],  then floats  frames [B][frames_row]
@@ -67,55 +61,24 @@ struct SfWs {
     float* frames;
 };
 
-__device__ __forceinline__ float sf_hann_tap(int n, int n_fft, int win) {
-    const int m = n - (n_fft - win) / 2;
-    if (m < 0 || m >= win) return 0.f;
-    return (float)(0.5 - 0.5 * cospi(2.0 * (double)m / (double)win));
-}
-
-// three sums over the workgroup at once, every thread gets them: the lanes of a wave by a shuffle tree (a fixed pairing), the four
-// waves in index order
-__device__ __forceinline__ void sf_block_sum3(double (*red)[SF_T / 64], double& a, double& b, double& c) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); c += __shfl_down(c, off, 64);
-    }
-    __syncthreads();                                                 // red is no longer read
-    if (lane == 0) { red[0][wave] = a; red[1][wave] = b; red[2][wave] = c; }
-    __syncthreads();
-    a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-    b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    c = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
-}
-
-// the resolution a workgroup of a row's grid belongs to, and the workgroup's index inside it
-__device__ __forceinline__ int sf_find(const SfPlan& p, int tile, int& local) {
-    int r = 0;
-    for (int i = 1; i < p.R; ++i)
-        if (tile >= p.res[i].tile0) r = i;
-    local = tile - p.res[r].tile0;
-    return r;
-}
-
 // The window table and delta P0 of (row, resolution): E0 and sum w^2 as a thread's groups of four samples (taps: the ones it has just
 // written) in index order, fp32 squares added in fp64, then the fixed pairing - the same bits in every workgroup of the row, whatever
 // the row's alignment (zeros past its end add exact zeros).  Returns false for a silent target (uniform over the workgroup).
-__device__ __forceinline__ bool sf_floor(float* wtab, double (*red)[SF_T / 64], const float* __restrict__ yt, const SfRes& g, int T,
+__device__ __forceinline__ bool sf_floor(float* wtab, double (*red)[SL_T / 64], const float* __restrict__ yt, const SfRes& g, int T,
                                          double delta, float& dp0) {
     const int tid = threadIdx.x;
     double e0 = 0.0, w2 = 0.0, none = 0.0;
-    for (int n = tid; n < g.N; n += SF_T) {
-        const float w = sf_hann_tap(n, g.N, g.win);
+    for (int n = tid; n < g.N; n += SL_T) {
+        const float w = stft_hann<float>(n, g.N, g.win);
         wtab[n] = w;
         w2 += (double)(w * w);
     }
     const bool vec = (T % 4 == 0) && aligned16(yt);
-    for (int t = 4 * tid; t < T; t += 4 * SF_T) {
+    for (int t = 4 * tid; t < T; t += 4 * SL_T) {
         const float4 v = ld_group(yt, t, T, vec);
         e0 += (double)(v.x * v.x); e0 += (double)(v.y * v.y); e0 += (double)(v.z * v.z); e0 += (double)(v.w * v.w);
     }
-    sf_block_sum3(red, e0, w2, none);                                // its barriers also stand behind the table
+    sl_block_sum3(red, e0, w2, none);                                // its barriers also stand behind the table
     dp0 = (float)(delta * (w2 * e0 / (double)T));
     return e0 != 0.0;
 }
@@ -170,7 +133,7 @@ __device__ __forceinline__ SfBin sf_bin(float re_p, float im_p, float re_t, floa
 }
 
 template <int M>
-__device__ __forceinline__ void sf_analysis(cf* img, float* wtab, double (*red)[SF_T / 64], const float* __restrict__ yp,
+__device__ __forceinline__ void sf_analysis(cf* img, float* wtab, double (*red)[SL_T / 64], const float* __restrict__ yp,
                                             const float* __restrict__ yt, const SfRes& g, int T, int f0, double delta,
                                             double* __restrict__ slab) {
 #pragma clang fp contract(off)
@@ -186,7 +149,7 @@ __device__ __forceinline__ void sf_analysis(cf* img, float* wtab, double (*red)[
     auto add = [&](const SfBin& o) { s_d += (double)(o.d * o.d); s_y += (double)(o.my * o.my); s_l += (double)(o.l * o.l); };
 #pragma unroll
     for (int e = 0; e < 4; ++e) {                                    // FR M = 1024 (frame, slot) pairs, four per thread
-        const int q = tid + SF_T * e, lf = q / M, i = q % M;
+        const int q = tid + SL_T * e, lf = q / M, i = q % M;
         if (f0 + lf >= g.F) continue;
         const cf a = img[lf * M + fl_swz(i)], c = img[(FR + lf) * M + fl_swz(i)];
         if (i == 0) {
@@ -196,18 +159,18 @@ __device__ __forceinline__ void sf_analysis(cf* img, float* wtab, double (*red)[
             add(sf_bin(a.x, a.y, c.x, c.y, dp0));
         }
     }
-    sf_block_sum3(red, s_d, s_y, s_l);
+    sl_block_sum3(red, s_d, s_y, s_l);
     if (tid == 0) { slab[0] = s_d; slab[1] = s_y; slab[2] = s_l; }
 }
 
-__global__ __launch_bounds__(SF_T) void slf_analysis_kernel(const float* __restrict__ wav_pred, const float* __restrict__ wav_true, SfPlan p,
+__global__ __launch_bounds__(SL_T) void slf_analysis_kernel(const float* __restrict__ wav_pred, const float* __restrict__ wav_true, SfPlan p,
                                                             double delta, SfWs ws) {
     __shared__ cf img[SF_IMG];
-    __shared__ float wtab[SF_MAX_NFFT];
-    __shared__ double red[3][SF_T / 64];
+    __shared__ float wtab[SL_MAX_NFFT];
+    __shared__ double red[3][SL_T / 64];
     const int b = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
     int local;
-    const SfRes g = p.res[sf_find(p, tile, local)];
+    const SfRes g = p.res[sl_find(p, &SfRes::tile0, tile, local)];
     const float* yp = wav_pred + (size_t)b * p.T;
     const float* yt = wav_true + (size_t)b * p.T;
     double* slab = ws.slabs + ((size_t)b * p.tiles + tile) * 3;
@@ -220,43 +183,9 @@ __global__ __launch_bounds__(SF_T) void slf_analysis_kernel(const float* __restr
     }
 }
 
-__global__ __launch_bounds__(SF_T) void slf_finalize_kernel(SfPlan p, double sc_weight, double log_weight, double scale, SfWs ws,
-                                                            double* __restrict__ spectral_out, float* __restrict__ loss_out) {
-    __shared__ double red[3][SF_T / 64];
-    const int tid = threadIdx.x;
-    const double c = scale / (double)p.R;
-    for (long long pair = tid; pair < (long long)p.B * p.R; pair += SF_T) {
-        const int b = (int)(pair / p.R), r = (int)(pair % p.R);
-        const SfRes& g = p.res[r];
-        const double* s = ws.slabs + ((size_t)b * p.tiles + g.tile0) * 3;
-        double d = 0.0, y = 0.0, l = 0.0;
-        for (int i = 0; i < g.ftiles; ++i) { d += s[3 * i]; y += s[3 * i + 1]; l += s[3 * i + 2]; }
-        const bool counted = y > 0.0;                                // M_y >= sqrt(delta P0) > 0 in a counted row
-        ws.terms[2 * pair] = counted ? d / y : 0.0;
-        ws.terms[2 * pair + 1] = counted ? l / ((double)g.F * (double)g.K) : 0.0;
-        ws.coef[2 * pair] = counted ? c * sc_weight / y : 0.0;
-        ws.coef[2 * pair + 1] = counted ? c * log_weight : 0.0;
-        if (r == 0) ws.rows[3 * (size_t)b + 2] = counted ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    double q_sc = 0.0, q_lm = 0.0, q_n = 0.0;
-    for (int b = tid; b < p.B; b += SF_T) {
-        double sc = 0.0, lm = 0.0;
-        for (int r = 0; r < p.R; ++r) { sc += ws.terms[2 * ((size_t)b * p.R + r)]; lm += ws.terms[2 * ((size_t)b * p.R + r) + 1]; }
-        sc /= (double)p.R; lm /= (double)p.R;
-        ws.rows[3 * (size_t)b] = sc; ws.rows[3 * (size_t)b + 1] = lm;
-        q_sc += sc; q_lm += lm; q_n += ws.rows[3 * (size_t)b + 2];
-    }
-    sf_block_sum3(red, q_sc, q_lm, q_n);
-    if (tid == 0) {
-        spectral_out[0] = q_sc; spectral_out[1] = q_lm; spectral_out[2] = q_n;
-        if (loss_out) loss_out[0] += (float)(scale * (sc_weight * q_sc + log_weight * q_lm));
-    }
-}
-
 // frames[f][n - n_lo] = w[n] sum_k g[f,k] (Re X^[f,k] cos(2 pi k n / N) - Im X^[f,k] sin(2 pi k n / N)) for the non-zero taps
 template <int M>
-__device__ __forceinline__ void sf_adjoint(cf* img, float* wtab, double (*red)[SF_T / 64], const float* __restrict__ yp,
+__device__ __forceinline__ void sf_adjoint(cf* img, float* wtab, double (*red)[SL_T / 64], const float* __restrict__ yp,
                                            const float* __restrict__ yt, const SfRes& g, int T, int f0, double delta, float ca, float cb,
                                            float* __restrict__ fr) {
 #pragma clang fp contract(off)
@@ -270,7 +199,7 @@ __device__ __forceinline__ void sf_adjoint(cf* img, float* wtab, double (*red)[S
     auto gain = [&](const SfBin& o) { return (ca * (2.f * o.d) + cb * (2.f * o.l * inv_fk / o.mp)) / o.mp; };
 #pragma unroll
     for (int e = 0; e < 4; ++e) {                                    // a thread rewrites the slots of y^ it has read itself
-        const int q = tid + SF_T * e, lf = q / M, i = q % M;
+        const int q = tid + SL_T * e, lf = q / M, i = q % M;
         const cf a = img[lf * M + fl_swz(i)], c = img[(FR + lf) * M + fl_swz(i)];
         cf G;
         if (i == 0) {
@@ -291,7 +220,7 @@ __device__ __forceinline__ void sf_adjoint(cf* img, float* wtab, double (*red)[S
     const int n_hi = g.n_lo + g.win;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const int q = tid + SF_T * e, lf = q / M, i = q % M, f = f0 + lf;
+        const int q = tid + SL_T * e, lf = q / M, i = q % M, f = f0 + lf;
         if (f >= g.F) continue;
         const cf z = img[lf * M + fl_swz(i)];
         float* __restrict__ o = fr + (size_t)f * g.win;
@@ -301,15 +230,15 @@ __device__ __forceinline__ void sf_adjoint(cf* img, float* wtab, double (*red)[S
     }
 }
 
-__global__ __launch_bounds__(SF_T) void slf_adjoint_kernel(const float* __restrict__ wav_pred, const float* __restrict__ wav_true, SfPlan p,
+__global__ __launch_bounds__(SL_T) void slf_adjoint_kernel(const float* __restrict__ wav_pred, const float* __restrict__ wav_true, SfPlan p,
                                                            double delta, SfWs ws) {
     __shared__ cf img[SF_IMG];
-    __shared__ float wtab[SF_MAX_NFFT];
-    __shared__ double red[3][SF_T / 64];
+    __shared__ float wtab[SL_MAX_NFFT];
+    __shared__ double red[3][SL_T / 64];
     const int b = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
     if (ws.rows[3 * (size_t)b + 2] == 0.0) return;                   // a row that is not counted: the fold writes its zeros
     int local;
-    const int r_of = sf_find(p, tile, local);
+    const int r_of = sl_find(p, &SfRes::tile0, tile, local);
     const SfRes g = p.res[r_of];
     const float* yp = wav_pred + (size_t)b * p.T;
     const float* yt = wav_true + (size_t)b * p.T;
@@ -324,44 +253,13 @@ __global__ __launch_bounds__(SF_T) void slf_adjoint_kernel(const float* __restri
     }
 }
 
-// p[j]: the frames whose non-zero taps reach the padded position j, in ascending frame order
-__device__ __forceinline__ double sf_ola(const float* __restrict__ fr, const SfRes& g, int j) {
-    const int num = j - (g.n_lo + g.win) + 1;
-    const int f_lo = num <= 0 ? 0 : (num + g.hop - 1) / g.hop;
-    int f_hi = j < g.n_lo ? -1 : (j - g.n_lo) / g.hop;
-    if (f_hi > g.F - 1) f_hi = g.F - 1;
-    double acc = 0.0;
-    for (int f = f_lo; f <= f_hi; ++f) acc += (double)fr[(size_t)f * g.win + (j - g.hop * f - g.n_lo)];
-    return acc;
-}
-
-__global__ __launch_bounds__(256) void slf_fold_kernel(SfPlan p, SfWs ws, int accumulate, float* __restrict__ dwav) {
-    const int chunks = (p.T + 255) / 256;
-    const int b = blockIdx.x / chunks, t = (blockIdx.x % chunks) * 256 + threadIdx.x;
-    if (t >= p.T) return;
-    const size_t o = (size_t)b * p.T + t;
-    double total = 0.0;
-    if (ws.rows[3 * (size_t)b + 2] != 0.0) {
-        for (int r = 0; r < p.R; ++r) {
-            const SfRes& g = p.res[r];
-            const float* __restrict__ fr = ws.frames + (size_t)b * p.frames_row + g.frame0;
-            const int half = g.N / 2;
-            double acc = sf_ola(fr, g, t + half);
-            if (t >= 1 && t <= half) acc += sf_ola(fr, g, half - t);
-            if (t <= p.T - 2 && t >= p.T - 1 - half) acc += sf_ola(fr, g, 2 * (p.T - 1) - t + half);
-            total += acc;
-        }
-    }
-    dwav[o] = accumulate ? (float)((double)dwav[o] + total) : (float)total;
-}
-
 bool sf_supported(int T, int N, int win, int hop) {
-    return (N == 128 || N == 256 || N == 512 || N == 1024) && win >= 2 && win <= N && hop >= 1 && T >= N / 2 + 1 && T <= SF_MAX_T;
+    return (N == 128 || N == 256 || N == 512 || N == 1024) && win >= 2 && win <= N && hop >= 1 && T >= N / 2 + 1 && T <= SL_MAX_T;
 }
 
 // the plan of a call; the doubles and the floats of its workspace (false: not supported)
 bool sf_plan(int B, int T, int R, const int* res, SfPlan* out, size_t& doubles, size_t& floats) {
-    if (B <= 0 || R < 1 || R > SF_MAX_R || !res) return false;
+    if (B <= 0 || R < 1 || R > SL_MAX_R || !res) return false;
     SfPlan p = {};
     p.R = R; p.B = B; p.T = T;
     long long tiles = 0, frames = 0;
@@ -370,16 +268,15 @@ bool sf_plan(int B, int T, int R, const int* res, SfPlan* out, size_t& doubles, 
         if (!sf_supported(T, N, win, hop)) return false;
         SfRes& g = p.res[r];
         const int per = 2048 / N;
-        g.N = N; g.win = win; g.hop = hop; g.F = 1 + T / hop; g.K = N / 2 + 1; g.n_lo = (N - win) / 2;
-        g.ftiles = (g.F + per - 1) / per;
-        g.tile0 = (int)tiles; g.frame0 = frames;
-        tiles += g.ftiles; frames += (long long)g.F * win;
+        sl_res_fill(g, T, N, win, hop, frames);
+        g.ntiles = (g.F + per - 1) / per;
+        g.tile0 = (int)tiles;
+        tiles += g.ntiles;
     }
-    const long long chunks = (T + 255) / 256;
-    if (tiles * B > 0x7fffffffLL || chunks * B > 0x7fffffffLL) return false;                        // the grids are one-dimensional
+    if (tiles * B > 0x7fffffffLL || sl_fold_blocks(B, T) > 0x7fffffffLL) return false;              // the grids are one-dimensional
     p.tiles = (int)tiles; p.frames_row = frames;
     if (out) *out = p;
-    doubles = (size_t)B * ((size_t)tiles * 3 + (size_t)R * 4 + 3);
+    doubles = sl_head_doubles(B, tiles, R);
     floats = (size_t)B * (size_t)frames;
     return true;
 }
@@ -402,28 +299,22 @@ size_t unetrir_spectral_loss_fft_ws_bytes(int B, int T, int R, const int* res) {
 int unetrir_spectral_loss_fft_f32(const float* wav_pred, const float* wav_true, int B, int T, int R, const int* res, double floor_db,
                                   double sc_weight, double log_weight, double weight, double inv_global_batch, int accumulate, float* dwav,
                                   double* spectral_out, float* loss_out, void* ws, size_t ws_bytes, unetrir_stream_t stream) {
-    if (!wav_pred || !wav_true || !spectral_out || !ws || !res || B <= 0 || R < 1 || R > SF_MAX_R) return UNETRIR_EINVAL;
-    if (!isfinite(floor_db) || !(floor_db > 0.0) || floor_db > 200.0 || !(sc_weight >= 0.0) || !isfinite(sc_weight) ||
-        !(log_weight >= 0.0) || !isfinite(log_weight) || !(weight >= 0.0) || !isfinite(weight) || !(inv_global_batch > 0.0) ||
-        !isfinite(inv_global_batch) || (accumulate && !dwav))
+    if (!sl_args_ok(wav_pred, wav_true, B, R, res, floor_db, sc_weight, log_weight, weight, inv_global_batch, accumulate, dwav,
+                    spectral_out, ws))
         return UNETRIR_EINVAL;
     SfPlan p;
     size_t doubles, floats;
     if (!sf_plan(B, T, R, res, &p, doubles, floats)) return UNETRIR_EINVAL;
-    if (ws_bytes < sf_bytes(doubles, floats) || ((uintptr_t)ws & 7)) return UNETRIR_EINVAL;
+    if (ws_bytes < sf_bytes(doubles, floats)) return UNETRIR_EINVAL;
     SfWs w;
-    w.slabs = (double*)ws;
-    w.terms = w.slabs + (size_t)B * p.tiles * 3;
-    w.coef = w.terms + (size_t)B * R * 2;
-    w.rows = w.coef + (size_t)B * R * 2;
-    w.frames = (float*)(w.rows + (size_t)B * 3);
+    w.frames = (float*)sl_head_carve(w, ws, B, p.tiles, R);
     const double delta = pow(10.0, -floor_db / 10.0), scale = weight * inv_global_batch;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(slf_analysis_kernel, dim3((unsigned)(B * p.tiles)), dim3(SF_T), 0, s, wav_pred, wav_true, p, delta, w);
-    hipLaunchKernelGGL(slf_finalize_kernel, dim3(1), dim3(SF_T), 0, s, p, sc_weight, log_weight, scale, w, spectral_out, loss_out);
+    hipLaunchKernelGGL(slf_analysis_kernel, dim3((unsigned)(B * p.tiles)), dim3(SL_T), 0, s, wav_pred, wav_true, p, delta, w);
+    hipLaunchKernelGGL(sl_finalize_kernel, dim3(1), dim3(SL_T), 0, s, p, sc_weight, log_weight, scale, w, spectral_out, loss_out);
     if (dwav) {
-        hipLaunchKernelGGL(slf_adjoint_kernel, dim3((unsigned)(B * p.tiles)), dim3(SF_T), 0, s, wav_pred, wav_true, p, delta, w);
-        hipLaunchKernelGGL(slf_fold_kernel, dim3((unsigned)(B * ((T + 255) / 256))), dim3(256), 0, s, p, w, accumulate, dwav);
+        hipLaunchKernelGGL(slf_adjoint_kernel, dim3((unsigned)(B * p.tiles)), dim3(SL_T), 0, s, wav_pred, wav_true, p, delta, w);
+        hipLaunchKernelGGL(sl_fold_kernel, dim3((unsigned)sl_fold_blocks(B, T)), dim3(SL_T), 0, s, p, w, accumulate, dwav);
     }
     return (int)hipGetLastError();
 }

@@ -45,10 +45,11 @@
 #include <stdint.h>
 #include <math.h>
 #include "kernels.h"
+#include "stft_common.h"
 
 namespace {
 
-// the constants of features.hip
+// the constants of features.hip; the window and the twiddle table are stft_common.h's
 constexpr int WL_MAX_NFFT = 1024;
 constexpr double WL_MD = 100.0;
 constexpr double WL_EP = 1e-5;
@@ -57,12 +58,6 @@ constexpr double WL_PI = 3.14159265358979323846;
 constexpr double WL_TINY32 = 1.1754943508222875e-38;
 constexpr double WL_LN10 = 2.30258509299404568402;
 constexpr int WSEG = 64;                                // output samples per workgroup of the synthesis
-
-__device__ __forceinline__ double hann_tap(int n, int n_fft, int win) {
-    const int m = n - (n_fft - win) / 2;
-    if (m < 0 || m >= win) return 0.0;
-    return 0.5 - 0.5 * cospi(2.0 * (double)m / (double)win);
-}
 
 // The loop of istft_feature_kernel, statement for statement (the fp32 waveform must come out with the same bits), then the residual.
 __global__ __launch_bounds__(256) void wave_synth_kernel(const float* __restrict__ feat, const float* __restrict__ phase_ref, int H,
@@ -78,11 +73,7 @@ __global__ __launch_bounds__(256) void wave_synth_kernel(const float* __restrict
     const float* __restrict__ f_ph = feat + ((size_t)b * 2 + 1) * H * W;
     const float* __restrict__ f_ref = phase_ref ? phase_ref + ((size_t)b * 2 + 1) * H * W : nullptr;
     const int nb = n_fft / 2 + 1, n_lo = (n_fft - win) / 2, n_hi = n_lo + win, mask = n_fft - 1;
-    for (int n = tid; n < n_fft; n += 256) {
-        double sn, cs;
-        sincospi(2.0 * (double)n / (double)n_fft, &sn, &cs);
-        tw_c[n] = cs; tw_s[n] = sn;
-    }
+    stft_tables(tw_c, tw_s, nullptr, n_fft, win, 256);
     const int p0 = t0 + n_fft / 2, p = p0 + s;
     int f_lo = (p0 - n_hi + 1 + hop - 1) / hop;
     if (p0 - n_hi + 1 <= 0) f_lo = 0;
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(256) void wave_synth_kernel(const float* __restrict
         __syncthreads();
         const int n = p - hop * f;
         if (n < n_lo || n >= n_hi) continue;
-        const double w = hann_tap(n, n_fft, win);
+        const double w = stft_hann<double>(n, n_fft, win);
         double part_k = 0.0;
         for (int k = kg; k < nb; k += 4) {
             const int idx = (k * n) & mask;
@@ -186,7 +177,7 @@ __global__ __launch_bounds__(256) void wave_adjoint_kernel(const float* __restri
             sincospi(2.0 * (double)n / (double)n_fft, &sn, &cs);
             tw_c[n] = cs; tw_s[n] = sn;
             const int i = f * hop + n - n_fft / 2;
-            sg[n] = (i >= 0 && i < T_out) ? hann_tap(n, n_fft, win) * (ub[i] * sc) : 0.0;
+            sg[n] = (i >= 0 && i < T_out) ? stft_hann<double>(n, n_fft, win) * (ub[i] * sc) : 0.0;
         }
         __syncthreads();
     }
