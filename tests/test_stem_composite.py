@@ -48,6 +48,46 @@ def test_composite_formulas_equal_autograd_of_the_two_layer_stack(H, W):
     assert np.abs(reg_w - (want_w + 0.25 * w0)).max() <= 1e-10 * np.abs(want_w).max()
 
 
+def test_chain_equals_autograd_of_the_two_layer_stack():
+    """SC.chain, the reference of the exact device tests, is the oracle's two layers under autograd - on integers, so with ==."""
+    rng = np.random.default_rng(7)
+    B, H, W, Ci, C0, C1 = 2, 4, 6, 2, 5, 3
+    x, g = rng.integers(-1, 4, (B, H, W, Ci)), rng.integers(-1, 4, (B, H, W, C1))
+    w0, b0, w1 = rng.integers(-1, 3, (C0, 3, 3, Ci)), rng.integers(-3, 4, C0), rng.integers(-1, 3, (C1, 3, 3, C0))
+    want_w, want_b = _autograd(x, g, w0, b0, w1)
+    got_w, got_b = SC.chain(x, g, w1)
+    assert np.array_equal(got_w, want_w) and np.array_equal(got_b, want_b)
+    reg_w, reg_b = SC.chain(x, g, w1, 0.5, w0)
+    assert np.array_equal(reg_w, want_w + 0.5 * w0) and np.array_equal(reg_b, want_b)
+
+
+@pytest.mark.parametrize("B,H,W", SC.EXACT_SHAPES)
+def test_exact_data_chain_equals_formulas_and_stays_exact_in_fp32(B, H, W):
+    """What tests/test_stem_composite_exact_gpu.py rests on, from the reference's side only (no kernel output is looked at): on the
+    integer data of each of its shapes the two-layer chain and the S, T, E, F formulas agree in every element; the inputs are
+    integers that bfloat16 holds; every fp32 partial sum of the device (products of magnitude <= 9 over at most P = B H W pixels)
+    stays below 2^24 in any order; and so does the result - below 2^23 where it is used with reg = 0.5, so that result + 0.5 * w0
+    is exact in fp32, fused or not."""
+    import exact_data as X
+    c = SC.exact_case(B, H, W)
+    t = torch.tensor
+    X.check_exactness_conditions({"x": (t(c["x"]), True), "g": (t(c["g"]), True), "w1": (t(c["w1"]), True), "w0": (t(c["w0"]), False)},
+                                 9 * B * H * W, what=f"stem composite {B}x{H}x{W}")
+    assert max(map(abs, X.ACT)) ** 2 == 9 and 9 * B * H * W < 2 ** 24
+    assert c["x"].shape == (B, H, W, 2) and c["g"].shape == (B, H, W, 64) and c["dw0"].shape == (64, 3, 3, 2) and c["db0"].shape == (64,)
+    got_w, got_b = SC.stem_composite(c["x"], c["g"], c["w1"])
+    assert np.array_equal(c["dw0"], got_w) and np.array_equal(c["db0"], got_b)
+    big = max(np.abs(c["dw0"]).max(), np.abs(c["db0"]).max())
+    assert big < 2 ** 24
+    assert np.array_equal(c["dw0"], np.round(c["dw0"])) and np.array_equal(c["db0"], np.round(c["db0"]))
+    assert (c["w0"][..., 2:] != 0).all()
+    if (B, H, W) in SC.REG_SHAPES:
+        reg_w, reg_b = SC.chain(c["x"], c["g"], c["w1"], X.REG, c["w0"][..., :2])
+        assert np.array_equal(reg_w, c["dw0"] + X.REG * c["w0"][..., :2]) and np.array_equal(reg_b, c["db0"])
+        assert np.abs(reg_w).max() < 2 ** 23 and big < 2 ** 23
+    print(f"stem composite exact data {B}x{H}x{W}: P {B * H * W}, largest |dW0| {np.abs(c['dw0']).max():.4g}, |db0| {np.abs(c['db0']).max():.4g}")
+
+
 def _model_stem_composite(rt):
     """The op on the simulated operators: reads g_y[1], the input and the transposed enc1.cb1 kernel, writes the two gradient ranges."""
     def stem_composite(g, x, w1t, dw0, db0, ws, reg=0.0, w0=None):

@@ -4,7 +4,9 @@ then the stem's weight gradient and a column sum.
 
 Tolerance: none of its own.  Both paths are measured against the fp64 reference (relative L2 per tensor); the composite path, which
 never rounds the tensor between the two layers to bf16, must be no worse than 1.25 x the replaced path's error - the margin covers
-summation-order scatter only.
+summation-order scatter only.  That is the statement about real-valued data against the replaced path; the per-element guarantee
+(every term, at the shapes where the kernels' loops take further trips) is tests/test_stem_composite_exact_gpu.py, which compares
+with == on integer data.
 
 Shapes: the kernel's minimum is a 1 x 1 image; its correlation tile is 16 rows x 256 columns, so 17 x 300 is a non-square image of
 two (ragged) tiles per side; 3 x 5 has nothing but border pixels and adjacent corners.
