@@ -16,67 +16,25 @@ decay_loss=DecayLoss(...))` adds the term to the train step; the object also wor
     dpred = dl(wav_pred, wav_true, pred=pred)                      # fp32 [B, 2, H, W], wav_pred = PostProcess(pred)
     engine.backward(dpred=dpred)
 """
-import math
-
-import torch
-
 from . import ops
 from .features import HOP_LENGTH, N_FFT, STFT_SHAPE, WIN_LENGTH
+from .waveterm import WaveTerm
 
 
-class DecayLoss:
+class DecayLoss(WaveTerm):
+    out_len = 2
+    decay_out = property(lambda self: self.out, doc="fp64 [2] on the device: (sum_b Q_b, samples counted) of the last call")
+
     def __init__(self, weight=1.0, floor_db=60.0, des_shape=STFT_SHAPE, n_fft=N_FFT, win_length=WIN_LENGTH, hop_length=HOP_LENGTH):
         """floor_db: the curves are floored at -floor_db relative to the target's energy: the fit ends where the window has nothing left
         to say."""
-        if not (weight >= 0.0) or not math.isfinite(weight):
-            raise ValueError("weight must be a finite number >= 0")
-        if not math.isfinite(floor_db) or not (0.0 < floor_db <= 200.0):
-            raise ValueError("floor_db must be in (0, 200]")
-        self.weight, self.floor_db = float(weight), float(floor_db)
-        self.des_shape = (int(des_shape[0]), int(des_shape[1]))
-        self.n_fft, self.win_length, self.hop_length = int(n_fft), int(win_length), int(hop_length)
-        self.T = self.hop_length * (self.des_shape[1] - 1)
-        self.decay_out = None           # fp64 [2] on the device: (sum_b Q_b, samples counted) of the last call
-        self._ws = None
-        self._dwav = None
-        self._dpred = None
+        super().__init__(floor_db, des_shape, n_fft, win_length, hop_length, weight=weight)
 
-    def prepare(self, device, B=None):
-        """Everything the calls need that does not depend on the batch, and with B the workspace and the cotangent as well (a HIP graph
-        capture must not allocate)."""
-        if self.decay_out is None or self.decay_out.device != torch.device(device):
-            self.decay_out = torch.zeros(2, dtype=torch.float64, device=device)
-            self._ws = ops.Workspace(device)
-            self._dwav = self._dpred = None
-        if B is not None:
-            self._ws.reserve(ops.decay_loss_ws_bytes(B, self.T))
-            if self._dwav is None or self._dwav.shape[0] != B:
-                self._dwav = torch.empty((B, self.T), dtype=torch.float32, device=device)
+    def ws_bytes(self, B):
+        return ops.decay_loss_ws_bytes(B, self.T)
 
-    def __call__(self, wav_pred, wav_true, *, pred=None, phase_ref=None, dpred=None, accumulate=False, global_batch=None, loss_out=None,
-                 backward=True):
-        """wav_pred, wav_true fp32 [B, T] -> dwav (a buffer this object keeps), or with pred fp32 [B, 2, H, W] (wav_pred =
-        PostProcess(pred); phase_ref: the network input of a phase-difference model) dpred: the given buffer or one this object keeps,
-        written, or with accumulate added to.  None with backward=False (the loss alone: no gradient, no vector-Jacobian product).
-        loss_out: a float32 device vector whose element 0 grows by weight / global_batch * sum_b Q_b."""
-        self.prepare(wav_pred.device)
-        dwav = None
-        if backward:
-            if self._dwav is None or self._dwav.shape != wav_pred.shape:
-                self._dwav = torch.empty_like(wav_pred)
-            dwav = self._dwav
-        ops.decay_loss(wav_pred, wav_true, self.decay_out, self._ws, floor_db=self.floor_db, weight=self.weight, global_batch=global_batch,
+    def _launch(self, wav_pred, wav_true, dwav, add, global_batch, loss_out):
+        if add:
+            raise ValueError("DecayLoss: the kernel writes its cotangent and cannot add to one; a dwav= the caller gives is not taken")
+        ops.decay_loss(wav_pred, wav_true, self.out, self._ws, floor_db=self.floor_db, weight=self.weight, global_batch=global_batch,
                        dwav=dwav, loss_out=loss_out)
-        if not backward:
-            return None
-        if pred is None:
-            return dwav
-        if dpred is None:
-            if accumulate:
-                raise ValueError("accumulate=True adds to a dpred the caller gives")
-            if self._dpred is None or self._dpred.shape != pred.shape:
-                self._dpred = torch.empty_like(pred)
-            dpred = self._dpred
-        ops.istft_features_bwd(pred, dwav, dpred, self.des_shape[0], self.des_shape[1], self.n_fft, self.win_length, self.hop_length,
-                               phase_ref=phase_ref, accumulate=accumulate)
-        return dpred

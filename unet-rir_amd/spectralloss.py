@@ -21,18 +21,19 @@ term that is paid every step; `"dft"` is the form for the end of training, where
     dpred = sl(wav_pred, wav_true, pred=pred)                      # fp32 [B, 2, H, W], wav_pred = PostProcess(pred)
     engine.backward(dpred=dpred)
 """
-import math
-
-import torch
-
 from . import ops
 from .features import HOP_LENGTH, N_FFT, STFT_SHAPE, WIN_LENGTH
+from .waveterm import WaveTerm
 
 # one resolution finer in time than the model's own (256, 128, 64), one finer in frequency and one much finer
 RESOLUTIONS = ((128, 64, 32), (512, 256, 128), (1024, 512, 256))
 
 
-class SpectralLoss:
+class SpectralLoss(WaveTerm):
+    out_len = 3
+    spectral_out = property(lambda self: self.out,
+                            doc="fp64 [3] on the device: (sum_b mean_r SC, sum_b mean_r LM, samples counted) of the last call")
+
     def __init__(self, weight=1.0, resolutions=RESOLUTIONS, sc_weight=1.0, log_weight=1.0, floor_db=60.0, des_shape=STFT_SHAPE,
                  n_fft=N_FFT, win_length=WIN_LENGTH, hop_length=HOP_LENGTH, *, method="dft"):
         """resolutions: 1 to 8 triples (n_fft, win_length, hop_length) of the loss's own transforms.  floor_db: the magnitudes are
@@ -42,15 +43,7 @@ class SpectralLoss:
         if method not in ("dft", "fft"):
             raise ValueError(f'method must be "dft" or "fft", not {method!r}')
         self.method = method
-        for name, v in (("weight", weight), ("sc_weight", sc_weight), ("log_weight", log_weight)):
-            if not (v >= 0.0) or not math.isfinite(v):
-                raise ValueError(f"{name} must be a finite number >= 0")
-        if not math.isfinite(floor_db) or not (0.0 < floor_db <= 200.0):
-            raise ValueError("floor_db must be in (0, 200]")
-        self.weight, self.sc_weight, self.log_weight, self.floor_db = float(weight), float(sc_weight), float(log_weight), float(floor_db)
-        self.des_shape = (int(des_shape[0]), int(des_shape[1]))
-        self.n_fft, self.win_length, self.hop_length = int(n_fft), int(win_length), int(hop_length)
-        self.T = self.hop_length * (self.des_shape[1] - 1)
+        super().__init__(floor_db, des_shape, n_fft, win_length, hop_length, weight=weight, sc_weight=sc_weight, log_weight=log_weight)
         self.resolutions = tuple(tuple(int(v) for v in r) for r in resolutions)
         if not 1 <= len(self.resolutions) <= 8 or any(len(r) != 3 for r in self.resolutions):
             raise ValueError("resolutions: 1 to 8 triples (n_fft, win_length, hop_length)")
@@ -63,52 +56,14 @@ class SpectralLoss:
                     raise ValueError(f'resolution {r} at {self.T} samples: method="fft" takes n_fft 128, 256, 512 or 1024 with '
                                      f'n_fft / 2 + 1 <= T <= 16384; use method="dft"')
         self._op = "spectral_loss_fft" if method == "fft" else "spectral_loss"       # looked up in ops at every call
-        self.spectral_out = None        # fp64 [3] on the device: (sum_b mean_r SC, sum_b mean_r LM, samples counted) of the last call
-        self._ws = None
-        self._dwav = None
-        self._dpred = None
 
-    def prepare(self, device, B=None):
-        """Everything the calls need that does not depend on the batch, and with B the workspace and the cotangent as well (a HIP graph
-        capture must not allocate)."""
-        if self.spectral_out is None or self.spectral_out.device != torch.device(device):
-            self.spectral_out = torch.zeros(3, dtype=torch.float64, device=device)
-            self._ws = ops.Workspace(device)
-            self._dwav = self._dpred = None
-        if B is not None:
-            need = getattr(ops, self._op + "_ws_bytes")(B, self.T, self.resolutions)
-            if not need:
-                raise ValueError(f"SpectralLoss: the kernels do not take waveforms of {self.T} samples at {self.resolutions}")
-            self._ws.reserve(need)
-            if self._dwav is None or self._dwav.shape[0] != B:
-                self._dwav = torch.empty((B, self.T), dtype=torch.float32, device=device)
+    def ws_bytes(self, B):
+        need = getattr(ops, self._op + "_ws_bytes")(B, self.T, self.resolutions)
+        if not need:
+            raise ValueError(f"SpectralLoss: the kernels do not take waveforms of {self.T} samples at {self.resolutions}")
+        return need
 
-    def __call__(self, wav_pred, wav_true, *, pred=None, phase_ref=None, dpred=None, accumulate=False, dwav=None, global_batch=None,
-                 loss_out=None, backward=True):
-        """wav_pred, wav_true fp32 [B, T] -> dwav (a buffer this object keeps; with dwav= given, the term's cotangent is ADDED to that
-        buffer and it is returned), or with pred fp32 [B, 2, H, W] (wav_pred = PostProcess(pred); phase_ref: the network input of a
-        phase-difference model) dpred: the given buffer or one this object keeps, written, or with accumulate added to.  None with
-        backward=False (the loss alone: no gradient, no vector-Jacobian product).  loss_out: a float32 device vector whose element 0
-        grows by weight / global_batch * sum_b Q_b."""
-        self.prepare(wav_pred.device)
-        add = dwav is not None
-        if backward and not add:
-            if self._dwav is None or self._dwav.shape != wav_pred.shape:
-                self._dwav = torch.empty_like(wav_pred)
-            dwav = self._dwav
-        getattr(ops, self._op)(wav_pred, wav_true, self.spectral_out, self._ws, self.resolutions, floor_db=self.floor_db,
-                               sc_weight=self.sc_weight, log_weight=self.log_weight, weight=self.weight, global_batch=global_batch,
-                               dwav=dwav if backward else None, accumulate=add and backward, loss_out=loss_out)
-        if not backward:
-            return None
-        if pred is None:
-            return dwav
-        if dpred is None:
-            if accumulate:
-                raise ValueError("accumulate=True adds to a dpred the caller gives")
-            if self._dpred is None or self._dpred.shape != pred.shape:
-                self._dpred = torch.empty_like(pred)
-            dpred = self._dpred
-        ops.istft_features_bwd(pred, dwav, dpred, self.des_shape[0], self.des_shape[1], self.n_fft, self.win_length, self.hop_length,
-                               phase_ref=phase_ref, accumulate=accumulate)
-        return dpred
+    def _launch(self, wav_pred, wav_true, dwav, add, global_batch, loss_out):
+        getattr(ops, self._op)(wav_pred, wav_true, self.out, self._ws, self.resolutions, floor_db=self.floor_db, sc_weight=self.sc_weight,
+                               log_weight=self.log_weight, weight=self.weight, global_batch=global_batch, dwav=dwav,
+                               accumulate=add and dwav is not None, loss_out=loss_out)

@@ -102,6 +102,14 @@ def lr_schedule(lr0, epoch, decay=(True, 80)):
     return lr0
 
 
+# The engines' own metrics: (record key, device counter of the engine, index of the raw per-step sum in it, attribute holding the
+# number of elements a step sums over - None: the batch size).  VAE: train_kl / val_kl, tf.keras.metrics.Mean over every (b, l) element
+# of kl_loss_object (main_training.py:246-250, :286-288, :318-320); VQ-VAE: mean((q - x)^2) over every element of the quantiser's
+# S (dl_models/vqvae.py:79-80); the classifier: correct rows over rows seen.  An engine with one of them has a loss term or target of
+# its own, and takes no term on the waveform.
+ENGINE_METRICS = (("kl", "kl_out", 1, "kl_elems"), ("vq", "vq_out", 1, "vq_elems"), ("acc", "acc_out", 0, None))
+
+
 class _LossFunction(torch.autograd.Function):
     """compute_loss of main_training.py:203-235 as an autograd node over the engine's fused sigmoid + loss kernel: the value is
     the per-replica scalar, backward() runs the engine's whole backward pass (and, through the trainer, the gradient
@@ -147,19 +155,15 @@ class Trainer:
         lr: the rate of every step that is not given one (`step(..., lr=)`).  Default 5e-7, or the LAMB object's learning_rate.
         dropout_seed: base seed of the Dropout streams; replica r draws from stream seed + r (independent masks per replica, as
         under MirroredStrategy).  Default: the engine's own seed (torch.initial_seed()).
-        wave_loss: a `unet_rir_amd.WaveLoss` - every step then also minimises weight / global batch * sum_b E_b / D_b on the waveform
-        the prediction reconstructs to (`step(..., wav_true=)`): the loss kernel runs as before (loss_out[1:3] keep their meaning,
-        loss_out[0] grows by the term), and the backward pass starts from dL/dpred of both terms (csrc/waveloss.hip) instead of the
-        loss kernel's dL/dlogits.  Engines with a loss term or target of their own (VAE, VQ-VAE, the classifier) are refused.
-        decay_loss: a `unet_rir_amd.DecayLoss` - every step then also minimises weight / global batch * sum_b Q_b on the energy decay
-        curve of that waveform (csrc/decayloss.hip): behind the wave-loss call, which also hands over the waveform, the term's
-        dL/dpred is added to that call's dpred (csrc/istft_bwd.hip) and loss_out[0] grows by the term.  Without a `wave_loss` the
-        trainer keeps one of weight 0 - an exact zero whose launch yields the waveform and the spectrogram loss's dL/dpred.  The same
-        engines are refused.
-        spectral_loss: a `unet_rir_amd.SpectralLoss` - every step then also minimises weight / global batch * sum_b Q_b, the
-        multi-resolution STFT loss of that waveform (csrc/spectralloss.hip), in the same place and under the same rules as the
-        decay_loss.  With both, the decay term writes its cotangent on the waveform, the spectral term adds to it, and ONE
-        vector-Jacobian product carries the sum onto dpred."""
+        wave_loss, decay_loss, spectral_loss: a `unet_rir_amd.WaveLoss`, `DecayLoss`, `SpectralLoss` - every step then also minimises
+        the term on the waveform the prediction reconstructs to (`step(..., wav_true=)`), all of one geometry.  The loss kernel runs as
+        before (loss_out[1:3] keep their meaning, loss_out[0] grows by every term); behind it runs one chain (`_waveform_terms`): the
+        wave-loss call (csrc/waveloss.hip), which yields dL/dpred of its own and of the spectrogram term and hands over the waveform;
+        the decay term, then the spectral term, the first writing its cotangent on the waveform and the next adding to it; and ONE
+        vector-Jacobian product (csrc/istft_bwd.hip) that adds the sum onto dpred, from which the backward pass starts instead of the
+        loss kernel's dL/dlogits.  For a decay_loss or spectral_loss without a `wave_loss` the trainer keeps one of weight 0 - an exact
+        zero whose launch yields the waveform and the spectrogram loss's dL/dpred.  Engines with a loss term or target of their own
+        (ENGINE_METRICS: VAE, VQ-VAE, the classifier) are refused."""
         self.module = None
         engine = model
         if not hasattr(model, "specs") and hasattr(model, "engine"):
@@ -169,32 +173,28 @@ class Trainer:
                 raise RuntimeError("build the model first (batch_size=...): the trainer drives the engine of one batch size")
         self.engine = engine
         self.rt = engine.rt
-        if wave_loss is not None:
-            own = [n for n in ("kl_out", "vq_out", "acc_out") if hasattr(engine, n)]
-            if own:
-                raise ValueError(f"wave_loss: {type(engine).__name__} has a loss term or target of its own ({own[0]}); the waveform loss "
-                                 "drives the spectrogram models only")
         self.wave_loss = wave_loss
         self.decay_loss = decay_loss
         self.spectral_loss = spectral_loss
         self._wave = wave_loss              # the WaveLoss the step calls: the user's, or for a decay_loss / spectral_loss without one, one of weight 0
-        for name, term, what in (("decay_loss", decay_loss, "decay"), ("spectral_loss", spectral_loss, "spectral")):
-            if term is None:
-                continue
-            own = [n for n in ("kl_out", "vq_out", "acc_out") if hasattr(engine, n)]
+        self._terms = tuple(t for t in (decay_loss, spectral_loss) if t is not None)       # on the waveform that call hands over, in launch order
+        given = [(n, t, w) for n, t, w in (("wave_loss", wave_loss, "waveform"), ("decay_loss", decay_loss, "decay"),
+                                           ("spectral_loss", spectral_loss, "spectral")) if t is not None]
+        self._wave_option = given[0][0] if given else None        # the first of the options set: the one the messages name
+        geo = lambda o: (o.des_shape, o.n_fft, o.win_length, o.hop_length)
+        for name, term, what in given:
+            own = [attr for _, attr, _, _ in ENGINE_METRICS if hasattr(engine, attr)]
             if own:
                 raise ValueError(f"{name}: {type(engine).__name__} has a loss term or target of its own ({own[0]}); the {what} loss "
                                  "drives the spectrogram models only")
-            geo = lambda o: (o.des_shape, o.n_fft, o.win_length, o.hop_length)
             if self._wave is None:
                 from .waveloss import WaveLoss
-                self._wave = WaveLoss(weight=0.0, des_shape=term.des_shape, n_fft=term.n_fft, win_length=term.win_length,
-                                      hop_length=term.hop_length)
+                self._wave = WaveLoss(0.0, "mse", None, *geo(term))
                 self._wave.prepare(engine.device, engine.B)
             elif geo(self._wave) != geo(term):
-                raise ValueError(f"{name}: its geometry {geo(term)} differs from the "
-                                 f"{'wave_loss' if wave_loss is not None else 'decay_loss'}'s {geo(self._wave)}")
-            term.prepare(engine.device, engine.B)
+                raise ValueError(f"{name}: its geometry {geo(term)} differs from the {self._wave_option}'s {geo(self._wave)}")
+            if term is not wave_loss:
+                term.prepare(engine.device, engine.B)
         if lr is None:
             lr = optimizer.learning_rate if isinstance(optimizer, LAMB) else 5e-7
         self.lr, self.alpha = lr, alpha
@@ -307,40 +307,36 @@ class Trainer:
         eng.forward(spec_in, emb, dropout_mask=dropout_mask, target=spec_out, global_batch=gb, alpha=self.alpha)
         if with_reg:
             eng.reg_loss()                      # on the pre-update weights, as compute_loss sees them
-        dpred = None
-        if self._wave is not None:
-            # on the current stream, behind the loss kernel: dL/dpred of the waveform term and of the spectrogram term in one launch
-            phase_ref = spec_in if eng.loss_diff else None
-            dpred = self._wave(eng.pred, wav_true, phase_ref=phase_ref, spec_target=spec_out, alpha=self.alpha,
-                               inv_norm=1.0 / (2.0 * eng.H * eng.W * gb), phase_weight=eng.loss_phase_weight, global_batch=gb,
-                               loss_out=eng.loss_out, want_wav=self.decay_loss is not None or self.spectral_loss is not None)
-            if self.decay_loss is not None and self.spectral_loss is None:
-                # the call above also handed over the waveform; the decay term's dL/dpred goes on top of its dpred
-                self.decay_loss(self._wave.wav_pred, wav_true, pred=eng.pred, phase_ref=phase_ref, dpred=dpred, accumulate=True,
-                                global_batch=gb, loss_out=eng.loss_out)
-            elif self.spectral_loss is not None:
-                # with a decay term as well: that one writes its cotangent on the waveform, the spectral term adds to it, and one
-                # vector-Jacobian product carries the sum onto dpred
-                dwav = None
-                if self.decay_loss is not None:
-                    dwav = self.decay_loss(self._wave.wav_pred, wav_true, global_batch=gb, loss_out=eng.loss_out)
-                self.spectral_loss(self._wave.wav_pred, wav_true, pred=eng.pred, phase_ref=phase_ref, dpred=dpred, accumulate=True,
-                                   dwav=dwav, global_batch=gb, loss_out=eng.loss_out)
+        dpred = None if self._wave is None else self._waveform_terms(spec_in, spec_out, wav_true)
         self._backward_and_reduce(dpred)
         self.apply_gradients()
+
+    def _waveform_terms(self, spec_in, spec_out, wav_true, backward=True):
+        """Everything on the current stream behind the loss kernel: the wave-loss call - dL/dpred of the waveform term and of the
+        spectrogram term in one launch, and the waveform for the terms on it; those terms in order, the first writing its cotangent on
+        the waveform into its own buffer, the next adding to that buffer; and, issued by the last of them, the one vector-Jacobian
+        product that adds the sum onto dpred.  -> dpred.  backward=False (a validation batch): the losses alone, -> None."""
+        eng = self.engine
+        gb = eng.B * self.world_size
+        phase_ref = spec_in if eng.loss_diff else None
+        fused = dict(spec_target=spec_out, alpha=self.alpha, inv_norm=1.0 / (2.0 * eng.H * eng.W * gb),
+                     phase_weight=eng.loss_phase_weight) if backward else {}
+        dpred = self._wave(eng.pred, wav_true, phase_ref=phase_ref, global_batch=gb, loss_out=eng.loss_out, want_wav=bool(self._terms),
+                           backward=backward, **fused)
+        dwav = None
+        for term in self._terms:
+            onto_dpred = dict(pred=eng.pred, phase_ref=phase_ref, dpred=dpred, accumulate=True) if backward and term is self._terms[-1] else {}
+            dwav = term(self._wave.wav_pred, wav_true, dwav=dwav, global_batch=gb, loss_out=eng.loss_out, backward=backward, **onto_dpred)
+        return dpred
 
     def step(self, spec_in, emb, spec_out, dropout_mask=None, lr=None, return_loss=False, wav_true=None):
         """inputs as DataGenerator.__getitem__ yields them (datageneratorv2.py:101-102), NCHW, per-replica shard.  wav_true fp32
         [B, T]: the target waveforms, with a `wave_loss` (DataGenerator(characteristics=True) delivers them)."""
         eng = self.engine
-        if self.wave_loss is not None and wav_true is None:
-            raise ValueError("this trainer has a wave_loss: step(..., wav_true=) needs the target waveforms")
-        if self.decay_loss is not None and wav_true is None:
-            raise ValueError("this trainer has a decay_loss: step(..., wav_true=) needs the target waveforms")
-        if self.spectral_loss is not None and wav_true is None:
-            raise ValueError("this trainer has a spectral_loss: step(..., wav_true=) needs the target waveforms")
         if self._wave is None:
             wav_true = None
+        elif wav_true is None:
+            raise ValueError(f"this trainer has a {self._wave_option}: step(..., wav_true=) needs the target waveforms")
         eng.training = True
         self._total_on_device = False
         self._lr_now = self.lr if lr is None else lr
@@ -528,6 +524,28 @@ class CheckpointManager:
         return state.get("epoch")
 
 
+class _Meter:
+    """A mean `fit` reports: the fp64 sums over an epoch of what `source()` - a view of a device counter, no copy - holds after every
+    batch, row 0 for the training and row 1 for the validation batches, and the rule that makes record entries of the summed rows.
+    count: the sums are divided by steps x count (per step, replicas included); None: the counter's last entry counts the samples that
+    entered the sums before it, which are divided by max(that, 1)."""
+
+    def __init__(self, keys, source, count, device):
+        self.keys, self.source, self.count = keys, source, count
+        self.tot = torch.zeros((2, len(keys) + (count is None)), dtype=torch.float64, device=device)
+
+    def add(self, row):
+        self.tot[row] += self.source()
+
+    def entries(self, tot, steps):
+        """tot: the sums, reduced over the replicas, on the host; steps: {"train": batches seen} and, with a validation pass, "val" """
+        out = {}
+        for row, (prefix, n) in enumerate(steps.items()):
+            den = max(float(tot[row, -1]), 1.0) if self.count is None else n * self.count
+            out.update({f"{prefix}_{key}": float(tot[row, i]) / den for i, key in enumerate(self.keys)})
+        return out
+
+
 def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: CheckpointManager = None, lr0=None,
         lr_exp_decay=(True, 80), start_epoch=0, log=print, val_updates_moving=True):
     """The epoch loop of main_training.py:336-390: exponential rate from epoch 80, running means of the amplitude / phase
@@ -541,77 +559,65 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
     test_step does (main_training.py:297-300): batch statistics, dropout active - and, as in Keras, the BatchNorm moving
     statistics move during it (`val_updates_moving=False` keeps them at their post-training values instead).
 
-    An engine with a device counter `acc_out` (cnn_clas.DeepCNNEngine, a classifier: batches are (x, None, one-hot target)) adds
-    `train_acc` / `val_acc` = correct rows over rows seen, across steps and replicas (History.train_acc_history of the legacy
-    trainer.py:230), accumulated on the device and read back once per epoch.  For such an engine `train_amp` / `val_amp` carry the
-    mean cross-entropy per row and `train_phase` / `val_phase` are 0.
+    Further means are summed on the device as fp64 and read back once per epoch, behind the validation pass where there is one
+    (`_Meter`); the keys of a validation pass are absent without one.  An engine with a counter of ENGINE_METRICS adds its metric,
+    the raw sum over steps x elements per step x replicas: `train_kl` / `val_kl` (VAE: kl_loss_object over every (b, l) element),
+    `train_vq` / `val_vq` (VQ-VAE: (q - x)^2 over every element) or `train_acc` / `val_acc` (cnn_clas.DeepCNNEngine, a classifier whose
+    batches are (x, None, one-hot target): correct rows over rows seen, History.train_acc_history of the legacy trainer.py:230; for such
+    an engine `train_amp` / `val_amp` carry the mean cross-entropy per row and `train_phase` / `val_phase` are 0).
 
-    With `trainer.wave_loss` a batch is (spec_in, emb, spec_out, wav_true) or DataGenerator(characteristics=True)'s (spec_in, emb,
-    spec_out, (room, wav_true)), and the record gains `train_wave` / `val_wave`: the mean of E_b / D_b over samples, steps and
-    replicas, accumulated on the device and read back once per epoch (the validation pass runs the loss alone, without its gradient).
-    `train_loss` / `val_loss` carry the term.
-
-    With `trainer.decay_loss` the batches are those four-tuples too, and the record gains `train_decay` / `val_decay`: the mean of Q_b
-    (dB^2) over the counted samples, steps and replicas, accumulated and read back the same way (the validation pass: the loss alone).
-
-    With `trainer.spectral_loss` likewise `train_sc` / `val_sc` and `train_logmag` / `val_logmag`: the means of mean_r SC and mean_r LM
-    over the counted samples, steps and replicas."""
+    With a term on the waveform (`trainer.wave_loss`, `decay_loss`, `spectral_loss`) a batch is (spec_in, emb, spec_out, wav_true) or
+    DataGenerator(characteristics=True)'s (spec_in, emb, spec_out, (room, wav_true)); `train_loss` / `val_loss` carry the terms, and the
+    validation pass runs the trainer's chain for the losses alone, without gradients.  The record gains, per term the user gave:
+    `train_wave` / `val_wave`, the sum of E_b / D_b over steps x batch size x replicas; `train_decay` / `val_decay`, the sum of Q_b (dB^2)
+    over max(samples counted, 1) - a sample with a silent target is not counted; `train_sc` / `val_sc` and `train_logmag` /
+    `val_logmag`, the sums of mean_r SC and mean_r LM over max(samples counted, 1)."""
     eng = trainer.engine
-    wl = trainer.wave_loss
-    dl = trainer.decay_loss
-    sl = trainer.spectral_loss
-    wave = trainer._wave                       # the WaveLoss the steps call (an internal one of weight 0 when the user gave none)
+    world = trainer.world_size
 
     def unpack(batch):
         """(spec_in, emb, spec_out, wav_true or None)"""
-        if wave is None:
+        if trainer._wave is None:
             spec_in, emb, spec_out = batch
             return spec_in, emb, spec_out, None
         if len(batch) != 4:
-            which = "wave_loss" if wl is not None else ("decay_loss" if dl is not None else "spectral_loss")
-            raise ValueError(f"a trainer with a {which} takes batches (spec_in, emb, spec_out, wav_true) or (..., (room, wav_true))")
+            raise ValueError(f"a trainer with a {trainer._wave_option} takes batches (spec_in, emb, spec_out, wav_true) or (..., (room, wav_true))")
         spec_in, emb, spec_out, extra = batch
         return spec_in, emb, spec_out, extra[1] if isinstance(extra, (tuple, list)) else extra
     lr0 = trainer.lr if lr0 is None else lr0
     has_acc = hasattr(eng, "acc_out")          # a classifier: loss_out[1] is the raw cross-entropy sum over the rows
-    per_elem = 1.0 / ((1 if has_acc else eng.H * eng.W) * eng.B * trainer.world_size)       # loss_out[1:3] are raw per-replica sums of the two terms
+    per_elem = 1.0 / ((1 if has_acc else eng.H * eng.W) * eng.B * world)       # loss_out[1:3] are raw per-replica sums of the two terms
     history = []
 
     def reduce_(t):
-        if trainer.world_size > 1:
+        if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=trainer.group)
         return t.cpu()
+
+    # the sources are looked up at every batch: a loss object allocates its result vector at its first call
+    meters = [_Meter((key,), lambda a=attr, i=i: getattr(eng, a)[i:i + 1], (eng.B if count is None else getattr(eng, count)) * world, eng.device)
+              for key, attr, i, count in ENGINE_METRICS if hasattr(eng, attr)]
+    if trainer.wave_loss is not None:
+        meters.append(_Meter(("wave",), lambda: trainer.wave_loss.wave_out[0:1], eng.B * world, eng.device))
+    if trainer.decay_loss is not None:
+        meters.append(_Meter(("decay",), lambda: trainer.decay_loss.decay_out, None, eng.device))
+    if trainer.spectral_loss is not None:
+        meters.append(_Meter(("sc", "logmag"), lambda: trainer.spectral_loss.spectral_out, None, eng.device))
 
     for epoch in range(start_epoch, n_epochs):
         lr = lr_schedule(lr0, epoch, lr_exp_decay)
         tot = torch.zeros(4, dtype=torch.float64, device=eng.device)      # data loss, amplitude sum, phase sum, l2 terms
         nb = 0
-        has_kl = hasattr(eng, "kl_out")           # VAE: train_loss_kl / val_loss_kl (main_training.py:246-250, :286-288, :318-320)
-        ktot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_kl else None      # raw KL sums: training, validation
-        has_vq = hasattr(eng, "vq_out")           # VQ-VAE: the quantiser's S = sum (q - x)^2 of every step (dl_models/vqvae.py:79-80)
-        qtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_vq else None
-        atot = torch.zeros(2, dtype=torch.float64, device=eng.device) if has_acc else None       # correct rows: training, validation
-        wtot = torch.zeros(2, dtype=torch.float64, device=eng.device) if wl is not None else None      # sum_b E_b / D_b: training, validation
-        dtot = torch.zeros(4, dtype=torch.float64, device=eng.device) if dl is not None else None      # (sum_b Q_b, samples counted): training, validation
-        stot = torch.zeros(6, dtype=torch.float64, device=eng.device) if sl is not None else None      # (sum SC, sum LM, samples counted): training, validation
+        for mt in meters:
+            mt.tot.zero_()
         eng.reg_loss()
         reg0 = eng.reg_out[0].double()           # l2 terms on the weights the first step of the epoch sees
         for batch in train_batches(epoch):
             spec_in, emb, spec_out, wav_true = unpack(batch)
             trainer.step(spec_in, emb, spec_out, lr=lr, wav_true=wav_true)
-            if wl is not None:
-                wtot[0] += wl.wave_out[0]
-            if dl is not None:
-                dtot[0:2] += dl.decay_out
-            if sl is not None:
-                stot[0:3] += sl.spectral_out
             tot[:3] += eng.loss_out[:3].double()     # total data loss, amplitude term, phase term of this step (raw sums ~1e5: fp64)
-            if has_kl:
-                ktot[0] += eng.kl_out[1].double()
-            if has_vq:
-                qtot[0] += eng.vq_out[1].double()
-            if has_acc:
-                atot[0] += eng.acc_out[0].double()
+            for mt in meters:
+                mt.add(0)
             nb += 1
         # the l2 terms drift over an epoch (Adam moves every weight by ~lr per step whatever the gradient's scale): the reported
         # mean takes the trapezoid of their value before the first and after the last step instead of nine reductions per step
@@ -621,22 +627,7 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
         n = max(nb, 1)
         rec = {"epoch": epoch + 1, "lr": lr, "train_loss": float(tot[0] + tot[3]) / n,
                "train_amp": float(tot[1]) * per_elem / n, "train_phase": float(tot[2]) * per_elem / n}
-        if has_kl:         # tf.keras.metrics.Mean over every (b, l) element of kl_loss_object, across steps and replicas
-            per_kl = 1.0 / (eng.kl_elems * trainer.world_size)
-            rec["train_kl"] = float(reduce_(ktot[0:1].clone())[0]) * per_kl / n
-        if has_vq:         # mean((q - x)^2) over every element, across steps and replicas
-            per_vq = 1.0 / (eng.vq_elems * trainer.world_size)
-            rec["train_vq"] = float(reduce_(qtot[0:1].clone())[0]) * per_vq / n
-        if wl is not None and val_batches is None:        # with a validation pass: both sums in one read-back behind it
-            rec["train_wave"] = float(reduce_(wtot.clone())[0]) / (n * eng.B * trainer.world_size)
-        if dl is not None and val_batches is None:
-            dv = reduce_(dtot.clone())
-            rec["train_decay"] = float(dv[0]) / max(float(dv[1]), 1.0)
-        if sl is not None and val_batches is None:
-            sv = reduce_(stot.clone())
-            rec["train_sc"], rec["train_logmag"] = float(sv[0]) / max(float(sv[2]), 1.0), float(sv[1]) / max(float(sv[2]), 1.0)
-        if has_acc and val_batches is None:        # with a validation pass: both counts in one read-back behind it
-            rec["train_acc"] = float(reduce_(atot.clone())[0]) / (n * eng.B * trainer.world_size)
+        steps = {"train": n}
         if val_batches is not None:
             vt = torch.zeros(3, dtype=torch.float64, device=eng.device)
             vb = 0
@@ -646,52 +637,21 @@ def fit(trainer: "Trainer", train_batches, n_epochs, val_batches=None, manager: 
                 eng.training = True
                 eng.begin_step(lr, n_draws=(eng.n_dropout_draws if trainer.dropout else 0) + eng.n_noise_draws, forward_only=True)     # device counters only
                 mask = eng.make_dropout_mask() if trainer.dropout else None
-                eng.forward(spec_in, emb, dropout_mask=mask, target=spec_out, global_batch=eng.B * trainer.world_size, alpha=trainer.alpha)
-                if wave is not None:
-                    wave(eng.pred, wav_true, phase_ref=spec_in if eng.loss_diff else None, global_batch=eng.B * trainer.world_size,
-                         loss_out=eng.loss_out, backward=False, want_wav=dl is not None or sl is not None)
-                if wl is not None:
-                    wtot[1] += wl.wave_out[0]
-                if dl is not None:
-                    dl(wave.wav_pred, wav_true, global_batch=eng.B * trainer.world_size, loss_out=eng.loss_out, backward=False)
-                    dtot[2:4] += dl.decay_out
-                if sl is not None:
-                    sl(wave.wav_pred, wav_true, global_batch=eng.B * trainer.world_size, loss_out=eng.loss_out, backward=False)
-                    stot[3:6] += sl.spectral_out
+                eng.forward(spec_in, emb, dropout_mask=mask, target=spec_out, global_batch=eng.B * world, alpha=trainer.alpha)
+                if trainer._wave is not None:
+                    trainer._waveform_terms(spec_in, spec_out, wav_true, backward=False)
                 vt += eng.loss_out[:3].double()
-                if has_kl:
-                    ktot[1] += eng.kl_out[1].double()
-                if has_vq:
-                    qtot[1] += eng.vq_out[1].double()
-                if has_acc:
-                    atot[1] += eng.acc_out[0].double()
+                for mt in meters:
+                    mt.add(1)
                 vb += 1
             if saved_moving is not None:
                 for k, v in saved_moving.items():
                     eng.moving[k].copy_(v)
             vt = reduce_(vt)
-            m = max(vb, 1)
+            m = steps["val"] = max(vb, 1)
             rec.update(val_loss=float(vt[0]) / m, val_amp=float(vt[1]) * per_elem / m, val_phase=float(vt[2]) * per_elem / m)
-            if has_kl:
-                rec["val_kl"] = float(reduce_(ktot[1:2].clone())[0]) * per_kl / m
-            if has_vq:
-                rec["val_vq"] = float(reduce_(qtot[1:2].clone())[0]) * per_vq / m
-            if wl is not None:
-                wv = reduce_(wtot.clone())
-                rec["train_wave"] = float(wv[0]) / (n * eng.B * trainer.world_size)
-                rec["val_wave"] = float(wv[1]) / (m * eng.B * trainer.world_size)
-            if dl is not None:
-                dv = reduce_(dtot.clone())
-                rec["train_decay"] = float(dv[0]) / max(float(dv[1]), 1.0)
-                rec["val_decay"] = float(dv[2]) / max(float(dv[3]), 1.0)
-            if sl is not None:
-                sv = reduce_(stot.clone())
-                rec["train_sc"], rec["train_logmag"] = float(sv[0]) / max(float(sv[2]), 1.0), float(sv[1]) / max(float(sv[2]), 1.0)
-                rec["val_sc"], rec["val_logmag"] = float(sv[3]) / max(float(sv[5]), 1.0), float(sv[4]) / max(float(sv[5]), 1.0)
-            if has_acc:
-                acc = reduce_(atot.clone())
-                rec["train_acc"] = float(acc[0]) / (n * eng.B * trainer.world_size)
-                rec["val_acc"] = float(acc[1]) / (m * eng.B * trainer.world_size)
+        for mt in meters:          # one reduction and one read-back each, the same on every rank
+            rec.update(mt.entries(reduce_(mt.tot), steps))
         if manager is not None and epoch % 2 == 0:
             rec["checkpoint"] = manager.save(epoch=epoch)
         history.append(rec)

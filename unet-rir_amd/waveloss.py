@@ -13,12 +13,11 @@ term to the train step; the object also works on its own with any NCHW predictio
     dpred = wl(pred, wav_true)                   # fp32 [B, 2, H, W]; wl.wave_out = (sum_b E_b / D_b, sum_b E_b) on the device
     engine.backward(dpred=dpred)
 """
-import math
-
 import torch
 
 from . import ops
 from .features import HOP_LENGTH, N_FFT, STFT_SHAPE, WIN_LENGTH
+from .waveterm import set_geometry
 
 
 class WaveLoss:
@@ -27,12 +26,8 @@ class WaveLoss:
         """time_weight: per-sample weights w[t], length hop_length * (des_shape[1] - 1) (None: ones) - e.g. a step over the first 50 ms."""
         if norm not in ops.WAVE_NORMS:
             raise ValueError(f"norm must be one of {sorted(ops.WAVE_NORMS)}")
-        if not (weight >= 0.0) or not math.isfinite(weight):
-            raise ValueError("weight must be a finite number >= 0")
-        self.weight, self.norm = float(weight), norm
-        self.des_shape = (int(des_shape[0]), int(des_shape[1]))
-        self.n_fft, self.win_length, self.hop_length = int(n_fft), int(win_length), int(hop_length)
-        self.T = self.hop_length * (self.des_shape[1] - 1)
+        set_geometry(self, des_shape, n_fft, win_length, hop_length, weight=weight)
+        self.norm = norm
         if time_weight is not None:
             time_weight = (time_weight.detach().to(torch.float32).clone() if isinstance(time_weight, torch.Tensor)
                            else torch.tensor(time_weight, dtype=torch.float32)).contiguous()
