@@ -818,6 +818,44 @@ size_t unetrir_auralize_fft_ws_bytes(int B, int K, int N, long long dry_stride, 
 int unetrir_auralize_fft_f32(const float* rir, const float* dry, float* out, int B, int K, int N, long long dry_stride, int L, void* ws,
                              size_t ws_bytes, unetrir_stream_t stream);
 
+/* ---- a moving listener: dry audio rendered along a path of impulse responses by crossfaded overlap-save (auralize_fft.hip; the
+ *      formulation, the gain arithmetic and the derivation of the bound are in its header).
+ *
+ * unetrir_auralize_path_f32: rir fp32 [B][R][K] (h_{b,r}: R nodes of a path, for each of B rows that move along one schedule); times
+ * int32 [R] ON THE DEVICE (tau_r: the output sample at which the listener is at node r; may be negative or beyond L); dry, dry_stride,
+ * out fp32 [B][L], N, L as unetrir_auralize_fft_f32.  With y_{b,r} = h_{b,r} * x_b the stationary convolution and 0 <= n < L:
+ *   n <= tau_0:                out[b][n] = y_{b,0}[n]                    n >= tau_{R-1}:  out[b][n] = y_{b,R-1}[n]
+ *   tau_r <= n < tau_{r+1}:    a = (n - tau_r) / (tau_{r+1} - tau_r),    out[b][n] = (1 - a) y_{b,r}[n] + a y_{b,r+1}[n]
+ * a linear crossfade of the outputs with hat-function gains that sum to 1 (equal, being linear, to a filter interpolated per output
+ * sample); R = 1 is the stationary case.
+ * Two launches whatever B, R, N, L: (1) the spectra of the FFT form, over the B R responses and x (same packing, block P = 2048, grid
+ * anchored at n = 0, a shared x transformed once); (2) one workgroup per row and output block j, which finds from `times` the nodes
+ * whose gains touch the block (r_lo: the last with tau <= jP, else 0; r_hi: the first with tau >= (j+1)P - 1, else R - 1; indices
+ * clamped into [0, R) whatever the table holds), forms for each in ascending r the stationary form's Y_j = sum_q H_q X_{j-q}, inverse
+ * and 2^-12 scaling, and blends the samples in registers.  No intermediate y_r in memory, no atomics, nothing cleared, no host
+ * synchronisation, capturable (times is read by the second launch, at replay); every element of out written exactly once and nothing
+ * beyond it.
+ * Gains are fp32: a = float(n - tau_r) / float(tau_{r+1} - tau_r) by IEEE division, the falling gain 1 - a; a node whose gain at a
+ * sample is exactly 0 contributes nothing to it, a gain of 1 multiplies exactly; the blend is one product, then one fmaf, in ascending r.
+ * The bits of an element depend on (h_{b,.}, x_b, times, n) and the fixed block grid alone: not on the run, B, the row's place in the
+ * batch, shared or per-row x, L (a truncated call returns the head of the full result) or a larger workspace.  Wherever one node has
+ * gain 1 - n <= tau_0, n >= tau_{R-1}, every n = tau_r, all of R = 1 - they are the bits of unetrir_auralize_fft_f32 for that response.
+ * Error, with E_r[n] the bound of unetrir_auralize_fft_f32 for h_{b,r}, g_r[n] the exact gains and u = 2^-24:
+ *   |out[b][n] - sum_r g_r[n] y_{b,r}[n]| <= sum_r g_r[n] E_r[n] + 4 u sum_r g_r[n] |y_{b,r}[n]|
+ * (4: the division, the subtraction, the product and the fmaf; where a spacing is no power of two the falling gain inherits the
+ * rounding of a, at most 2^-25 |y_r[n]| more).
+ * Precondition: times strictly increasing and |tau| <= 2^30; otherwise the result is unspecified, but nothing outside out and ws is
+ * read or written.  Cost: one product chain and one inverse transform per node that touches a block - 2 to 3 times the stationary
+ * render for nodes at least P apart, more where they are denser.
+ * unetrir_auralize_path_supported(K): 1 for 1 <= K <= 16384, as the FFT form.  ws: unetrir_auralize_path_ws_bytes(B, R, K, N,
+ * dry_stride, L) bytes = 16384 (B R Q + (dry_stride ? B : 1) J), 16-byte aligned; 0 for arguments the call refuses.
+ * UNETRIR_EINVAL before the device is touched: as unetrir_auralize_fft_f32, and R < 1, a null times, more workgroups than a launch
+ * takes (B R Q + (dry_stride ? B : 1) J or B J above 2^31 - 8). */
+int unetrir_auralize_path_supported(int K);
+size_t unetrir_auralize_path_ws_bytes(int B, int R, int K, int N, long long dry_stride, int L);
+int unetrir_auralize_path_f32(const float* rir, const int* times, const float* dry, float* out, int B, int R, int K, int N,
+                              long long dry_stride, int L, void* ws, size_t ws_bytes, unetrir_stream_t stream);
+
 /* ---- scoring of generated impulse responses: the loss block of the evaluation loop (rir_generation.py:185-225) and its per-room
  *      bookkeeping (:227-290, :311-357), on the device and without a read-back.
  *

@@ -1,8 +1,10 @@
-"""Render a dry recording through impulse responses, on the device: one .wav per position (unet_rir_amd.auralize).
+"""Render a dry recording through impulse responses, on the device: one .wav per position (unet_rir_amd.auralize), or with --walk one
+.wav of a listener who moves from position to position (unet_rir_amd.auralize_path).
 
     python scripts/auralize.py --rirs RIR_DIR --dry speech.wav --out OUT_DIR
     python scripts/auralize.py --checkpoint CKPT_DIR --filters 32 --kernels 3 --data BATCH_DIR --dry speech.wav --out OUT_DIR
     python scripts/auralize.py --load SAVED_MODEL_DIR --arch aenet --synthetic 1 --dry speech.wav --out OUT_DIR [--diff-gen]
+    python scripts/auralize.py --rirs RIR_DIR --dry speech.wav --out OUT_DIR --walk 250
 
 --rirs         a directory of impulse-response .wav files (sorted by name), read by `read_wav`'s rules: --sr Hz, the first --duration
                seconds, mean removed; no resampler
@@ -14,6 +16,10 @@
 --length       full (default: N + K - 1 samples), same (N) or a number of samples
 --method       direct (default: one fma per tap on the matrix cores, exact on integer data) or fft (partitioned overlap-save: the fast
                one for long recordings, within a rounding bound instead of exact)
+--walk MS      the responses become ONE path, neighbouring positions MS milliseconds apart, the first at the start of the output: the
+               files of --rirs in sorted order, or a model's responses in the order they are generated, over all batches.  One file,
+               OUT_DIR/walk.wav; --length and --peak as without it; on the FFT form whatever --method says (MS at --sr must come to
+               at least 32 samples)
 --out          OUT_DIR/NAME.wav per position, 32-bit float at --sr: NAME is the response's file name, or b{batch}_{row} for generated ones
 --peak         scale every output file so that the loudest sample of the whole set is this (default: values as computed)
 """
@@ -103,6 +109,7 @@ def main():
     ap.add_argument("--length", default="full")
     ap.add_argument("--method", choices=("direct", "fft"), default="direct")
     ap.add_argument("--peak", type=float, default=None)
+    ap.add_argument("--walk", type=float, default=None, metavar="MS")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     generated = bool(a.load or a.checkpoint or a.data or a.synthetic)
@@ -118,7 +125,14 @@ def main():
     dry = torch.from_numpy(U.read_wav(a.dry, a.sr, (frames + 0.5) / a.sr)).to(dev)
     os.makedirs(a.out, exist_ok=True)
     rendered = []
-    for names, wav in (rir_batches(a, dev) if a.rirs else model_batches(a, dev)):
+    batches = rir_batches(a, dev) if a.rirs else model_batches(a, dev)
+    if a.walk is not None:
+        spacing = int(round(a.walk * a.sr / 1000.0))
+        path = torch.cat([wav.float() for _, wav in batches]).contiguous()                 # [R, K]: one listener, R positions
+        wet = U.auralize_path(path, dry, spacing=spacing, start=0, length=length)[0].cpu().numpy()
+        batches = []
+        rendered = [("walk", wet)]
+    for names, wav in batches:
         wet = U.auralize(wav, dry, length=length, method=a.method).cpu().numpy()
         rendered += list(zip(names, wet))
     gain = 1.0
@@ -127,6 +141,8 @@ def main():
         gain = a.peak / top if top > 0 else 1.0
     for name, w in rendered:
         write_wav(os.path.join(a.out, name + ".wav"), w * np.float32(gain), a.sr)
+    if a.walk is not None:
+        print(f"walked {path.shape[0]} positions, {spacing} samples apart")
     print(f"wrote {len(rendered)} files of {rendered[0][1].shape[0]} samples to {a.out} (dry: {frames} samples, gain {gain:.6g})")
 
 

@@ -222,6 +222,11 @@ _SIGS = {
     "unetrir_auralize_fft_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
     "unetrir_auralize_fft_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
                                            C.c_size_t, c_stream]),
+    # a moving listener: the same spectra, blended per output block along a path of responses (auralize_fft.hip)
+    "unetrir_auralize_path_supported": (C.c_int, [C.c_int]),
+    "unetrir_auralize_path_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
+    "unetrir_auralize_path_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int,
+                                            C.c_void_p, C.c_size_t, c_stream]),
     "unetrir_eval_metrics_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int,
                                            C.c_void_p, c_stream]),
     "unetrir_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),

@@ -225,9 +225,162 @@ bool af_plan(int B, int K, int N, long long dry_stride, int L, long long& Q, lon
     return nH + nX <= 0x7ffffff8LL && (long long)B * J <= 0x7ffffff8LL;          // grids are padded to a multiple of 8
 }
 
+// ---- auralize_path: a listener that moves past R responses h_0 ... h_{R-1}, node r reached at output sample tau_r (strictly increasing):
+//
+//     out[n] = sum_r g_r[n] y_r[n],   y_r = h_r * x,   g_r the hat function over the nodes: 1 at tau_r, 0 at tau_{r-1} and tau_{r+1}, linear
+//     between; g_0 = 1 for n <= tau_0 and g_{R-1} = 1 for n >= tau_{R-1}.  The gains of a sample sum to 1 and at most two are not 0.
+//
+// Launches: two.  (1) the spectra kernel above over the B R responses and x.  (2) one workgroup per row b and output block j: it finds
+// r_lo (the last node with tau <= jP, else 0) and r_hi (the first with tau >= (j+1)P - 1, else R - 1) by two bisections of `times` that
+// every thread makes alike (the outcome is clamped into [0, R) and r_hi >= r_lo whatever the table holds), and for r = r_lo ... r_hi forms
+// Y_j^(r) = sum_q H^(r)_q X_{j-q} by af_mac in ascending q from +0 - the stationary kernel's sequence of operations - runs the same inverse
+// split, inverse FFT and 2^-12 scaling in the one image, multiplies the thread's 8 samples by the node's gains and adds them up in
+// registers; one store per output sample after the last node.  No y_r reaches memory, no atomics, nothing cleared.  Forming the
+// products of two neighbouring nodes from one reading of every X_{j-q} (two accumulators) gave the same bits and measured no faster
+// for B = 1 and 27 - 41 % SLOWER for B = 8 (profiles/auralize_path.json, nodes_ab; 256 VGPRs against 228): it is not here.
+//
+// Gains, fp32, per sample n and node r, contraction off:
+//     n <  tau_r:  r = 0 ? 1 : n < tau_{r-1} ? 0 : a,          a = float(n - tau_{r-1}) / float(tau_r - tau_{r-1})   (IEEE division)
+//     n >= tau_r:  r = R - 1 ? 1 : n >= tau_{r+1} ? 0 : 1 - a,   a = float(n - tau_r) / float(tau_{r+1} - tau_r)
+// A gain of 0 adds nothing (the node is skipped for that sample); the first node that counts gives o = g y, the second o = fmaf(g, y, o),
+// in ascending r.  A gain of 1 multiplies exactly, so wherever one node has gain 1 - n <= tau_0, n >= tau_{R-1}, every n = tau_r, all of
+// R = 1 - out[n] is the bits of the stationary form for that response.
+//
+// Bits: out[b][n] depends on (h_{b,.}, x_b, times, n) alone - not on the run, B, the row's place, shared or per-row x, L or the workspace.
+//
+// Error.  With E_r[n] the stationary bound above for h_r and u = 2^-24:
+//     |out[n] - sum_r g_r[n] y_r[n]| <= sum_r g_r[n] E_r[n] + 4 u sum_r g_r[n] |y_r[n]|
+// The differences n - tau and tau' - tau are exact in fp32 below 2^24 (beyond it each conversion rounds once more, covered by the 4), so
+// a^ = a (1 + d), |d| <= u.  The rising node's term a^ y^ then carries the division, the product and the sum: 3 u.  The falling node's
+// 1 - a^ is exact for a^ >= 1/2 (Sterbenz) and rounds by u / 2 below; with the product and the sum again 3 u; 4 covers the second order.
+// The falling gain also inherits the error of a^: |a d| |y_r| <= u g_{r+1} |y_r|, at most 2^-25 |y_r| - not proportional to g_r; where
+// g_r >= 1 / 237 it is below g_r E_r itself (E_r >= 237 u |y_r|, as |y_r[n]| <= s_j), and it is 0 wherever the spacing is a power of two.
+//
+// Precondition: times strictly increasing, |tau| <= 2^30.  Otherwise the result is unspecified; nothing outside out and ws is touched.
+// Cost: one product chain (Q_j spectra of h, Q_j of x) and one inverse transform per node that touches a block.
+FL_HD float ap_gain(long long n, int r, int R, long long tp, long long tc, long long tn) {
+#pragma clang fp contract(off)
+    if (n < tc) {
+        if (r == 0) return 1.f;
+        if (n < tp) return 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __fdiv_rn((float)(n - tp), (float)(tc - tp));
+#else
+        return (float)(n - tp) / (float)(tc - tp);
+#endif
+    }
+    if (r == R - 1) return 1.f;
+    if (n >= tn) return 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return 1.f - __fdiv_rn((float)(n - tc), (float)(tn - tc));
+#else
+    return 1.f - (float)(n - tc) / (float)(tn - tc);
+#endif
+}
+
+__global__ __launch_bounds__(AF_THREADS) void auralize_path_render_kernel(const float4* __restrict__ spec, const int* __restrict__ times,
+                                                                          float* __restrict__ out, int R, int Q, int J, int L, int nH,
+                                                                          int xrows, int B) {
+#pragma clang fp contract(off)
+    __shared__ cf buf[AF_M];
+    const int t = threadIdx.x;
+    const int blk = af_block(B * J);
+    if (blk >= B * J) return;
+    const int b = blk / J, j = blk - b * J;
+    const long long n0 = (long long)j * AF_P, n1 = n0 + AF_P - 1;
+    int lo = 0, hi = R;                                 // the first node with tau > n0
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (times[mid] <= n0) lo = mid + 1; else hi = mid;
+    }
+    const int r_lo = lo > 0 ? lo - 1 : 0;
+    lo = 0, hi = R;                                     // the first node with tau >= n1
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (times[mid] < n1) lo = mid + 1; else hi = mid;
+    }
+    int r_hi = lo < R ? lo : R - 1;
+    if (r_hi < r_lo) r_hi = r_lo;
+    const size_t node_stride = (size_t)Q * (AF_M / 2);
+    const float4* __restrict__ H = spec + (size_t)b * R * node_stride;
+    const float4* __restrict__ X = spec + ((size_t)nH + (xrows > 1 ? (size_t)b * J : 0)) * (AF_M / 2);
+    float o[8];
+    unsigned have = 0;                                  // bit s: sample s of the thread has its first term
+#pragma unroll
+    for (int s = 0; s < 8; ++s) o[s] = 0.f;
+    for (int r = r_lo; r <= r_hi; ++r) {
+        cf acc[1][8];
+        af_accumulate<1>(acc, H + (size_t)r * node_stride, X, j, 0, Q, t);     // Y_j of node r: the stationary kernel's own chain
+        if (r > r_lo) __syncthreads();                  // the blend of the node before has read the image
+        af_store_acc(buf, acc[0], t);
+        __syncthreads();
+        fl_split_inv<AF_M>(buf, t, AF_THREADS);
+        __syncthreads();
+        fl_fft<AF_M, 1>(buf, t);
+        const long long tp = times[r > 0 ? r - 1 : 0], tc = times[r], tn = times[r < R - 1 ? r + 1 : r];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = t + AF_THREADS * e;
+            const cf z = buf[fl_swz(AF_M / 2 + i)];
+            const long long n = n0 + 2 * i;
+            const float y[2] = {z.x * (1.f / (2 * AF_M)), z.y * (1.f / (2 * AF_M))};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float gn = ap_gain(n + k, r, R, tp, tc, tn);
+                const unsigned bit = 1u << (2 * e + k);
+                if (gn != 0.f) {
+                    o[2 * e + k] = (have & bit) ? fmaf(gn, y[k], o[2 * e + k]) : gn * y[k];
+                    have |= bit;
+                }
+            }
+        }
+    }
+    float* __restrict__ yrow = out + (size_t)b * L;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const long long n = n0 + 2 * (t + AF_THREADS * e);
+        if (n + 1 < L && ((uintptr_t)(yrow + n) & 7) == 0) {
+            *reinterpret_cast<float2*>(yrow + n) = make_float2(o[2 * e], o[2 * e + 1]);
+        } else {
+            if (n < L) yrow[n] = o[2 * e];
+            if (n + 1 < L) yrow[n + 1] = o[2 * e + 1];
+        }
+    }
+}
+
+// af_plan for B R responses; false in addition for R < 1 and for more responses than an int counts
+bool ap_plan(int B, int R, int K, int N, long long dry_stride, int L, long long& Q, long long& J, long long& nH, long long& nX) {
+    if (B < 1 || R < 1 || (long long)B * R > 0x7fffffffLL) return false;
+    if (!af_plan(B, K, N, dry_stride, L, Q, J, nH, nX)) return false;
+    nH = (long long)B * R * Q;
+    return nH + nX <= 0x7ffffff8LL;
+}
+
 }  // namespace
 
 extern "C" {
+
+int unetrir_auralize_path_supported(int K) { return K >= 1 && K <= AF_MAXK ? 1 : 0; }
+
+size_t unetrir_auralize_path_ws_bytes(int B, int R, int K, int N, long long dry_stride, int L) {
+    long long Q, J, nH, nX;
+    return ap_plan(B, R, K, N, dry_stride, L, Q, J, nH, nX) ? (size_t)(nH + nX) * AF_SPEC : 0;
+}
+
+int unetrir_auralize_path_f32(const float* rir, const int* times, const float* dry, float* out, int B, int R, int K, int N,
+                              long long dry_stride, int L, void* ws, size_t ws_bytes, unetrir_stream_t stream) {
+    long long Q, J, nH, nX;
+    if (!rir || !times || !dry || !out || !ws || !ap_plan(B, R, K, N, dry_stride, L, Q, J, nH, nX)) return UNETRIR_EINVAL;
+    if (ws_bytes < (size_t)(nH + nX) * AF_SPEC || ((uintptr_t)ws & 15)) return UNETRIR_EINVAL;
+    float4* spec = static_cast<float4*>(ws);
+    hipLaunchKernelGGL(auralize_fft_spectra_kernel, dim3(af_grid(nH + nX)), dim3(AF_THREADS), 0, (hipStream_t)stream, rir, dry, spec, K,
+                       N, dry_stride, (int)Q, (int)J, (int)nH, (int)nX);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(auralize_path_render_kernel, dim3(af_grid((long long)B * J)), dim3(AF_THREADS), 0, (hipStream_t)stream,
+                       (const float4*)spec, times, out, R, (int)Q, (int)J, L, (int)nH, dry_stride == 0 ? 1 : B, B);
+    return (int)hipGetLastError();
+}
 
 int unetrir_auralize_fft_supported(int K) { return K >= 1 && K <= AF_MAXK ? 1 : 0; }
 

@@ -830,14 +830,16 @@ def auralize_supported(K):
     return bool(_lib.lib().unetrir_auralize_supported(int(K)))
 
 
-def _auralize_args(rir, dry, out):
-    """The tensor checks of both forms of auralize -> (B, K, N, L)"""
+def _auralize_args(rir, dry, out, path=False):
+    """The tensor checks of every form of auralize -> (B, K, N, L); path: rir is [B, R, K], R >= 1"""
     named = ((rir, "rir"), (dry, "dry"), (out, "out"))
     if not all(isinstance(t, torch.Tensor) for t, _ in named):
         raise ValueError("auralize: rir, dry and out must be tensors")
-    if rir.dim() != 2 or dry.dim() not in (1, 2) or out.dim() != 2:
-        raise ValueError("auralize: rir [B, K], dry [N] or [B, N], out [B, L]")
-    B, K = rir.shape
+    if rir.dim() != (3 if path else 2) or dry.dim() not in (1, 2) or out.dim() != 2:
+        raise ValueError(f"auralize: rir {'[B, R, K]' if path else '[B, K]'}, dry [N] or [B, N], out [B, L]")
+    B, K = rir.shape[0], rir.shape[-1]
+    if path and rir.shape[1] < 1:
+        raise ValueError("auralize: empty input: a path has at least one node")
     N, L = dry.shape[-1], out.shape[1]
     if (dry.dim() == 2 and dry.shape[0] != B) or out.shape[0] != B:
         raise ValueError(f"auralize: batch sizes differ: rir {tuple(rir.shape)}, dry {tuple(dry.shape)}, out {tuple(out.shape)}")
@@ -896,6 +898,40 @@ def auralize_fft_f32(rir, dry, out, ws: Workspace = None):
         ws.reserve(need)
     check(_lib.lib().unetrir_auralize_fft_f32(_p(rir), _p(dry), _p(out), B, K, N, stride, L, ws.ptr, ws.nbytes, _stream()),
           "auralize_fft")
+
+
+def auralize_path_supported(K):
+    """Whether `auralize_path_f32` takes impulse responses of K taps (1 <= K <= 16384)."""
+    return bool(_lib.lib().unetrir_auralize_path_supported(int(K)))
+
+
+def auralize_path_ws_bytes(B, R, K, N, dry_stride, L):
+    """Bytes `auralize_path_f32` keeps in its workspace: the spectra of the B R responses and of x (0: arguments the call refuses)."""
+    return int(_lib.lib().unetrir_auralize_path_ws_bytes(int(B), int(R), int(K), int(N), int(dry_stride), int(L)))
+
+
+def auralize_path_f32(rir, times_dev, dry, out, ws: Workspace = None):
+    """out fp32 [B, L] = dry rendered along the path of responses rir fp32 [B, R, K]: node r is reached at output sample times_dev[r]
+    (a contiguous int32 [R] tensor on the device, strictly increasing, |tau| <= 2^30 - its CONTENTS are not looked at here, so a captured
+    graph replays with whatever schedule the tensor holds then), hat-function gains between the nodes (include/unetrir.h).  dry, out
+    and ws as `auralize_fft_f32`: two launches on the current stream."""
+    B, K, N, L = _auralize_args(rir, dry, out, path=True)
+    R = rir.shape[1]
+    if (not isinstance(times_dev, torch.Tensor) or times_dev.dtype != torch.int32 or tuple(times_dev.shape) != (R,) or
+            not times_dev.is_contiguous() or times_dev.device != rir.device):
+        raise ValueError(f"auralize_path: times must be a contiguous int32 [{R}] tensor on {rir.device}")
+    if not auralize_path_supported(K):
+        raise ValueError(f"auralize: impulse responses of {K} taps are not supported (1 ... 16384)")
+    stride = 0 if dry.dim() == 1 else N
+    need = auralize_path_ws_bytes(B, R, K, N, stride, L)
+    if ws is None:
+        ws = Workspace(rir.device, need)
+    elif not isinstance(ws, Workspace) or ws.buf.device != rir.device:
+        raise ValueError(f"auralize: ws must be a Workspace on {rir.device}")
+    else:
+        ws.reserve(need)
+    check(_lib.lib().unetrir_auralize_path_f32(_p(rir), _p(times_dev), _p(dry), _p(out), B, R, K, N, stride, L, ws.ptr, ws.nbytes,
+                                               _stream()), "auralize_path")
 
 
 def griffinlim_ws_bytes(B, n_bins, n_frames, n_fft):
