@@ -125,9 +125,7 @@ def gains(times, L):
 
 def entry(lib_path):
     """unetrir_auralize_path_f32 of another build"""
-    fn = C.CDLL(lib_path).unetrir_auralize_path_f32
-    fn.restype, fn.argtypes = U._lib._SIGS["unetrir_auralize_path_f32"]
-    return fn
+    return U._lib.bind(C.CDLL(lib_path), "unetrir_auralize_path_f32")
 
 
 def nodes_ab(other, h, x, times, B, N, a):

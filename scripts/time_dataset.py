@@ -44,9 +44,7 @@ def abl_gather():
         U.build.build_ablations()
     L = C.CDLL(lib)
     L.unetrir_abl_set(16384)
-    f = L.unetrir_gather_batch_f32
-    f.restype, f.argtypes = U._lib._SIGS["unetrir_gather_batch_f32"]
-    return f
+    return U._lib.bind(L, "unetrir_gather_batch_f32")
 
 
 def count_launches(fn):

@@ -14,7 +14,7 @@ _src = [os.path.join(U.build.CSRC, f) for f in os.listdir(U.build.CSRC)]
 if not os.path.exists(U.build.ABL_LIB) or any(os.path.getmtime(s) > os.path.getmtime(U.build.ABL_LIB) for s in _src):
     U.build.build_ablations()
 A = C.CDLL(U.build.ABL_LIB); A.unetrir_abl_set(16384)
-fa = A.unetrir_gather_batch_f32; fa.restype, fa.argtypes = U._lib._SIGS["unetrir_gather_batch_f32"]
+fa = U._lib.bind(A, "unetrir_gather_batch_f32")
 fn_ = L.unetrir_gather_batch_f32
 g = torch.Generator(device=DEV).manual_seed(1)
 bank = torch.rand((N, 2, H, W), device=DEV, generator=g)

@@ -1,361 +1,106 @@
-"""ctypes binding of libunetrir.so (the C ABI declared in include/unetrir.h).
+"""ctypes binding of libunetrir.so, derived from include/unetrir.h when this module is imported.
+
+The header is the one place where the C ABI is written down: its function declarations become `FUNCS` (restype, argtypes and
+parameter names), its `typedef struct`s the ctypes mirrors (ConvGeom, Config, CastDesc, ReduceDesc, LambSeg) and its integer
+`#define UNETRIR_<NAME>`s `CONSTS`.  A new entry point is declared there and wrapped in ops.py; nothing is repeated here.
+
+Type rule: a scalar (`_SCALARS`) is its ctypes twin; a pointer to a struct of the header is POINTER(mirror); every other pointer is
+c_void_p, because device addresses travel as integers.  The parameters for which host and device differ from that rule are listed in
+`_EXCEPTIONS`, by function and parameter name, and nowhere else.  Whatever the rule cannot map raises at import and names the offender.
 
 There is no CPU fallback: if the library is missing or a call fails, this raises.
 """
 import ctypes as C
+import functools
 import os
+import re
 
 from . import build as _build
-
-_LIB = None
-
-c_f32p = C.c_void_p   # device pointers travel as integers
-c_stream = C.c_void_p
-
-
-class CastDesc(C.Structure):
-    """unetrir_cast_desc (include/unetrir.h)."""
-    _fields_ = [("w", C.c_void_p), ("same", C.c_void_p), ("transposed", C.c_void_p), ("N", C.c_int), ("T", C.c_int), ("C", C.c_int),
-                ("Cp", C.c_int), ("Np", C.c_int), ("reserved", C.c_int), ("packed_s2", C.c_void_p)]
-
-
-class ReduceDesc(C.Structure):
-    """unetrir_reduce_desc (include/unetrir.h): one deferred split-K reduction."""
-    _fields_ = [("part", C.c_void_p), ("nsplit", C.c_int), ("n", C.c_size_t), ("out", C.c_void_p), ("reg", C.c_float), ("w", C.c_void_p)]
-
-
-class LambSeg(C.Structure):
-    """unetrir_lamb_seg (include/unetrir.h): one variable of the LAMB segment table."""
-    _fields_ = [("offset", C.c_longlong), ("count", C.c_longlong), ("slot", C.c_longlong), ("flags", C.c_int), ("chunk0", C.c_int)]
-
-
-class Config(C.Structure):
-    """unetrir_config: kernel-selection switches (include/unetrir.h)."""
-    _fields_ = [(n, C.c_int) for n in ("conv3x3", "conv3x3g", "conv3x3g_pair", "conv3x3h", "conv3x3s", "conv3x3r", "stem",
-                                       "upconv3x3g", "wgrad3x3g", "wgrad3x3r", "head_mfma", "wgrad3x3d", "conv3x3d", "conv3x3p", "upconv3x3q", "dyn_tiles", "pw1x1", "igemm2")]
-
-
-class ConvGeom(C.Structure):
-    """unetrir_conv_geom"""
-    _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
-                ("k", C.c_int), ("stride", C.c_int)]
-
-
-_SIGS = {
-    "unetrir_abi_version": (C.c_int, []),
-    "unetrir_get_config": (C.c_int, [C.POINTER(Config)]),
-    "unetrir_set_config": (C.c_int, [C.POINTER(Config)]),
-    "unetrir_conv2d_fwd_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int,
-                                         c_f32p, C.c_int, c_stream]),
-    "unetrir_conv2d_dgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p,
-                                           C.c_int, c_stream]),
-    "unetrir_conv2d_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
-    "unetrir_conv2d_wgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float,
-                                           c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_conv2d_transpose_fwd_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p,
-                                                   C.c_int, c_stream]),
-    "unetrir_conv2d_transpose_dgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int,
-                                                     c_f32p, C.c_int, c_stream]),
-    "unetrir_conv2d_transpose_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
-    "unetrir_conv2d_transpose_wgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p,
-                                                     C.c_float, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_dense_fwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "unetrir_dense_fwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_transpose_weight_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
-    "unetrir_bn_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int]),
-    "unetrir_bn_stats_f32": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_float, C.c_float,
-                                       c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_bn_apply_f32": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int,
-                                       c_stream]),
-    "unetrir_bn_bwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, c_f32p,
-                                     C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_colsum_f32": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_void_p, C.c_size_t,
-                                     c_stream]),
-    "unetrir_relu_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_relu_bwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_int,
-                                       c_stream]),
-    "unetrir_bn_act_add_f32": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p,
-                                         C.c_int, c_stream]),
-    "unetrir_act_bwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, C.c_int, c_f32p, C.c_int,
-                                      c_stream]),
-    "unetrir_add_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_longlong, c_stream]),
-    "unetrir_nchw_to_nhwc_pad_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
-                                               c_stream]),
-    "unetrir_head6x6_supported": (C.c_int, [C.c_int]),
-    "unetrir_head6x6_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p,
-                                          C.c_int, c_stream]),
-    "unetrir_head6x6_wgrad_ws_bytes": (C.c_size_t, [C.c_int]),
-    "unetrir_head6x6_wgrad_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p,
-                                            C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_loss_ws_bytes": (C.c_size_t, [C.c_longlong]),
-    "unetrir_sigmoid_loss_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                           c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_sigmoid_nchw_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_sigmoid_bwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_embedding_fwd_f32": (C.c_int, [C.c_void_p, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_embedding_bwd_f32": (C.c_int, [C.c_void_p, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_mul_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_longlong, c_stream]),
-    "unetrir_sumsq_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_float, c_f32p, C.c_int, C.c_void_p, C.c_size_t,
-                                    c_stream]),
-    "unetrir_adam_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_longlong, C.c_float, C.c_float, C.c_float,
-                                   C.c_float, C.c_float, c_stream]),
-    # ---- bf16-storage variants (same argument lists; pointers are void*) ----
-    "unetrir_conv2d_fwd_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int,
-                                          c_f32p, C.c_int, c_stream]),
-    "unetrir_conv3x3s2_packed_elems": (C.c_size_t, [C.c_int, C.c_int]),
-    "unetrir_conv2d_fwd_packed_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int,
-                                                 c_f32p, C.c_int, c_stream]),
-    "unetrir_conv2d_transpose_dgrad_packed_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int,
-                                                             c_f32p, C.c_int, c_stream]),
-    "unetrir_conv2d_dgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p,
-                                            C.c_int, c_stream]),
-    "unetrir_conv2d_wgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float,
-                                            c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_conv2d_transpose_fwd_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p,
-                                                    C.c_int, c_stream]),
-    "unetrir_conv2d_transpose_dgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int,
-                                                      c_f32p, C.c_int, c_stream]),
-    "unetrir_conv2d_wgrad_partials_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float, c_f32p,
-                                                     C.c_void_p, C.c_size_t, C.POINTER(ReduceDesc), c_stream]),
-    "unetrir_conv2d_transpose_wgrad_partials_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float,
-                                                               c_f32p, C.c_void_p, C.c_size_t, C.POINTER(ReduceDesc), c_stream]),
-    "unetrir_splitk_reduce_batched": (C.c_int, [C.POINTER(ReduceDesc), C.c_int, c_stream]),
-    "unetrir_conv2d_transpose_wgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p,
-                                                      C.c_float, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    # the 2x2 stride-2 layers (conv2x2.hip): the argument lists of their unetrir_conv2d_* twins
-    "unetrir_conv2x2s2_supported_bf16": (C.c_int, [C.POINTER(ConvGeom), C.c_int, C.c_int]),
-    "unetrir_conv2x2s2_transpose_supported_bf16": (C.c_int, [C.POINTER(ConvGeom), C.c_int, C.c_int]),
-    "unetrir_conv2x2s2_fwd_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int,
-                                             c_stream]),
-    "unetrir_conv2x2s2_dgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_conv2x2s2_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
-    "unetrir_conv2x2s2_wgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float, c_f32p,
-                                               C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_conv2x2s2_wgrad_partials_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float, c_f32p,
-                                                        C.c_void_p, C.c_size_t, C.POINTER(ReduceDesc), c_stream]),
-    "unetrir_conv2x2s2_transpose_fwd_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_stream]),
-    "unetrir_conv2x2s2_transpose_dgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int,
-                                                         c_stream]),
-    "unetrir_conv2x2s2_transpose_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
-    "unetrir_conv2x2s2_transpose_wgrad_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float, c_f32p,
-                                                         C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_conv2x2s2_transpose_wgrad_partials_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_float,
-                                                                  c_f32p, C.c_void_p, C.c_size_t, C.POINTER(ReduceDesc), c_stream]),
-    "unetrir_cast_weight_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
-    "unetrir_transpose_cast_weight_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
-    "unetrir_bn_stats_bf16": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_float, C.c_float,
-                                        c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_bn_apply_bf16": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int,
-                                        c_stream]),
-    "unetrir_bn_bwd_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p,
-                                      C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_colsum_bf16": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_void_p, C.c_size_t,
-                                      c_stream]),
-    "unetrir_relu_bwd_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_int,
-                                        c_stream]),
-    "unetrir_nchw_to_nhwc_pad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
-                                                c_stream]),
-    "unetrir_head6x6_fwd_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p,
-                                           C.c_int, c_stream]),
-    "unetrir_head6x6_wgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
-                                             c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_stem_composite_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_stem_composite_ws_bytes": (C.c_size_t, [C.c_int]),
-    "unetrir_stem_composite_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_float, c_f32p,
-                                              c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_stage_h2d": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), c_stream]),
-    "unetrir_conv2d_colstat_rows_bf16": (C.c_longlong, [C.POINTER(ConvGeom), C.c_int, C.c_int]),
-    "unetrir_conv3x3_kernel_id_bf16": (C.c_int, [C.POINTER(ConvGeom), C.c_int, C.c_int]),
-    "unetrir_conv2d_fwd_colstat_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int,
-                                                  c_f32p, c_stream]),
-    "unetrir_conv2d_dgrad_colstat_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int,
-                                                    c_f32p, c_stream]),
-    "unetrir_conv2d_transpose_colstat_rows_bf16": (C.c_longlong, [C.POINTER(ConvGeom), C.c_int]),
-    "unetrir_conv2d_transpose_fwd_colstat_bf16": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p,
-                                                            c_stream]),
-    "unetrir_bn_stats_colstat": (C.c_int, [c_f32p, C.c_longlong, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_float, C.c_float,
-                                           c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "unetrir_bn_colstat_act_add_f32": (C.c_int, [c_f32p, C.c_longlong, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_bn_colstat_act_add_bf16": (C.c_int, [c_f32p, C.c_longlong, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_colsum_colstat": (C.c_int, [c_f32p, C.c_longlong, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_cast_weights_batched_bf16": (C.c_int, [C.c_void_p, C.c_int, c_stream]),
-    "unetrir_dense_dgrad_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "unetrir_dense_dgrad_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "unetrir_dense_dgrad_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
-                                          c_stream]),
-    "unetrir_stft_frames": (C.c_int, [C.c_int, C.c_int]),
-    "unetrir_stft_features_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            c_f32p, C.c_int, C.c_int, c_stream]),
-    "unetrir_istft_features_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, c_f32p, c_stream]),
-    # waveform-domain loss and its gradient on the prediction (waveloss.hip)
-    "unetrir_wave_loss_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "unetrir_wave_loss_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_double, C.c_double, c_f32p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p,
-                                        C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    # the vector-Jacobian product of PostProcess (istft_bwd.hip) and the loss on the energy decay curve (decayloss.hip)
-    "unetrir_istft_features_bwd_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_decay_loss_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "unetrir_decay_loss_supported": (C.c_int, [C.c_int]),
-    "unetrir_decay_loss_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, c_f32p, C.c_void_p,
-                                         c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    # the multi-resolution STFT loss on the waveform (spectralloss.hip); res is a host array of 3 R ints
-    "unetrir_spectral_loss_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_spectral_loss_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
-    "unetrir_spectral_loss_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double,
-                                            C.c_double, C.c_double, C.c_double, C.c_int, c_f32p, C.c_void_p, c_f32p, C.c_void_p,
-                                            C.c_size_t, c_stream]),
-    # the same loss with fp32 FFTs in LDS (spectralloss_fft.hip)
-    "unetrir_spectral_loss_fft_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_spectral_loss_fft_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
-    "unetrir_spectral_loss_fft_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double,
-                                                C.c_double, C.c_double, C.c_double, C.c_int, c_f32p, C.c_void_p, c_f32p, C.c_void_p,
-                                                C.c_size_t, c_stream]),
-    # y = h * x on the fp32 matrix cores (auralize.hip)
-    "unetrir_auralize_supported": (C.c_int, [C.c_int]),
-    "unetrir_auralize_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, c_stream]),
-    # the same by partitioned overlap-save, FFTs in LDS (auralize_fft.hip)
-    "unetrir_auralize_fft_supported": (C.c_int, [C.c_int]),
-    "unetrir_auralize_fft_block": (C.c_int, [C.c_int]),
-    "unetrir_auralize_fft_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
-    "unetrir_auralize_fft_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
-                                           C.c_size_t, c_stream]),
-    # a moving listener: the same spectra, blended per output block along a path of responses (auralize_fft.hip)
-    "unetrir_auralize_path_supported": (C.c_int, [C.c_int]),
-    "unetrir_auralize_path_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
-    "unetrir_auralize_path_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int,
-                                            C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_eval_metrics_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int,
-                                           C.c_void_p, c_stream]),
-    "unetrir_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
-    # room-acoustic figures (acoustics.hip)
-    "unetrir_acoustic_figures_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
-                                               c_stream]),
-    "unetrir_acoustic_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, c_stream]),
-    "unetrir_head6x6_dgrad_supported": (C.c_int, [C.c_int, C.c_int]),
-    "unetrir_head6x6_dgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int,
-                                             c_stream]),
-    "unetrir_sigmoid_loss_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                            c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_sigmoid_bwd_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_add_f32_to_bf16": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_longlong, c_stream]),
-    "unetrir_cast_bf16_to_f32": (C.c_int, [c_f32p, c_f32p, C.c_longlong, c_stream]),
-    "unetrir_cast_f32_to_bf16": (C.c_int, [c_f32p, c_f32p, C.c_longlong, c_stream]),
-    "unetrir_bn_act_add_bf16": (C.c_int, [c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p,
-                                          C.c_int, c_stream]),
-    "unetrir_act_bwd_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, C.c_int, c_f32p, C.c_int,
-                                       c_stream]),
-    "unetrir_bn_inference_affine_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, C.c_int, c_f32p, c_stream]),
-    "unetrir_dropout_mask_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_float, C.c_ulonglong, C.c_ulonglong, c_stream]),
-    "unetrir_index_to_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, c_stream]),
-    "unetrir_reset_tile_tickets": (C.c_int, []),
-    "unetrir_bn_bwd_junction_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_bn_bwd_junction_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_longlong, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_sigmoid_loss_ex_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                              c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_sigmoid_loss_ex_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                               c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_relu1_loss_ex_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                            c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_relu1_loss_ex_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                             c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_relu1_nchw_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_relu1_bwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_relu1_bwd_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_linear_loss_ex_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                             c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_linear_loss_ex_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                              c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_linear_nchw_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_linear_bwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_linear_bwd_bf16": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    # Conv2D(2, (1, 1)) head of DiffUNet on a bf16 trunk (head1x1.hip)
-    "unetrir_head1x1_supported": (C.c_int, [C.c_int]),
-    "unetrir_head1x1_fwd_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_stream]),
-    "unetrir_head1x1_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_head1x1_bwd_bf16": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int,
-                                           c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    # UpSampling2D((2, 2)) -> Conv2D(2, (6, 6)) head of the half-resolution U-Net, folded to the coarse grid (head_up2.hip)
-    "unetrir_head_up2_supported_f32": (C.c_int, [C.c_int]),
-    "unetrir_head_up2_supported_bf16": (C.c_int, [C.c_int]),
-    "unetrir_head_up2_fold": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_head_up2_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_stream]),
-    "unetrir_head_up2_fwd_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_stream]),
-    "unetrir_head_up2_dgrad_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_head_up2_dgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_head_up2_wgrad_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_head_up2_wgrad_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_void_p,
-                                             C.c_size_t, c_stream]),
-    "unetrir_head_up2_wgrad_bf16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_void_p,
-                                              C.c_size_t, c_stream]),
-    "unetrir_sgd_f32": (C.c_int, [c_f32p, c_f32p, C.c_longlong, C.c_float, C.c_float, c_stream]),
-    "unetrir_nadam_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                    C.c_float, C.c_float, C.c_float, c_stream]),
-    "unetrir_step_advance": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, c_stream]),
-    "unetrir_adam_dev_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_longlong, c_f32p, c_stream]),
-    "unetrir_dropout_mask_dev_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_float, C.c_ulonglong, C.c_void_p, C.c_ulonglong, c_stream]),
-    "unetrir_normal_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_ulonglong, c_stream]),
-    "unetrir_normal_dev_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_void_p, C.c_ulonglong, c_stream]),
-    "unetrir_vae_sample_kl_fwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_float, c_f32p, C.c_int,
-                                                c_f32p, c_stream]),
-    "unetrir_vae_sample_kl_bwd_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                                c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_vae_loss_add_f32": (C.c_int, [c_f32p, c_f32p, c_stream]),
-    "unetrir_vq_ws_bytes": (C.c_size_t, []),
-    "unetrir_vq_fwd_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_float, C.c_float, C.c_void_p,
-                                     c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_vq_bwd_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, c_f32p, C.c_int, c_f32p, C.c_int,
-                                     C.c_float, C.c_float, c_f32p, C.c_int, c_f32p, c_stream]),
-    "unetrir_gather_batch_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, c_f32p, C.c_longlong, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_int, c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, c_stream]),
-    "unetrir_griffinlim_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_griffinlim_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, C.c_int, C.c_float, c_f32p, C.c_ulonglong, C.c_ulonglong, c_f32p, C.c_void_p,
-                                         C.c_size_t, c_stream]),
-    "unetrir_uniform_f32": (C.c_int, [c_f32p, C.c_longlong, C.c_ulonglong, C.c_ulonglong, c_stream]),
-    "unetrir_griffinlim_fft_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_griffinlim_fft_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "unetrir_griffinlim_fft_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, C.c_int, C.c_float, c_f32p, C.c_ulonglong, C.c_ulonglong, c_f32p, C.c_void_p,
-                                             C.c_size_t, c_stream]),
-    # tfa.optimizers.LAMB (lamb.hip)
-    "unetrir_lamb_chunk_elems": (C.c_int, []),
-    "unetrir_lamb_table_init": (C.c_longlong, [C.POINTER(LambSeg), C.c_int, C.c_void_p, C.c_longlong]),
-    "unetrir_lamb_ws_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
-    "unetrir_lamb_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(LambSeg), C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
-                                   C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                   C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_lamb_dev_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.POINTER(LambSeg), C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
-                                       C.c_longlong, C.c_float, C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    # the room classifier deep_CNN (cnn_clas.hip): 'valid' 3x3 convolution, average / global pooling, softmax + cross-entropy
-    "unetrir_conv3x3_valid_fwd_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_conv3x3_valid_dgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int,
-                                                  c_stream]),
-    "unetrir_conv3x3_valid_wgrad_ws_bytes": (C.c_size_t, [C.POINTER(ConvGeom)]),
-    "unetrir_conv3x3_valid_wgrad_f32": (C.c_int, [C.POINTER(ConvGeom), c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p,
-                                                  c_f32p, C.c_void_p, C.c_size_t, c_stream]),
-    "unetrir_avgpool2_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_stream]),
-    "unetrir_avgpool2_bwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_gap_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_stream]),
-    "unetrir_gap_bwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_softmax_ce_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, C.c_int, c_f32p, c_f32p,
-                                         c_stream]),
-    "unetrir_softmax_fwd_f32": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
-    "unetrir_softmax_bwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, c_f32p, C.c_int, c_stream]),
-    "unetrir_prof_enable": (C.c_int, [C.c_int]),
-    "unetrir_prof_collect": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-}
-
-EXPORTS = tuple(_SIGS)
-PROF_FAMILIES = 8
 
 
 class UnetrirError(RuntimeError):
     pass
 
 
+_SCALARS = {"int": C.c_int, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "float": C.c_float,
+            "double": C.c_double, "size_t": C.c_size_t, "unetrir_stream_t": C.c_void_p}
+
+_EXCEPTIONS = {                                                     # (function, parameter): host arrays, and device-resident structs
+    **{("unetrir_stage_h2d", p): C.POINTER(C.c_void_p) for p in ("src", "pinned", "dev")},
+    ("unetrir_stage_h2d", "bytes"): C.POINTER(C.c_size_t),
+    **{(f"unetrir_spectral_loss{form}", "res"): C.POINTER(C.c_int)   # a host array of 3 R ints
+       for form in ("_ws_bytes", "_f32", "_fft_ws_bytes", "_fft_f32")},
+    ("unetrir_prof_collect", "counts"): C.POINTER(C.c_int),
+    ("unetrir_prof_collect", "ms"): C.POINTER(C.c_double),
+    ("unetrir_prof_collect", "flops"): C.POINTER(C.c_double),
+    ("unetrir_lamb_f32", "segs"): C.c_void_p,                       # the table in device memory (segs_host follows the rule)
+    ("unetrir_lamb_dev_f32", "segs"): C.c_void_p,
+    ("unetrir_cast_weights_batched_bf16", "desc"): C.c_void_p,      # descriptors in device memory
+}
+
+
+_DECL = re.compile(r"([^,]*[\s*])(\w+(?:\s*,\s*\w+)*)", re.S)       # type, then a name (a struct field: or a comma list of names)
+
+
+@functools.lru_cache(None)                                          # 1700 parameters, a few hundred distinct spellings
+def _decl(text):
+    """'const unetrir_bf16* const* w' -> ('unetrir_bf16', 2, ['w']): base type, pointer depth, names.  None: cannot be mapped."""
+    m = _DECL.fullmatch(text)
+    base, stars = (" ".join(re.sub(r"\bconst\b|\*", " ", m.group(1)).split()), m.group(1).count("*")) if m else ("", 0)
+    return (base, stars, re.split(r"\s*,\s*", m.group(2))) if stars or base in _SCALARS else None
+
+
+def parse_header(text, exceptions=None):
+    """(funcs, structs, consts) of a header text: funcs[name] = (restype, [argtypes], [parameter names]); structs[C name] = a
+    ctypes.Structure named in CamelCase without the prefix; consts[NAME] = int for every `#define UNETRIR_NAME <integer>`."""
+    exceptions = dict(exceptions or {})
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+UNETRIR_(\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$",
+                                                  text, re.M)}
+    structs = {}
+    for m in re.finditer(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(unetrir_\w+)\s*;", text):
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+            d = _decl(decl)
+            if d is None:
+                raise UnetrirError(f"include/unetrir.h: struct {m.group(2)}: cannot map the field declaration '{decl}'")
+            base, stars, names = d
+            fields += [(n, C.c_void_p if stars else _SCALARS[base]) for n in names]
+        py_name = "".join(w.capitalize() for w in m.group(2).split("_")[1:])
+        structs[m.group(2)] = type(py_name, (C.Structure,), {"_fields_": fields, "__doc__": f"{m.group(2)} (include/unetrir.h)"})
+    if len(structs) != len(re.findall(r"\btypedef\s+struct\b", text)):
+        raise UnetrirError(f"include/unetrir.h: a typedef struct beside {sorted(structs)} did not parse")
+    funcs = {}
+    for m in re.finditer(r"^((?:\w+[ \t]+)+)(unetrir_\w+)\s*\(([^()]*)\)\s*;", text, re.M):
+        ret, name, params = " ".join(m.group(1).split()), m.group(2), m.group(3).strip()
+        if ret not in _SCALARS:
+            raise UnetrirError(f"include/unetrir.h: {name}: cannot map the return type '{ret}'")
+        argtypes, argnames = [], []
+        for p in ([] if params in ("", "void") else params.split(",")):
+            d = _decl(p.strip())
+            if d is None:
+                raise UnetrirError(f"include/unetrir.h: {name}: cannot map the parameter '{p.strip()}'")
+            base, stars, (pname,) = d
+            rule = C.POINTER(structs[base]) if stars == 1 and base in structs else C.c_void_p if stars else _SCALARS[base]
+            argtypes.append(exceptions.pop((name, pname), rule))
+            argnames.append(pname)
+        funcs[name] = (_SCALARS[ret], argtypes, argnames)
+    unparsed = sorted(set(re.findall(r"\b(unetrir_\w+)\s*\(", text)) - set(funcs))
+    if unparsed:
+        raise UnetrirError(f"include/unetrir.h: no binding could be derived for {unparsed}")
+    if exceptions:
+        raise UnetrirError(f"_lib._EXCEPTIONS names what include/unetrir.h does not declare: {sorted(exceptions)}")
+    return funcs, structs, consts
+
+
+with open(_build.HEADER) as _f:
+    FUNCS, _STRUCTS, CONSTS = parse_header(_f.read(), _EXCEPTIONS)
+ConvGeom, Config, CastDesc, ReduceDesc, LambSeg = (_STRUCTS["unetrir_" + n] for n in ("conv_geom", "config", "cast_desc", "reduce_desc",
+                                                                                     "lamb_seg"))
+EXPORTS = tuple(FUNCS)
+ABI_VERSION, EINVAL, PROF_FAMILIES = CONSTS["ABI_VERSION"], CONSTS["EINVAL"], CONSTS["PROF_FAMILIES"]
+
+_LIB = None
 _LIB_PATH = None
 
 
@@ -365,6 +110,13 @@ def use_library(path):
     if _LIB is not None:
         raise UnetrirError("the library is already loaded")
     _LIB_PATH = path
+
+
+def bind(L, name):
+    """Give export `name` of the loaded library L the header's restype and argtypes."""
+    fn = getattr(L, name)      # AttributeError if the export is missing: fail loudly
+    fn.restype, fn.argtypes = FUNCS[name][:2]
+    return fn
 
 
 def lib():
@@ -378,11 +130,9 @@ def lib():
     if not os.path.exists(path):
         raise UnetrirError(f"HIP extension missing: {path}")
     L = C.CDLL(path)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(L, name)      # AttributeError if the export is missing: fail loudly
-        fn.restype = res
-        fn.argtypes = args
-    if L.unetrir_abi_version() != 1:
+    for name in EXPORTS:
+        bind(L, name)
+    if L.unetrir_abi_version() != ABI_VERSION:
         raise UnetrirError("libunetrir.so ABI version mismatch")
     _LIB = L
     return L

@@ -271,7 +271,7 @@ def conv2d_transpose_wgrad(g, x: Act, dy: Act, dw, ws: Workspace, reg=0.0, w=Non
 
 # ---- the 2x2 stride-2 layers (dl_models/ae_net.py:273-279, :301-307; csrc/conv2x2.hip): same arguments as the conv2d_* twins
 
-C22_FWD, C22_DGRAD, C22_WGRAD = 1, 2, 4
+C22_FWD, C22_DGRAD, C22_WGRAD = (_lib.CONSTS[n] for n in ("C22_FWD", "C22_DGRAD", "C22_WGRAD"))
 
 
 def conv2x2s2_supported(g, x: Act, y: Act, transpose=False):
@@ -1265,7 +1265,7 @@ def adam_dev(theta, g, m, v, hyper):
 
 # ---- tfa.optimizers.LAMB (trainer.py:37-38; csrc/lamb.hip) ---------------------------------------------
 
-LAMB_DECAY, LAMB_ADAPT = 1, 2
+LAMB_DECAY, LAMB_ADAPT = _lib.CONSTS["LAMB_DECAY"], _lib.CONSTS["LAMB_ADAPT"]
 
 
 def lamb_chunk_elems():
