@@ -856,6 +856,39 @@ size_t unetrir_auralize_path_ws_bytes(int B, int R, int K, int N, long long dry_
 int unetrir_auralize_path_f32(const float* rir, const int* times, const float* dry, float* out, int B, int R, int K, int N,
                               long long dry_stride, int L, void* ws, size_t ws_bytes, unetrir_stream_t stream);
 
+/* ---- sample-rate conversion: a polyphase Kaiser-windowed sinc filter (resample.hip; the table is built on the host by
+ *      resample_table.h, the tiling is in the former's header).
+ *
+ * The ratio rate_out / rate_in reduced to L / M (gcd 1), `zeros` zero crossings Z to each side, a rolloff and a Kaiser beta.  With
+ * C = Z max(L, M), s = rolloff min(1, L / M) and W = C / L:
+ *   h(tau) = s sinc(s tau) I0(beta sqrt(1 - (tau / W)^2)) / I0(beta)   for |tau| < W, else 0        (sinc(u) = sin(pi u) / (pi u))
+ *   y[m] = sum_n h(m M / L - n) x[n]        0 <= m < ceil(N L / M),   x[n] = 0 outside 0 <= n < N
+ * (librosa's output length, zero extension, gain 1 at DC both ways, exact phase: every phase is evaluated at its own argument).
+ * The table fp32 [L][T], D = ceil(C / L), T = 2 D:  table[p][i] = h((p - (i - D + 1) L) / L), each entry evaluated in fp64 (I0: its
+ * power series to convergence) and rounded once, exactly 0 outside the support (the integer test |p - (i - D + 1) L| < C); then
+ *   y[m] = sum_{i=0}^{T-1} table[p][i] x[q - D + 1 + i]        (q, p) = divmod(m M, L).
+ * unetrir_resample_supported(L, M, zeros): 1 for gcd(L, M) = 1, 1 <= L, M <= 2048, 1 <= zeros <= 64, T <= 8192 and L T <= 2^20, else 0.
+ * unetrir_resample_taps: T (0: not supported).  unetrir_resample_out_length: ceil(N L / M) (0: an argument < 1, or beyond 2^62).
+ * unetrir_resample_table_f32: table is a HOST array of L T floats; UNETRIR_EINVAL (nothing written) for a null table, an unsupported
+ * (L, M, zeros), rolloff outside (0, 1] or beta outside [0, 32].
+ *
+ * unetrir_resample_f32: x fp32 [B][N], table fp32 [L][T] in DEVICE memory, out fp32 [B][Nout], 1 <= Nout <= ceil(N L / M) - a shorter
+ * Nout returns the head of the full result.  The kernel does not interpret the table: T is even, the window of output m starts at
+ * x[q - T/2 + 1], and any table may be passed.  One launch on the given stream: no workspace, no atomics, nothing cleared, no host
+ * synchronisation (capturable); every element of out is written and nothing else.  Each output is ONE fp32 chain in ascending i from +0,
+ *   y[m] = fmaf(table[p][T-1], x[q + T/2], ... fmaf(table[p][0], x[q - T/2 + 1], +0) ...),     x[n] = +0 outside the signal,
+ * contraction off, so the bits of an element depend on (x_b, table, L, M, T, m) alone: not on the run, B, the row's place in the batch,
+ * Nout or the tiling; on integer data whose partial sums stay below 2^24 the result is exact.  Inputs are taken to be finite.
+ * UNETRIR_EINVAL before the device is touched: a null pointer; B, N or Nout < 1; Nout beyond ceil(N L / M); T odd, < 2 or > 8192;
+ * gcd(L, M) != 1, L or M outside 1 ... 2048, L T > 2^20; N > 2^49 or B max(N, Nout) > 2^60 (index arithmetic stays within 63 bits);
+ * more than 2^31 - 1 workgroups. */
+int unetrir_resample_supported(int L, int M, int zeros);
+int unetrir_resample_taps(int L, int M, int zeros);
+long long unetrir_resample_out_length(long long N, int L, int M);
+int unetrir_resample_table_f32(float* table, int L, int M, int zeros, double rolloff, double beta);
+int unetrir_resample_f32(const float* x, const float* table, float* out, int B, long long N, int L, int M, int T, long long Nout,
+                         unetrir_stream_t stream);
+
 /* ---- scoring of generated impulse responses: the loss block of the evaluation loop (rir_generation.py:185-225) and its per-room
  *      bookkeeping (:227-290, :311-357), on the device and without a read-back.
  *

@@ -7,12 +7,15 @@
     python scripts/auralize.py --rirs RIR_DIR --dry speech.wav --out OUT_DIR --walk 250
 
 --rirs         a directory of impulse-response .wav files (sorted by name), read by `read_wav`'s rules: --sr Hz, the first --duration
-               seconds, mean removed; no resampler
+               seconds, mean removed; files at another rate need --resample
 --load / --checkpoint / --arch / --filters / --kernels / --latent / --height / --width
                a model, as scripts/evaluate.py takes it; its responses are generated from --data (a directory of .npz batches with
                spec_in and emb, as scripts/evaluate.py reads them) or --synthetic N batches, and reconstructed by PostProcess
                (--diff-gen: the predicted phase is a difference to the input's)
---dry          the dry recording: a .wav file at --sr, read whole by the same rules (channels averaged, mean removed)
+--dry          the dry recording: a .wav file, read whole by the same rules (channels averaged, mean removed); at --sr, or at any
+               rate with --resample
+--resample     none (default: a file that is not at --sr is an error), kaiser_best or kaiser_fast: --dry and --rirs files at another
+               rate are converted to --sr on the device (unet_rir_amd.Resampler; the names are librosa's res_type)
 --length       full (default: N + K - 1 samples), same (N) or a number of samples
 --method       direct (default: one fma per tap on the matrix cores, exact on integer data) or fft (partitioned overlap-save: the fast
                one for long recordings, within a rounding bound instead of exact)
@@ -39,24 +42,25 @@ from unet_rir_amd.features import PostProcess
 
 
 def wav_frames(path):
-    """Frames in a RIFF/WAVE file, from its 'fmt ' and 'data' chunks."""
+    """(frames, rate) of a RIFF/WAVE file, from its 'fmt ' and 'data' chunks."""
     with open(path, "rb") as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
             raise SystemExit(f"{path}: not a RIFF/WAVE file")
-        align = None
+        align = rate = None
         while True:
             ck = f.read(8)
             if len(ck) < 8:
                 raise SystemExit(f"{path}: no data chunk")
             name, size = struct.unpack("<4sI", ck)
             if name == b"fmt ":
-                align = struct.unpack("<HHIIHH", f.read(16))[4]
+                fmt = struct.unpack("<HHIIHH", f.read(16))
+                rate, align = fmt[2], fmt[4]
                 f.seek(size - 16 + (size & 1), 1)
             elif name == b"data":
                 if not align:
                     raise SystemExit(f"{path}: data before fmt")
-                return size // align
+                return size // align, rate
             else:
                 f.seek(size + (size & 1), 1)
 
@@ -67,7 +71,7 @@ def rir_batches(a, dev):
         raise SystemExit(f"no .wav files in {a.rirs}")
     for i in range(0, len(files), a.batch):
         part = files[i:i + a.batch]
-        wav = np.stack([U.read_wav(f, a.sr, a.duration) for f in part])
+        wav = np.stack([U.read_wav(f, a.sr, a.duration, resample=a.resample) for f in part])
         yield [os.path.splitext(os.path.basename(f))[0] for f in part], torch.from_numpy(wav).to(dev)
 
 
@@ -110,8 +114,10 @@ def main():
     ap.add_argument("--method", choices=("direct", "fft"), default="direct")
     ap.add_argument("--peak", type=float, default=None)
     ap.add_argument("--walk", type=float, default=None, metavar="MS")
+    ap.add_argument("--resample", choices=("none", "kaiser_best", "kaiser_fast"), default="none")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
+    a.resample = None if a.resample == "none" else a.resample
     generated = bool(a.load or a.checkpoint or a.data or a.synthetic)
     if bool(a.rirs) == generated:
         raise SystemExit("give either --rirs, or a model (--load / --checkpoint) with --data or --synthetic")
@@ -121,8 +127,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("auralization runs on the GPU; there is none here")
     dev = torch.device("cuda:0")
-    frames = wav_frames(a.dry)
-    dry = torch.from_numpy(U.read_wav(a.dry, a.sr, (frames + 0.5) / a.sr)).to(dev)
+    frames, rate = wav_frames(a.dry)
+    # the whole file: int(duration * rate) = frames, and int(duration * sr) <= ceil(frames * sr / rate), what resampling yields
+    duration = (frames + min(0.5, 0.5 * rate / a.sr)) / rate
+    with torch.cuda.device(dev):
+        dry = torch.from_numpy(U.read_wav(a.dry, a.sr, duration, resample=a.resample)).to(dev)
     os.makedirs(a.out, exist_ok=True)
     rendered = []
     batches = rir_batches(a, dev) if a.rirs else model_batches(a, dev)
@@ -143,7 +152,7 @@ def main():
         write_wav(os.path.join(a.out, name + ".wav"), w * np.float32(gain), a.sr)
     if a.walk is not None:
         print(f"walked {path.shape[0]} positions, {spacing} samples apart")
-    print(f"wrote {len(rendered)} files of {rendered[0][1].shape[0]} samples to {a.out} (dry: {frames} samples, gain {gain:.6g})")
+    print(f"wrote {len(rendered)} files of {rendered[0][1].shape[0]} samples to {a.out} (dry: {frames} samples at {rate} Hz, gain {gain:.6g})")
 
 
 if __name__ == "__main__":

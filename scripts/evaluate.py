@@ -90,7 +90,8 @@ def file_batches(folder, dev):
 
 def dataset_batches(a, dev):
     ds = U.Dataset(a.dataset[0], a.dataset[1], normalization=True, room_characteristics=True, room=a.rooms, array=a.arrays,
-                   device=dev, keep_waveforms=True, input_shape=(a.height, a.width))
+                   device=dev, keep_waveforms=True, input_shape=(a.height, a.width),
+                   resample=None if a.resample == "none" else a.resample)
     gen = U.DataGenerator(ds, batch_size=a.batch, partition="test", shuffle=False, characteristics=True)
     if len(gen) == 0:
         raise SystemExit(f"the test partition ({len(gen.index_in)} pairs) holds less than one batch of {a.batch}")
@@ -120,6 +121,8 @@ def main():
     ap.add_argument("--dataset", nargs=2, metavar=("DIR", "NAME"))
     ap.add_argument("--rooms", nargs="+", default=None, help="with --dataset: room names (default: all five)")
     ap.add_argument("--arrays", nargs="+", default=None, help="with --dataset: array names (default: both)")
+    ap.add_argument("--resample", choices=("none", "kaiser_best", "kaiser_fast"), default="none",
+                    help="with --dataset: files of --dataset that are not at the data set's rate: none (an error), or converted on the device (librosa's res_type names)")
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--diff-gen", action="store_true")
     ap.add_argument("--algorithm", choices=("ph", "gl"), default="ph")

@@ -57,6 +57,8 @@ def main():
                     help="instead of --dataset: N batches of synthetic_batches per epoch (the same ones every epoch), no validation")
     ap.add_argument("--rooms", nargs="+", default=["LargeMeetingRoom"], help="room names, or All")
     ap.add_argument("--arrays", nargs="+", default=["PlanarMicrophoneArray", "CircularMicrophoneArray"])
+    ap.add_argument("--resample", choices=("none", "kaiser_best", "kaiser_fast"), default="none",
+                    help="files of --dataset that are not at the data set's rate: none (an error), or converted on the device (librosa's res_type names)")
     ap.add_argument("--no-debug", action="store_true", help="load the whole tree (main_training.py runs with debug = True)")
     ap.add_argument("--extract", action="store_true", help="unpack the zone archives first")
     ap.add_argument("--name", choices=("ae", "resae", "vae", "vqvae", "aenet", "diffunet", "diffvae", "unet"), default="unet")
@@ -136,7 +138,7 @@ def main():
 
     dataset = U.Dataset(a.dataset[0], a.dataset[1], normalization=True, debugging=not a.no_debug, extract=a.extract,
                         room=["All"] if a.rooms == ["All"] else a.rooms, array=a.arrays, device=dev, input_shape=(a.height, a.width),
-                        keep_waveforms=wavs)
+                        keep_waveforms=wavs, resample=None if a.resample == "none" else a.resample)
     # shuffle=True as main_training.py:78-79 passes it - and, as there, without effect: nothing calls on_epoch_end() (fit does
     # not either), so every epoch visits the batches in the order the seeded shuffle of the constructor gave them
     train = U.DataGenerator(dataset, batch_size=a.batch, partition="train", shuffle=True, characteristics=wavs)

@@ -36,6 +36,7 @@ _EXCEPTIONS = {                                                     # (function,
     ("unetrir_lamb_f32", "segs"): C.c_void_p,                       # the table in device memory (segs_host follows the rule)
     ("unetrir_lamb_dev_f32", "segs"): C.c_void_p,
     ("unetrir_cast_weights_batched_bf16", "desc"): C.c_void_p,      # descriptors in device memory
+    ("unetrir_resample_table_f32", "table"): C.POINTER(C.c_float),  # a host array of L T floats
 }
 
 

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libunetrir.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "unetrir.h")      # the C ABI: compiled into the library, parsed by _lib
-SOURCES = ["igemm.hip", "api.hip", "elementwise.hip", "head.hip", "head_mfma.hip", "head1x1.hip", "head_up2.hip", "wgrad3x3.hip", "wgrad3x3r.hip", "wgrad3x3g.hip", "wgrad3x3d.hip", "igemm_bf16.hip", "conv3x3.hip", "conv3x3r.hip", "conv3x3g.hip", "conv3x3h.hip", "conv3x3s.hip", "conv3x3d.hip", "conv3x3p.hip", "upconv3x3.hip", "upconv3x3g.hip", "upconv3x3q.hip", "features.hip", "dense.hip", "stem3x3.hip", "stem_composite.hip", "pw1x1.hip", "conv2x2.hip", "igemm2_bf16.hip", "weights.hip", "splitk_reduce.hip", "evalmetrics.hip", "acoustics.hip", "vae.hip", "vq.hip", "dataset.hip", "griffinlim.hip", "griffinlim_fft.hip", "lamb.hip", "cnn_clas.hip", "waveloss.hip", "auralize.hip", "auralize_fft.hip", "istft_bwd.hip", "decayloss.hip", "spectralloss.hip", "spectralloss_fft.hip"]
+SOURCES = ["igemm.hip", "api.hip", "elementwise.hip", "head.hip", "head_mfma.hip", "head1x1.hip", "head_up2.hip", "wgrad3x3.hip", "wgrad3x3r.hip", "wgrad3x3g.hip", "wgrad3x3d.hip", "igemm_bf16.hip", "conv3x3.hip", "conv3x3r.hip", "conv3x3g.hip", "conv3x3h.hip", "conv3x3s.hip", "conv3x3d.hip", "conv3x3p.hip", "upconv3x3.hip", "upconv3x3g.hip", "upconv3x3q.hip", "features.hip", "dense.hip", "stem3x3.hip", "stem_composite.hip", "pw1x1.hip", "conv2x2.hip", "igemm2_bf16.hip", "weights.hip", "splitk_reduce.hip", "evalmetrics.hip", "acoustics.hip", "vae.hip", "vq.hip", "dataset.hip", "griffinlim.hip", "griffinlim_fft.hip", "lamb.hip", "cnn_clas.hip", "waveloss.hip", "auralize.hip", "auralize_fft.hip", "istft_bwd.hip", "decayloss.hip", "spectralloss.hip", "spectralloss_fft.hip", "resample.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
 

@@ -18,9 +18,11 @@ reference's; what differs:
     numbers - and with them the pairs and the partitions - are the same on every machine;
   * `debugging=True` stops after the first array folder that yielded a sample.  The reference's flag is overwritten by every
     file it lists (:169-171), so whether it stops depends on whether the LAST file of a folder passed the filter;
-  * there is no resampler and no padding of short files: `read_wav` raises for a file whose rate is not `sr` or that is
-    shorter than `duration` (the reference goes through librosa, which would resample the first and pass the second on
-    short, to fail later in `np.stack`);
+  * a file whose rate is not `sr` is resampled only when asked: `Dataset(..., resample="kaiser_best")` (or "kaiser_fast",
+    librosa's `res_type` names) converts it on the device (resample.py, csrc/resample.hip), one file at a time, in the
+    reference's order - read, average, resample, cut, remove the mean; with the default resample=None `read_wav` raises for
+    it (the reference goes through librosa, which always resamples).  There is no padding of short files: `read_wav` raises
+    for a file shorter than `duration`, which librosa would pass on short, to fail later in `np.stack`;
   * `DataGenerator.on_epoch_end()` reshuffles with `random.Random` seeded from (seed, epoch count) instead of the unseeded
     global generator (:55-62), so two equal generators yield equal epochs.  `main_training.py` never calls it, `fit` does not
     either;
@@ -49,6 +51,7 @@ import torch
 from . import ops
 from .evaluate import ROOMS
 from .features import PreProcess
+from .resample import PRESETS, resample as _resample
 from .rooms import uts_room_embedding
 
 __all__ = ["Dataset", "DataGenerator", "read_wav", "ALL_ROOMS", "ARRAYS"]
@@ -77,6 +80,7 @@ def _pcm(raw, width, channels, path):
 
 
 def _read_float_wav(path, frames):
+    """-> (rate, fp32 [frames(rate) at most, channels])"""
     try:
         from scipy.io import wavfile
     except ImportError:
@@ -85,7 +89,7 @@ def _read_float_wav(path, frames):
         rate, data = wavfile.read(path)
     except Exception as e:          # scipy's own errors do not say which file
         raise ValueError(f"{path}: cannot be read as a wav file ({e})") from e
-    data = data[:frames]
+    data = data[:frames(rate)]
     if data.dtype.kind == "f":
         x = data.astype(np.float32)
     elif data.dtype.kind == "i":
@@ -95,28 +99,54 @@ def _read_float_wav(path, frames):
     return rate, x.reshape(len(x), -1)
 
 
-def read_wav(path, sample_rate, duration, mono=True):
+def read_wav(path, sample_rate, duration, mono=True, resample=None):
     """What `Loader.load` (preprocess.py:51-57) yields for this data set: the first int(duration * sample_rate) samples as fp32
     in [-1, 1), channels averaged when `mono`, then `signal -= np.mean(signal)` in fp32.  -> [T] (or [channels, T]).
 
     PCM 16 / 24 / 32 bit is decoded with the standard library; anything else goes through scipy.io.wavfile when it
-    imports.  There is no resampler: a file whose rate is not `sample_rate`, or that is shorter than `duration`, raises a
-    ValueError naming it."""
+    imports.  resample=None: a file whose rate is not `sample_rate` raises a ValueError naming it.  resample="kaiser_best" or
+    "kaiser_fast" (librosa's `res_type`): such a file is read for `duration` seconds at its own rate, averaged when `mono` (else
+    every channel for itself), resampled on the current CUDA device (`resample.Resampler`; a ValueError without one), cut to
+    int(duration * sample_rate) samples, and the mean removed on the host as before - the reference's order.  A file at
+    `sample_rate` takes the same path, bit for bit, whatever `resample` is; one that is shorter than `duration` raises either way."""
+    if resample is not None and resample not in PRESETS:
+        raise ValueError(f"read_wav: resample must be None or one of {sorted(PRESETS)}, not {resample!r}")
     frames = int(duration * sample_rate)
     try:
         with wave.open(path, "rb") as f:
             rate, channels, width, total = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
-            raw = f.readframes(min(frames, total)) if rate == sample_rate else b""
-        x = _pcm(raw, width, channels, path) if rate == sample_rate else None
+            want = frames if rate == sample_rate else int(duration * rate) if resample is not None else 0
+            raw = f.readframes(min(want, total))
+        x = _pcm(raw, width, channels, path) if want or rate == sample_rate else None
     except wave.Error:
-        rate, x = _read_float_wav(path, frames)
+        rate, x = _read_float_wav(path, lambda rate: frames if rate == sample_rate else int(duration * rate))
     if rate != sample_rate:
-        raise ValueError(f"{path}: sample rate {rate} Hz, expected {sample_rate} Hz (there is no resampler)")
-    if x.shape[0] < frames:
+        if resample is None:
+            raise ValueError(f"{path}: sample rate {rate} Hz, expected {sample_rate} Hz (pass resample='kaiser_best' or "
+                             "'kaiser_fast' to convert it)")
+        if x is None or x.shape[0] < 1:
+            raise ValueError(f"{path}: no samples within {duration} s")
+        x = _to_rate(x, rate, sample_rate, resample, mono, frames, path)
+        if x.shape[0] < frames:
+            raise ValueError(f"{path}: {x.shape[0]} samples after resampling from {rate} Hz, shorter than the {frames} that "
+                             f"{duration} s at {sample_rate} Hz take")
+    elif x.shape[0] < frames:
         raise ValueError(f"{path}: {x.shape[0]} samples, shorter than the {frames} that {duration} s at {sample_rate} Hz take")
     signal = x.mean(axis=1, dtype=np.float32) if mono else np.ascontiguousarray(x.T)
     signal -= np.mean(signal)
     return signal
+
+
+def _to_rate(x, rate, sample_rate, res_type, mono, frames, path):
+    """x fp32 [n, channels] at `rate` -> fp32 [min(frames, ceil(n L / M)), 1 or channels] at `sample_rate`: the channels averaged
+    first when `mono` (librosa's order), one launch on the current CUDA device, the head of the result copied back."""
+    if not torch.cuda.is_available():
+        raise ValueError(f"{path}: sample rate {rate} Hz, expected {sample_rate} Hz, and resampling runs on a CUDA device: none is "
+                         "available (there is no CPU path)")
+    rows = x.mean(axis=1, dtype=np.float32)[None] if mono else np.ascontiguousarray(x.T)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    y = _resample(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), int(rate), int(sample_rate), res_type)
+    return np.ascontiguousarray(y[:, :frames].cpu().numpy().T)
 
 
 class Dataset:
@@ -126,7 +156,7 @@ class Dataset:
 
     def __init__(self, dir_dataset, dataset_name, extract=False, normalization=True, debugging=False, room_characteristics=False,
                  room=None, array=None, *, device=None, keep_waveforms=False, n_fft=256, win_length=128, hop_length=64,
-                 duration=0.2, sr=48000, input_shape=(144, 160)):
+                 duration=0.2, sr=48000, input_shape=(144, 160), resample=None):
         if room is None:
             room = ["All"]
         self.array = list(ARRAYS) if array is None else array
@@ -134,6 +164,9 @@ class Dataset:
         self.dir_dataset, self.dataset_name = dir_dataset, dataset_name
         self.n_fft, self.win_length, self.hop_length = n_fft, win_length, hop_length
         self.duration, self.sr, self.mono = duration, sr, True
+        if resample is not None and resample not in PRESETS:
+            raise ValueError(f"Dataset: resample must be None or one of {sorted(PRESETS)}, not {resample!r}")
+        self.resample = resample
         self.input_shape = tuple(input_shape)
         self.normalization, self.debugging, self.room_characteristics = normalization, debugging, room_characteristics
         self.seed = 500          # dataset.py:76: one seed for the pairing and for the partitions
@@ -210,8 +243,8 @@ class Dataset:
         self.index_out = [i for lst in per_room for i in lst]
 
     def waveform(self, index):
-        """The decoded file of sample `index` (host, fp32 [T]): `read_wav` with the data set's rate and duration."""
-        return read_wav(self.files[index], self.sr, self.duration, self.mono)
+        """The decoded file of sample `index` (host, fp32 [T]): `read_wav` with the data set's rate, duration and `resample`."""
+        return read_wav(self.files[index], self.sr, self.duration, self.mono, self.resample)
 
     def return_characteristics(self):
         return self.characteristics if self.room_characteristics else None

@@ -934,6 +934,72 @@ def auralize_path_f32(rir, times_dev, dry, out, ws: Workspace = None):
                                                _stream()), "auralize_path")
 
 
+def resample_supported(L, M, zeros):
+    """Whether the resampler takes the reduced ratio L / M with `zeros` zero crossings to each side (include/unetrir.h)."""
+    return bool(_lib.lib().unetrir_resample_supported(int(L), int(M), int(zeros)))
+
+
+def resample_taps(L, M, zeros):
+    """T, the taps of every phase of the table (even; 0: not supported)."""
+    return int(_lib.lib().unetrir_resample_taps(int(L), int(M), int(zeros)))
+
+
+def resample_out_length(N, L, M):
+    """ceil(N L / M): the samples N input samples become (0: an argument below 1)."""
+    return int(_lib.lib().unetrir_resample_out_length(int(N), int(L), int(M)))
+
+
+def resample_table(L, M, zeros, rolloff, beta):
+    """The polyphase Kaiser-windowed sinc table of include/unetrir.h as a CPU fp32 tensor [L, T], built on the host in fp64."""
+    T = resample_taps(L, M, zeros)
+    if not T:
+        raise ValueError(f"resample: the ratio L = {L}, M = {M} with zeros = {zeros} is not supported "
+                         "(gcd 1, L and M <= 2048, zeros <= 64, T <= 8192, L T <= 2^20)")
+    table = torch.empty((int(L), T), dtype=torch.float32)
+    err = _lib.lib().unetrir_resample_table_f32(C.cast(table.data_ptr(), C.POINTER(C.c_float)), int(L), int(M), int(zeros),
+                                                float(rolloff), float(beta))
+    if err == _lib.EINVAL:
+        raise ValueError(f"resample: rolloff {rolloff} outside (0, 1] or beta {beta} outside [0, 32]")
+    check(err, "resample_table")
+    return table
+
+
+def resample_f32(x, table, L, M, out):
+    """out fp32 [B, Nout] = the first Nout <= ceil(N L / M) samples of x fp32 [B, N] resampled by L / M through table fp32 [L, T] (T
+    even; `resample_table`, or any other: the kernel does not interpret it): one launch on the current stream, every element one fp32
+    fma chain in ascending tap order (include/unetrir.h)."""
+    named = ((x, "x"), (table, "table"), (out, "out"))
+    if not all(isinstance(t, torch.Tensor) for t, _ in named):
+        raise ValueError("resample: x, table and out must be tensors")
+    if x.dim() != 2 or table.dim() != 2 or out.dim() != 2:
+        raise ValueError("resample: x [B, N], table [L, T], out [B, Nout]")
+    L, M = int(L), int(M)
+    B, N = x.shape
+    T, Nout = table.shape[1], out.shape[1]
+    if table.shape[0] != L or T < 2 or T % 2:
+        raise ValueError(f"resample: table {tuple(table.shape)} is not [L = {L}, T] with T even")
+    if out.shape[0] != B:
+        raise ValueError(f"resample: batch sizes differ: x {tuple(x.shape)}, out {tuple(out.shape)}")
+    if B < 1 or N < 1:
+        raise ValueError("resample: empty input")
+    full = resample_out_length(N, L, M)
+    if not 1 <= Nout <= full:
+        raise ValueError(f"resample: {Nout} output samples outside 1 ... ceil(N L / M) = {full}")
+    for t, what in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"resample: {what} must be float32, not {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"resample: {what} must be contiguous")
+    for t, what in named:
+        if not t.is_cuda or t.device != x.device:
+            raise ValueError(f"resample: {what} must be a CUDA tensor on the device of x (there is no CPU path)")
+    err = _lib.lib().unetrir_resample_f32(_p(x), _p(table), _p(out), B, N, L, M, T, Nout, _stream())
+    if err == _lib.EINVAL:
+        raise ValueError(f"resample: the geometry L = {L}, M = {M}, T = {T} is not supported (gcd 1, L and M <= 2048, T <= 8192, "
+                         "L T <= 2^20)")
+    check(err, "resample")
+
+
 def griffinlim_ws_bytes(B, n_bins, n_frames, n_fft):
     """Bytes of fp64 state `griffinlim` keeps in its workspace (0: a geometry the kernels do not take)."""
     return int(_lib.lib().unetrir_griffinlim_ws_bytes(int(B), int(n_bins), int(n_frames), int(n_fft)))
