@@ -856,6 +856,59 @@ size_t unetrir_auralize_path_ws_bytes(int B, int R, int K, int N, long long dry_
 int unetrir_auralize_path_f32(const float* rir, const int* times, const float* dry, float* out, int B, int R, int K, int N,
                               long long dry_stride, int L, void* ws, size_t ws_bytes, unetrir_stream_t stream);
 
+/* ---- auralization block by block: the FFT form with its state carried between calls, and a response that can be exchanged while
+ *      audio runs (auralize_fft.hip; the state layout and the launches are in its header).
+ *
+ * A stream renders y_b = h_b * x_b for a dry signal that arrives over time, P = 2048 samples (one block) or a multiple at a call.  With
+ * Q = ceil(K / P), H_q and X_i as unetrir_auralize_fft_f32 and i, j counted from the first sample pushed since init:
+ *   Y_j = sum_{q <= min(j, Q-1)} H_q X_{j-q}, ascending q from +0,   out block j = the last P samples of irfft(Y_j)
+ * - the same formulation on the same block grid, with the last Q + max_blocks - 1 spectra of x kept in a ring (X_i in slot i mod S,
+ * S = Q + max_blocks - 1) and the last P dry samples carried as the first half of the next window.
+ * state: one opaque block of DEVICE memory, 16-byte aligned, unetrir_auralize_stream_state_bytes(B, K, dry_rows, max_blocks) bytes
+ *   = 64 + 16384 (2 B Q + dry_rows S) + 8192 dry_rows
+ * (control words; the spectra of the current response and of the one being faded in; the ring; the carry), 0 for arguments the calls
+ * refuse.  dry_rows: 1 (one dry signal heard through all B responses) or B (one per row); 1 <= max_blocks <= 64: the most blocks one
+ * push takes.  Everything that changes from call to call - the count of blocks rendered (64-bit), which response is current, whether a
+ * fade is pending - lives in state, so the launch arguments of a push are the same every time: a push is capturable and a replay
+ * renders the NEXT blocks from whatever the dry buffer holds then.  A larger state than advertised is accepted; the rest is not touched.
+ *
+ * unetrir_auralize_stream_init: rir fp32 [B][K].  Clears state (ring, carry, control) and writes the spectra of rir as the current
+ *   response: a memset and one launch.  Calling it again restarts the stream (block 0, silence before it).
+ * unetrir_auralize_stream_update: rir fp32 [B][K], a new response: its spectra go into the slot that is not current and a fade is marked
+ *   pending; ONE launch.  The next push renders its first block through both responses and crossfades them linearly across that block
+ *   (below); from the second block on the new response alone is heard, and it becomes the current one.  A second update before a push
+ *   replaces the first: the last one wins.
+ * unetrir_auralize_stream_push: consumes blocks P new dry samples per dry row, 1 <= blocks <= max_blocks, and writes the next blocks P
+ *   output samples of every row into out fp32 [B][out_stride], out_stride >= blocks P.  dry fp32 [blocks P] with dry_stride = 0
+ *   (dry_rows = 1) or [dry_rows][dry_stride], dry_stride >= blocks P; a NULL dry stands for zeros (to render the tail after the last
+ *   sample; dry_stride is then not looked at).  THREE launches whatever B, K, blocks: (a) the spectra of the new windows into their ring slots; (b) one workgroup per row
+ *   and pair of output blocks: products through the ring, inverse, store; (c) the last P dry samples into the carry, the count advanced
+ *   by blocks and a pending fade completed - a launch of its own because the workgroups of (a) and (b) read what it writes.
+ *   No atomics, no host synchronisation; nothing outside state and the blocks P samples per row of out is written, and every one of
+ *   those samples exactly once.
+ * The fade: with the update pending at block j, block j is the result of unetrir_auralize_path_f32 for the two nodes (old response at
+ *   jP, new response at (j+1)P): out[n] = (1 - a) y_old[n] + a y_new[n], a = float(n - jP) / 2048 (exact), by that kernel's sequence -
+ *   o = g y for the first node, o = fmaf(g, y, o) for the second, a gain of exactly 0 skipped.
+ * Bits: block j of a stream that was never updated is block j of unetrir_auralize_fft_f32(rir, x, ..., L) for x = everything pushed so
+ *   far (followed by zeros), bit for bit; after an update at block j the blocks from j on are those of unetrir_auralize_path_f32 with
+ *   the two nodes above.  They do not depend on how the samples were divided into pushes, max_blocks, B, the row's place, shared or
+ *   per-row dry, the run, or a larger state.  The error bounds are those of the two one-shot calls.
+ * unetrir_auralize_stream_supported(K): 1 for 1 <= K <= 16384, as the FFT form.
+ * UNETRIR_EINVAL before the device is touched: a null state, rir (init, update) or out (push); state not 16-byte aligned; state_bytes
+ * below unetrir_auralize_stream_state_bytes(B, K, dry_rows, max_blocks) for the arguments given (so B, K, dry_rows and max_blocks
+ * must be those the state was sized and initialised for: they are not stored where the host could compare them); B or K < 1, K
+ * unsupported, dry_rows neither 1 nor B, max_blocks outside 1 ... 64; blocks outside 1 ... max_blocks; with a dry, a dry_stride that
+ * is neither 0 with dry_rows = 1 nor >= blocks P; out_stride < blocks P; more workgroups than a launch takes (2 B Q + dry_rows S or
+ * B max_blocks above 2^31 - 8). */
+int unetrir_auralize_stream_supported(int K);
+size_t unetrir_auralize_stream_state_bytes(int B, int K, int dry_rows, int max_blocks);
+int unetrir_auralize_stream_init(void* state, size_t state_bytes, const float* rir, int B, int K, int dry_rows, int max_blocks,
+                                 unetrir_stream_t stream);
+int unetrir_auralize_stream_update(void* state, size_t state_bytes, const float* rir, int B, int K, int dry_rows, int max_blocks,
+                                   unetrir_stream_t stream);
+int unetrir_auralize_stream_push(void* state, size_t state_bytes, int B, int K, int dry_rows, int max_blocks, const float* dry,
+                                 long long dry_stride, float* out, long long out_stride, int blocks, unetrir_stream_t stream);
+
 /* ---- sample-rate conversion: a polyphase Kaiser-windowed sinc filter (resample.hip; the table is built on the host by
  *      resample_table.h, the tiling is in the former's header).
  *

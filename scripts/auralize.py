@@ -5,6 +5,7 @@
     python scripts/auralize.py --checkpoint CKPT_DIR --filters 32 --kernels 3 --data BATCH_DIR --dry speech.wav --out OUT_DIR
     python scripts/auralize.py --load SAVED_MODEL_DIR --arch aenet --synthetic 1 --dry speech.wav --out OUT_DIR [--diff-gen]
     python scripts/auralize.py --rirs RIR_DIR --dry speech.wav --out OUT_DIR --walk 250
+    python scripts/auralize.py --rirs RIR_DIR --dry hour_long.wav --out OUT_DIR --stream
 
 --rirs         a directory of impulse-response .wav files (sorted by name), read by `read_wav`'s rules: --sr Hz, the first --duration
                seconds, mean removed; files at another rate need --resample
@@ -23,6 +24,10 @@
                files of --rirs in sorted order, or a model's responses in the order they are generated, over all batches.  One file,
                OUT_DIR/walk.wav; --length and --peak as without it; on the FFT form whatever --method says (MS at --sr must come to
                at least 32 samples)
+--stream       render block by block (unet_rir_amd.AuralizeStream): --dry is read in chunks of --chunk-ms milliseconds (default 1000), in two
+               passes - the mean that `read_wav` removes, then the rendering - and every output file is written as it is produced, so
+               memory does not depend on the length of the recording.  The files are those of --method fft, byte for byte.  The dry file
+               is read once per batch of responses (--batch).  Not with --resample, --peak or --walk: each needs the whole signal
 --out          OUT_DIR/NAME.wav per position, 32-bit float at --sr: NAME is the response's file name, or b{batch}_{row} for generated ones
 --peak         scale every output file so that the loudest sample of the whole set is this (default: values as computed)
 """
@@ -37,7 +42,8 @@ import numpy as np
 import torch
 
 import unet_rir_amd as U
-from unet_rir_amd.auralize import write_wav
+from unet_rir_amd.auralize import WavWriter, write_wav
+from unet_rir_amd.dataset import _pcm
 from unet_rir_amd.features import PostProcess
 
 
@@ -63,6 +69,115 @@ def wav_frames(path):
                 return size // align, rate
             else:
                 f.seek(size + (size & 1), 1)
+
+
+def dry_chunks(path, frames_per_chunk):
+    """-> (frames, rate, chunks): chunks() yields the file as fp32 [n, channels] pieces of frames_per_chunk frames (the last shorter),
+    decoded as `read_wav` decodes them: PCM of 16, 24 or 32 bits through the standard `wave` module, 32- and 64-bit IEEE float (which
+    `wave` does not take) from the data chunk itself."""
+    import wave
+    try:
+        with wave.open(path, "rb") as f:
+            rate, channels, width, total = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
+
+        def chunks():
+            with wave.open(path, "rb") as f:
+                for _ in range(0, total, frames_per_chunk):
+                    yield _pcm(f.readframes(frames_per_chunk), width, channels, path)
+        return total, rate, chunks
+    except wave.Error:
+        pass
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise SystemExit(f"{path}: not a RIFF/WAVE file")
+        fmt = None
+        while True:
+            ck = f.read(8)
+            if len(ck) < 8:
+                raise SystemExit(f"{path}: no data chunk")
+            name, size = struct.unpack("<4sI", ck)
+            if name == b"fmt ":
+                fmt = struct.unpack("<HHIIHH", f.read(16))
+                f.seek(size - 16 + (size & 1), 1)
+            elif name == b"data":
+                start = f.tell()
+                break
+            else:
+                f.seek(size + (size & 1), 1)
+    if fmt is None or fmt[0] != 3 or fmt[5] not in (32, 64):
+        raise SystemExit(f"{path}: --stream reads PCM and IEEE-float wav files")
+    channels, rate, width = fmt[1], fmt[2], fmt[5] // 8
+    total = size // (width * channels)
+
+    def chunks():
+        with open(path, "rb") as f:
+            f.seek(start)
+            for at in range(0, total, frames_per_chunk):
+                n = min(frames_per_chunk, total - at)
+                raw = np.frombuffer(f.read(n * width * channels), dtype="<f4" if width == 4 else "<f8")
+                yield raw.astype(np.float32).reshape(n, channels)
+    return total, rate, chunks
+
+
+def dry_mean(chunks):
+    """The mean `read_wav` removes - np.mean of the channel-averaged fp32 signal - from the signal in pieces: numpy sums an fp32 array
+    in runs of np.getbufsize() elements, each pairwise, and adds the runs up in order; so do we, one run at a time.  -> (fp32 mean, n)"""
+    run = np.getbufsize()
+    total, n, rest = np.float32(0.0), 0, np.zeros(0, dtype=np.float32)
+    for x in chunks():
+        mono = np.concatenate([rest, x.mean(axis=1, dtype=np.float32)])
+        whole = mono.shape[0] // run * run
+        for at in range(0, whole, run):
+            total = np.float32(total + np.add.reduce(mono[at:at + run]))
+        n += whole
+        rest = mono[whole:]
+    if rest.shape[0]:
+        total = np.float32(total + np.add.reduce(rest))
+        n += rest.shape[0]
+    return np.float32(total / np.float32(n)), n
+
+
+def stream(a, dev, batches, length):
+    """--stream: per batch of responses one AuralizeStream, the dry file pushed through it chunk by chunk, the output files written as
+    the blocks arrive and cut to the --length asked for"""
+    per_chunk = max(1, int(round(a.chunk_ms * a.sr / 1000.0)))
+    per_chunk = -(-per_chunk // np.getbufsize()) * np.getbufsize()                          # whole runs of the mean's summation
+    frames, rate, chunks = dry_chunks(a.dry, per_chunk)
+    if rate != a.sr:
+        raise SystemExit(f"{a.dry}: sample rate {rate} Hz, expected {a.sr} Hz (--stream does not resample)")
+    if frames < 1:
+        raise SystemExit(f"{a.dry}: no samples")
+    mean, n = dry_mean(chunks)
+    assert n == frames
+    count = L = 0
+    for names, wav in batches:
+        wav = wav.float().contiguous()
+        K = wav.shape[1]
+        L = frames + K - 1 if length == "full" else frames if length == "same" else length
+        if not 1 <= L <= frames + K - 1:
+            raise SystemExit(f"--length must be full, same or 1 ... N + K - 1 = {frames + K - 1}")
+        s = U.AuralizeStream(wav, "shared", max_blocks=8)
+        writers = [WavWriter(os.path.join(a.out, name + ".wav"), a.sr) for name in names]
+        done = 0
+
+        def emit(y):
+            nonlocal done
+            y = y[:, :max(0, min(y.shape[1], L - done))].cpu().numpy()
+            for w, row in zip(writers, y):
+                w.write(row)
+            done += y.shape[1]
+        for x in chunks():
+            mono = x.mean(axis=1, dtype=np.float32)
+            mono -= mean
+            emit(s.push(torch.from_numpy(mono).to(dev)))
+        emit(s.flush())
+        for w in writers:
+            w.close()
+        assert done == L
+        count += len(names)
+    print(f"streamed {count} files of {L} samples to {a.out} (dry: {frames} samples at {rate} Hz, in chunks of {per_chunk}; "
+          f"mean removed {float(mean):.6g})")
 
 
 def rir_batches(a, dev):
@@ -115,6 +230,8 @@ def main():
     ap.add_argument("--peak", type=float, default=None)
     ap.add_argument("--walk", type=float, default=None, metavar="MS")
     ap.add_argument("--resample", choices=("none", "kaiser_best", "kaiser_fast"), default="none")
+    ap.add_argument("--stream", action="store_true")
+    ap.add_argument("--chunk-ms", type=float, default=1000.0)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     a.resample = None if a.resample == "none" else a.resample
@@ -124,9 +241,20 @@ def main():
     if generated and bool(a.data) == bool(a.synthetic):
         raise SystemExit("a model needs exactly one of --data and --synthetic")
     length = a.length if a.length in ("full", "same") else int(a.length)
+    if a.stream:
+        for given, option in ((a.resample is not None, "--resample"), (a.peak is not None, "--peak"), (a.walk is not None, "--walk")):
+            if given:
+                raise SystemExit(f"--stream does not go with {option}: it needs the whole signal (or a schedule) before the first block")
+        if a.chunk_ms <= 0:
+            raise SystemExit("--chunk-ms must be positive")
     if not torch.cuda.is_available():
         raise SystemExit("auralization runs on the GPU; there is none here")
     dev = torch.device("cuda:0")
+    if a.stream:
+        os.makedirs(a.out, exist_ok=True)
+        with torch.cuda.device(dev):
+            stream(a, dev, rir_batches(a, dev) if a.rirs else model_batches(a, dev), length)
+        return
     frames, rate = wav_frames(a.dry)
     # the whole file: int(duration * rate) = frames, and int(duration * sr) <= ceil(frames * sr / rate), what resampling yields
     duration = (frames + min(0.5, 0.5 * rate / a.sr)) / rate

@@ -25,7 +25,7 @@ from .trainer import CheckpointManager, GradBucketer, Trainer, fit, lr_schedule 
 from .waveloss import WaveLoss  # noqa: F401
 from .decayloss import DecayLoss  # noqa: F401
 from .spectralloss import SpectralLoss  # noqa: F401
-from .auralize import auralize, auralize_path  # noqa: F401
+from .auralize import AuralizeStream, auralize, auralize_path  # noqa: F401
 from .resample import Resampler, resample  # noqa: F401
 
-__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "DiffUNet", "DiffUNetEngine", "DiffVAE", "DiffVAEEngine", "deep_CNN", "DeepCNNEngine", "HipRuntime", "Trainer", "WaveLoss", "DecayLoss", "SpectralLoss", "LAMB", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "acoustics", "write_report", "Dataset", "DataGenerator", "read_wav", "auralize", "auralize_path", "Resampler", "resample"]
+__all__ = ["ops", "build", "UnetrirError", "UNetEngine", "UNetGraphEngine", "ResAEEngine", "UNet", "ResAE", "Autoencoder", "AutoencoderEngine", "VAE", "VAEEngine", "VQVAE", "VQVAEEngine", "AENet", "AENetEngine", "DiffUNet", "DiffUNetEngine", "DiffVAE", "DiffVAEEngine", "deep_CNN", "DeepCNNEngine", "HipRuntime", "Trainer", "WaveLoss", "DecayLoss", "SpectralLoss", "LAMB", "GradBucketer", "lr_schedule", "CheckpointManager", "fit", "DeviceBatchPipeline", "synthetic_batches", "evaluate", "Evaluator", "score", "acoustics", "write_report", "Dataset", "DataGenerator", "read_wav", "auralize", "auralize_path", "AuralizeStream", "Resampler", "resample"]

@@ -40,6 +40,9 @@
 // integer data to round(out) == y.
 //
 // Not exact on integer data (the direct form is); a non-finite sample spoils the whole blocks its window feeds, not K outputs.
+//
+// Two more forms on the same helpers follow further down, each with its own header: auralize_path (a moving listener: crossfaded
+// responses) and the stream (the stationary form block by block with its state carried between calls).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
@@ -104,8 +107,13 @@ FL_HD void af_mac(cf (&acc)[8], const AfBins& h, const AfBins& x, int t) {
 // Y_{j0 + g} = sum_q H_q X_{j0 + g - q} for g = 0 ... gmax (< G) at once, each in ascending q from +0: step q reads H_q and ONE new
 // spectrum of x, X_{j0 - q}; the other G - 1 it needs are still in registers from the steps before (X_i sits in slot (i - j0) mod G, so
 // the q loop is unrolled by G to keep the slots static).  H (this row's spectra) and X are indexed by spectrum, AF_M / 2 float4 each.
-template <int G>
-FL_HD void af_accumulate(cf (&acc)[G][8], const float4* __restrict__ H, const float4* __restrict__ X, int j0, int gmax, int Q, int t) {
+// slot(i): where spectrum X_i lies in X - i itself for the one-shot forms, i mod S through a stream's ring.
+struct AfLinear {
+    FL_HD int operator()(int i) const { return i; }
+};
+template <int G, class Slot = AfLinear>
+FL_HD void af_accumulate(cf (&acc)[G][8], const float4* __restrict__ H, const float4* __restrict__ X, int j0, int gmax, int Q, int t,
+                         Slot slot = Slot()) {
     AfBins x[G], h;
 #pragma unroll
     for (int g = 0; g < G; ++g)
@@ -113,7 +121,7 @@ FL_HD void af_accumulate(cf (&acc)[G][8], const float4* __restrict__ H, const fl
         for (int e = 0; e < 8; ++e) acc[g][e] = {0.f, 0.f};
 #pragma unroll
     for (int g = 1; g < G; ++g)
-        if (g <= gmax) af_read(x[g], X + (size_t)(j0 + g) * (AF_M / 2), t);
+        if (g <= gmax) af_read(x[g], X + (size_t)slot(j0 + g) * (AF_M / 2), t);
     const int qn = (j0 + gmax < Q - 1 ? j0 + gmax : Q - 1) + 1;
     for (int qq = 0; qq < qn; qq += G) {
 #pragma unroll
@@ -121,7 +129,7 @@ FL_HD void af_accumulate(cf (&acc)[G][8], const float4* __restrict__ H, const fl
             const int q = qq + s;
             if (q < qn) {
                 af_read(h, H + (size_t)q * (AF_M / 2), t);
-                if (q <= j0) af_read(x[(G - s) % G], X + (size_t)(j0 - q) * (AF_M / 2), t);
+                if (q <= j0) af_read(x[(G - s) % G], X + (size_t)slot(j0 - q) * (AF_M / 2), t);
 #pragma unroll
                 for (int g = 0; g < G; ++g)
                     if (g <= gmax && q <= j0 + g) af_mac(acc[g], h, x[(g - s + G) % G], t);
@@ -356,9 +364,294 @@ bool ap_plan(int B, int R, int K, int N, long long dry_stride, int L, long long&
     return nH + nX <= 0x7ffffff8LL;
 }
 
+// ---- AuralizeStream: the stationary form block by block, its state carried between calls, and a response exchanged while audio runs.
+//
+// Partitioned overlap-save is a streaming algorithm: output block j needs X_j ... X_{j-Q+1} and nothing else of x.  A stream keeps
+//     state = [control: 64 bytes] [H: 2][B][Q] spectra [X: xrows][S] spectra [carry: xrows][P] floats,     S = Q + max_blocks - 1
+// X_i in ring slot i mod S (a push of at most max_blocks blocks writes X_c ... X_{c+blocks-1} and reads back to X_{c-Q+1}: at most S
+// distinct spectra), the carry = the last P dry samples, the first half of the next window.  Control, on the device so that a push has
+// the same launch arguments every time (capturable): count c of blocks rendered (64-bit), the current H slot, whether a fade is pending.
+//
+// push = three launches.  (a) X_{c+i} = rfft(carry | new) for i = 0, rfft(new[(i-1)P ... (i+1)P)) beyond: the spectra kernel's transform
+// on the same sample values, so the same bits.  (b) one workgroup per row and pair of blocks (c + 2g, c + 2g + 1): af_accumulate<2> -
+// the stationary render's own chain, reading X through the ring - inverse split, inverse FFT, 2^-12 scaling, store.  With a fade pending
+// the first workgroup of a row renders block c through the old and then the new response by af_accumulate<1> and blends them with
+// ap_gain for the two nodes (old at cP, new at (c+1)P) and the path kernel's accumulate sequence, then block c + 1 through the new
+// response alone; every other workgroup uses the new response.  (c) the last P new samples into the carry, c += blocks, and after a
+// fade the new slot becomes current.  (c) cannot be folded into (a) or (b): their other workgroups still read carry and control.
+// An index into the ring never needs j itself: the chain sees j clamped to AS_JCLAMP >= Q - 1 (it only compares j with q < Q) and the
+// ring's base makes up the difference.
+//
+// Tried: the fade in a kernel of its own chosen on the host - that needs the flag on the host, a synchronisation or a second set of
+// launch arguments, and a captured push could no longer follow an update.  It is a branch of the one kernel, uniform over the grid.
+// Registers (the compiler's report): the stationary branch alone 168 VGPRs, as the one-shot render; with the fade written out as three
+// chains 272 - 276; as ONE loop of three passes over one copy of the chain 252, no spills: two waves per SIMD for both branches.
+// Holding it to 256 by an occupancy attribute instead spilled 14 registers.
+struct AsCtrl {
+    long long count;                                    // blocks rendered since init
+    int cur;                                            // the H slot that is heard
+    int pending;                                        // 1: the other slot holds a response to fade in at the next block
+    int pad[12];
+};
+static_assert(sizeof(AsCtrl) == 64, "the control words take the first 64 bytes of a stream's state");
+constexpr int AS_MAXBLOCKS = 64;
+constexpr int AS_JCLAMP = 16;                           // >= AF_MAXK / AF_P - 1 + AF_G
+
+struct AsRing {
+    int base, S;                                        // base = (j - min(j, AS_JCLAMP)) mod S
+    FL_HD int operator()(int i) const { return (base + i) % S; }
+};
+
+struct AsPlan {
+    long long Q, S, nH, nX;
+    size_t bytes;
+};
+
+bool as_plan(int B, int K, int dry_rows, int max_blocks, AsPlan& p) {
+    if (B < 1 || K < 1 || K > AF_MAXK || max_blocks < 1 || max_blocks > AS_MAXBLOCKS) return false;
+    if (dry_rows != 1 && dry_rows != B) return false;
+    p.Q = (K + AF_P - 1) / AF_P;
+    p.S = p.Q + max_blocks - 1;
+    p.nH = (long long)B * p.Q;
+    p.nX = (long long)dry_rows * p.S;
+    if (2 * p.nH + p.nX > 0x7ffffff8LL || (long long)B * max_blocks > 0x7ffffff8LL) return false;          // grids are padded to 8
+    p.bytes = sizeof(AsCtrl) + (size_t)(2 * p.nH + p.nX) * AF_SPEC + (size_t)dry_rows * AF_P * sizeof(float);
+    return true;
+}
+
+// The spectra of rir [B][K] into H slot 0 (init) or the slot that is not current (update, which also marks the fade)
+__global__ __launch_bounds__(AF_THREADS) void auralize_stream_response_kernel(const float* __restrict__ rir, AsCtrl* ctrl,
+                                                                              float4* __restrict__ Hs, int K, int Q, int nH, int update) {
+    __shared__ cf buf[AF_M];
+    const int t = threadIdx.x;
+    const int blk = af_block(nH);
+    if (blk >= nH) return;
+    const int slot = update ? 1 - (ctrl->cur & 1) : 0;
+    const int b = blk / Q, q = blk - b * Q;
+    af_load(buf, rir + (size_t)b * K, (long long)q * AF_P, K, AF_P, t);
+    __syncthreads();
+    fl_fft<AF_M, -1>(buf, t);
+    fl_split_fwd<AF_M>(buf, t, AF_THREADS);
+    __syncthreads();
+    af_store_spec(Hs + ((size_t)slot * nH + blk) * (AF_M / 2), buf, t);
+    if (update && blk == 0 && t == 0) ctrl->pending = 1;         // nobody reads this word in this launch
+}
+
+// (a): X_{c+i}, i in [0, blocks), per dry row; dry null: zeros
+__global__ __launch_bounds__(AF_THREADS) void auralize_stream_spectra_kernel(const float* __restrict__ dry, long long dry_stride,
+                                                                             const AsCtrl* __restrict__ ctrl,
+                                                                             const float* __restrict__ carry, float4* __restrict__ X,
+                                                                             int S, int blocks, int xrows) {
+    __shared__ cf buf[AF_M];
+    const int t = threadIdx.x;
+    const int blk = af_block(xrows * blocks);
+    if (blk >= xrows * blocks) return;
+    const int r = blk / blocks, i = blk - r * blocks;
+    const float* __restrict__ row = dry ? dry + (long long)r * dry_stride : nullptr;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int k = t + AF_THREADS * e, m = 2 * k;                // m and m + 1 lie in the same half of the window
+        cf z = {0.f, 0.f};
+        if (m < AF_P && i == 0) {
+            z = {carry[(size_t)r * AF_P + m], carry[(size_t)r * AF_P + m + 1]};
+        } else if (row) {
+            const long long s = (long long)(i - 1) * AF_P + m;
+            z = {row[s], row[s + 1]};
+        }
+        buf[fl_swz(k)] = z;
+    }
+    __syncthreads();
+    fl_fft<AF_M, -1>(buf, t);
+    fl_split_fwd<AF_M>(buf, t, AF_THREADS);
+    __syncthreads();
+    const int slot = (int)((ctrl->count + i) % S);
+    af_store_spec(X + ((size_t)r * S + slot) * (AF_M / 2), buf, t);
+}
+
+// The inverse of one accumulated block, as the stationary render does it; the image holds the samples afterwards
+FL_HD void as_inverse(cf* buf, const cf (&acc)[8], int t) {
+    af_store_acc(buf, acc, t);
+    __syncthreads();
+    fl_split_inv<AF_M>(buf, t, AF_THREADS);
+    __syncthreads();
+    fl_fft<AF_M, 1>(buf, t);
+}
+
+// (b): one workgroup per row and pair of push-local blocks (2g, 2g + 1)
+__global__ __launch_bounds__(AF_THREADS) void auralize_stream_render_kernel(const AsCtrl* __restrict__ ctrl, const float4* __restrict__ Hs,
+                                                                            const float4* __restrict__ Xs, float* __restrict__ out,
+                                                                            long long out_stride, int Q, int S, int blocks, int NG,
+                                                                            int xrows, int B) {
+#pragma clang fp contract(off)
+    __shared__ cf buf[AF_M];
+    const int t = threadIdx.x;
+    const int blk = af_block(B * NG);
+    if (blk >= B * NG) return;
+    const int b = blk / NG, i0 = (blk - b * NG) * AF_G;
+    const int gmax = blocks - 1 - i0 < AF_G - 1 ? blocks - 1 - i0 : AF_G - 1;
+    const long long j = ctrl->count + i0;               // the stream's block index of this workgroup's first block
+    const int cur = ctrl->cur & 1, pending = ctrl->pending;
+    const int jq = j < AS_JCLAMP ? (int)j : AS_JCLAMP;
+    const AsRing ring{(int)((j - jq) % S), S};
+    const size_t row_spec = (size_t)Q * (AF_M / 2);
+    const float4* __restrict__ Hold = Hs + ((size_t)cur * B + b) * row_spec;
+    const float4* __restrict__ Hnew = Hs + ((size_t)(1 - cur) * B + b) * row_spec;
+    const float4* __restrict__ X = Xs + (xrows > 1 ? (size_t)b * S : 0) * (AF_M / 2);
+    float* __restrict__ yrow = out + (long long)b * out_stride;
+    const long long L = (long long)blocks * AF_P;
+    if (!(pending && i0 == 0)) {
+        cf acc[AF_G][8];
+        af_accumulate<AF_G>(acc, pending ? Hnew : Hold, X, jq, gmax, Q, t, ring);
+#pragma unroll
+        for (int g = 0; g < AF_G; ++g) {
+            if (g > gmax) break;
+            if (g) __syncthreads();                     // the stores of block g - 1 have read the image
+            as_inverse(buf, acc[g], t);
+            af_store_out(yrow, buf, (long long)(i0 + g) * AF_P, L, t);
+        }
+        return;
+    }
+    // the fade: block j through the old response (node 0 at jP) and the new one (node 1 at (j+1)P), the path kernel's blend; then
+    // (pass 2) its neighbour through the new response alone.  One loop, so that one copy of the chain serves all three passes.
+    const long long n0 = j * AF_P, tau[2] = {n0, n0 + AF_P};
+    float o[8];
+    unsigned have = 0;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) o[s] = 0.f;
+#pragma unroll 1
+    for (int pass = 0; pass < 2 + gmax; ++pass) {
+        const int r = pass & 1;                         // the node of passes 0 and 1: old, new
+        cf acc[1][8];
+        af_accumulate<1>(acc, pass ? Hnew : Hold, X, jq + (pass >> 1), 0, Q, t, ring);
+        if (pass) __syncthreads();                      // the pass before has read the image
+        as_inverse(buf, acc[0], t);
+        if (pass == 2) {
+            af_store_out(yrow, buf, (long long)AF_P, L, t);
+            break;
+        }
+        const long long tp = tau[0], tc = tau[r], tn = tau[1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = t + AF_THREADS * e;
+            const cf z = buf[fl_swz(AF_M / 2 + i)];
+            const long long n = n0 + 2 * i;
+            const float y[2] = {z.x * (1.f / (2 * AF_M)), z.y * (1.f / (2 * AF_M))};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float gn = ap_gain(n + k, r, 2, tp, tc, tn);
+                const unsigned bit = 1u << (2 * e + k);
+                if (gn != 0.f) {
+                    o[2 * e + k] = (have & bit) ? fmaf(gn, y[k], o[2 * e + k]) : gn * y[k];
+                    have |= bit;
+                }
+            }
+        }
+        if (pass == 1) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float* __restrict__ p = yrow + 2 * (t + AF_THREADS * e);          // block 0 of the push: always whole
+                if (((uintptr_t)p & 7) == 0) {
+                    *reinterpret_cast<float2*>(p) = make_float2(o[2 * e], o[2 * e + 1]);
+                } else {
+                    p[0] = o[2 * e];
+                    p[1] = o[2 * e + 1];
+                }
+            }
+        }
+    }
+}
+
+// (c): what the next push starts from
+__global__ __launch_bounds__(AF_THREADS) void auralize_stream_advance_kernel(const float* __restrict__ dry, long long dry_stride,
+                                                                             AsCtrl* ctrl, float* __restrict__ carry, int blocks) {
+    const int t = threadIdx.x, r = blockIdx.x;
+    const float* __restrict__ last = dry ? dry + (long long)r * dry_stride + (long long)(blocks - 1) * AF_P : nullptr;
+#pragma unroll
+    for (int e = 0; e < AF_P / AF_THREADS; ++e) {
+        const int m = t + AF_THREADS * e;
+        carry[(size_t)r * AF_P + m] = last ? last[m] : 0.f;
+    }
+    if (r == 0 && t == 0) {
+        ctrl->count += blocks;
+        if (ctrl->pending) {
+            ctrl->cur = 1 - (ctrl->cur & 1);
+            ctrl->pending = 0;
+        }
+    }
+}
+
+struct AsState {
+    AsCtrl* ctrl;
+    float4 *H, *X;
+    float* carry;
+};
+
+// The parts of a state that passed the checks every entry point makes; false: refuse
+bool as_state(void* state, size_t state_bytes, int B, int K, int dry_rows, int max_blocks, AsPlan& p, AsState& s) {
+    if (!state || ((uintptr_t)state & 15) || !as_plan(B, K, dry_rows, max_blocks, p) || state_bytes < p.bytes) return false;
+    char* base = static_cast<char*>(state);
+    s.ctrl = reinterpret_cast<AsCtrl*>(base);
+    s.H = reinterpret_cast<float4*>(base + sizeof(AsCtrl));
+    s.X = s.H + (size_t)(2 * p.nH) * (AF_M / 2);
+    s.carry = reinterpret_cast<float*>(s.X + (size_t)p.nX * (AF_M / 2));
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int unetrir_auralize_stream_supported(int K) { return K >= 1 && K <= AF_MAXK ? 1 : 0; }
+
+size_t unetrir_auralize_stream_state_bytes(int B, int K, int dry_rows, int max_blocks) {
+    AsPlan p;
+    return as_plan(B, K, dry_rows, max_blocks, p) ? p.bytes : 0;
+}
+
+int unetrir_auralize_stream_init(void* state, size_t state_bytes, const float* rir, int B, int K, int dry_rows, int max_blocks,
+                                 unetrir_stream_t stream) {
+    AsPlan p;
+    AsState s;
+    if (!rir || !as_state(state, state_bytes, B, K, dry_rows, max_blocks, p, s)) return UNETRIR_EINVAL;
+    hipError_t e = hipMemsetAsync(state, 0, p.bytes, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(auralize_stream_response_kernel, dim3(af_grid(p.nH)), dim3(AF_THREADS), 0, (hipStream_t)stream, rir, s.ctrl, s.H, K,
+                       (int)p.Q, (int)p.nH, 0);
+    return (int)hipGetLastError();
+}
+
+int unetrir_auralize_stream_update(void* state, size_t state_bytes, const float* rir, int B, int K, int dry_rows, int max_blocks,
+                                   unetrir_stream_t stream) {
+    AsPlan p;
+    AsState s;
+    if (!rir || !as_state(state, state_bytes, B, K, dry_rows, max_blocks, p, s)) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL(auralize_stream_response_kernel, dim3(af_grid(p.nH)), dim3(AF_THREADS), 0, (hipStream_t)stream, rir, s.ctrl, s.H, K,
+                       (int)p.Q, (int)p.nH, 1);
+    return (int)hipGetLastError();
+}
+
+int unetrir_auralize_stream_push(void* state, size_t state_bytes, int B, int K, int dry_rows, int max_blocks, const float* dry,
+                                 long long dry_stride, float* out, long long out_stride, int blocks, unetrir_stream_t stream) {
+    AsPlan p;
+    AsState s;
+    if (!out || !as_state(state, state_bytes, B, K, dry_rows, max_blocks, p, s)) return UNETRIR_EINVAL;
+    if (blocks < 1 || blocks > max_blocks) return UNETRIR_EINVAL;
+    const long long n = (long long)blocks * AF_P;
+    if (out_stride < n || (dry && !(dry_stride >= n || (dry_stride == 0 && dry_rows == 1)))) return UNETRIR_EINVAL;
+    hipLaunchKernelGGL(auralize_stream_spectra_kernel, dim3(af_grid((long long)dry_rows * blocks)), dim3(AF_THREADS), 0,
+                       (hipStream_t)stream, dry, dry_stride, (const AsCtrl*)s.ctrl, (const float*)s.carry, s.X, (int)p.S, blocks, dry_rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const int NG = (blocks + AF_G - 1) / AF_G;
+    hipLaunchKernelGGL(auralize_stream_render_kernel, dim3(af_grid((long long)B * NG)), dim3(AF_THREADS), 0, (hipStream_t)stream,
+                       (const AsCtrl*)s.ctrl, (const float4*)s.H, (const float4*)s.X, out, out_stride, (int)p.Q, (int)p.S, blocks, NG,
+                       dry_rows, B);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(auralize_stream_advance_kernel, dim3(dry_rows), dim3(AF_THREADS), 0, (hipStream_t)stream, dry, dry_stride, s.ctrl,
+                       s.carry, blocks);
+    return (int)hipGetLastError();
+}
 
 int unetrir_auralize_path_supported(int K) { return K >= 1 && K <= AF_MAXK ? 1 : 0; }
 

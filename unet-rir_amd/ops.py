@@ -934,6 +934,112 @@ def auralize_path_f32(rir, times_dev, dry, out, ws: Workspace = None):
                                                _stream()), "auralize_path")
 
 
+def auralize_stream_supported(K):
+    """Whether a stream takes impulse responses of K taps (1 <= K <= 16384)."""
+    return bool(_lib.lib().unetrir_auralize_stream_supported(int(K)))
+
+
+def auralize_stream_state_bytes(B, K, dry_rows, max_blocks):
+    """Bytes of a stream's device state: 64 + 16384 (2 B Q + dry_rows S) + 8192 dry_rows, Q = ceil(K / 2048), S = Q + max_blocks - 1
+    (0: arguments the calls refuse: dry_rows is 1 or B, 1 <= max_blocks <= 64)."""
+    return int(_lib.lib().unetrir_auralize_stream_state_bytes(int(B), int(K), int(dry_rows), int(max_blocks)))
+
+
+class AuralizeStreamState:
+    """The device state of one stream and the arguments it was sized for (include/unetrir.h).  buf: a uint8 tensor to use instead of a
+    new one - at least `auralize_stream_state_bytes` bytes, 16-byte aligned."""
+
+    def __init__(self, device, B, K, dry_rows, max_blocks, buf=None):
+        self.B, self.K, self.dry_rows, self.max_blocks = int(B), int(K), int(dry_rows), int(max_blocks)
+        if not auralize_stream_supported(self.K):
+            raise ValueError(f"auralize: impulse responses of {K} taps are not supported (1 ... 16384)")
+        self.need = auralize_stream_state_bytes(self.B, self.K, self.dry_rows, self.max_blocks)
+        if not self.need:
+            raise ValueError(f"auralize_stream: B = {B} >= 1, dry_rows = {dry_rows} in (1, B), max_blocks = {max_blocks} in 1 ... 64")
+        if buf is None:
+            buf = torch.empty(self.need, dtype=torch.uint8, device=device)
+        elif (not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous() or
+              buf.numel() < self.need or buf.data_ptr() % 16 or buf.device != torch.device(device)):
+            raise ValueError(f"auralize_stream: buf must be a contiguous uint8 tensor of at least {self.need} bytes on {device}, 16-byte aligned")
+        self.buf = buf
+        self.block = auralize_fft_block(self.K)
+
+    @property
+    def ptr(self):
+        return C.c_void_p(self.buf.data_ptr())
+
+    @property
+    def nbytes(self):
+        return self.buf.numel()
+
+
+def _stream_rir(state, rir, what):
+    if not isinstance(state, AuralizeStreamState):
+        raise ValueError(f"{what}: state must be an AuralizeStreamState")
+    if not isinstance(rir, torch.Tensor):
+        raise ValueError(f"{what}: rir must be a tensor")
+    if tuple(rir.shape) != (state.B, state.K):
+        raise ValueError(f"{what}: rir must have the shape the stream was made for, {(state.B, state.K)}, not {tuple(rir.shape)}")
+    if rir.dtype != torch.float32:
+        raise ValueError(f"{what}: rir must be float32, not {rir.dtype}")
+    if not rir.is_contiguous():
+        raise ValueError(f"{what}: rir must be contiguous")
+    if not rir.is_cuda or rir.device != state.buf.device:
+        raise ValueError(f"{what}: rir must be a CUDA tensor on the device of the state (there is no CPU path)")
+
+
+def auralize_stream_init(state, rir):
+    """Clears the stream (block 0, silence before it) and makes rir fp32 [B, K] its response: a memset and one launch on the current
+    stream."""
+    _stream_rir(state, rir, "auralize_stream_init")
+    check(_lib.lib().unetrir_auralize_stream_init(state.ptr, state.nbytes, _p(rir), state.B, state.K, state.dry_rows, state.max_blocks,
+                                                  _stream()), "auralize_stream_init")
+
+
+def auralize_stream_update(state, rir):
+    """A new response rir fp32 [B, K], faded in across the first block of the next push: one launch on the current stream.  A second
+    update before a push replaces the first."""
+    _stream_rir(state, rir, "auralize_stream_update")
+    check(_lib.lib().unetrir_auralize_stream_update(state.ptr, state.nbytes, _p(rir), state.B, state.K, state.dry_rows, state.max_blocks,
+                                                    _stream()), "auralize_stream_update")
+
+
+def auralize_stream_push_f32(state, dry, out):
+    """The next blocks of the stream: out fp32 [B, blocks 2048], 1 <= blocks <= max_blocks, from as many new dry samples - dry fp32
+    [blocks 2048] (dry_rows = 1) or [dry_rows, blocks 2048], or None for zeros (the tail after the last sample).  Three launches on the
+    current stream, whose arguments do not change from call to call: a captured push renders the next blocks at every replay, from
+    what dry holds then.  dry and out may be column slices of larger tensors: their rows must be dense (stride 1), not the tensors."""
+    if not isinstance(state, AuralizeStreamState):
+        raise ValueError("auralize_stream_push: state must be an AuralizeStreamState")
+    if not isinstance(out, torch.Tensor) or (dry is not None and not isinstance(dry, torch.Tensor)):
+        raise ValueError("auralize_stream_push: dry (or None) and out must be tensors")
+    P = state.block
+    if out.dim() != 2 or out.shape[0] != state.B or out.shape[1] < P or out.shape[1] % P or out.shape[1] // P > state.max_blocks:
+        raise ValueError(f"auralize_stream_push: out must be [{state.B}, blocks {P}] with 1 <= blocks <= {state.max_blocks}, not "
+                         f"{tuple(out.shape)}")
+    n = out.shape[1]
+    named = [(out, "out")]
+    stride = 0
+    if dry is not None:
+        want = (n,) if state.dry_rows == 1 and dry.dim() == 1 else (state.dry_rows, n)
+        if tuple(dry.shape) != want:
+            raise ValueError(f"auralize_stream_push: dry must be {want} for out {tuple(out.shape)} and dry_rows = {state.dry_rows}, not "
+                             f"{tuple(dry.shape)}")
+        named.append((dry, "dry"))
+        stride = dry.stride(0) if dry.dim() == 2 and state.dry_rows > 1 else 0
+    for t, what in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"auralize_stream_push: {what} must be float32, not {t.dtype}")
+        if t.stride(-1) != 1 or (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < n):
+            raise ValueError(f"auralize_stream_push: {what} must be contiguous along its rows, and the rows must not overlap")
+    for t, what in named:
+        if not t.is_cuda or t.device != state.buf.device:
+            raise ValueError(f"auralize_stream_push: {what} must be a CUDA tensor on the device of the state (there is no CPU path)")
+    out_stride = out.stride(0) if state.B > 1 else n
+    check(_lib.lib().unetrir_auralize_stream_push(state.ptr, state.nbytes, state.B, state.K, state.dry_rows, state.max_blocks, _p(dry),
+                                                  stride, _p(out), out_stride, n // P, _stream()), "auralize_stream_push")
+
+
 def resample_supported(L, M, zeros):
     """Whether the resampler takes the reduced ratio L / M with `zeros` zero crossings to each side (include/unetrir.h)."""
     return bool(_lib.lib().unetrir_resample_supported(int(L), int(M), int(zeros)))
